@@ -15,6 +15,11 @@ launcher, WORLD_SIZE must equal --gpus, and the RCCL communicator's own rank cou
 
 Rank 0 prints ONE JSON line; `value` is the whole-job aggregate (tokens/s over all ranks),
 timed over exactly K steps bracketed by barrier + device synchronize, max over ranks.
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  ``--dump-outputs DIR``
+also writes the loss and the parameters after the last timed step as DIR/<name>.npy (seeded inputs and
+weights: two builds can be compared output for output).  ``--full`` is where anything measured beyond
+the headline figure belongs; nothing is today.
 """
 from __future__ import annotations
 
@@ -51,6 +56,24 @@ def _launch_plan(K: int):
             if best is None or cost < best[0] - 1e-9:
                 best = (cost, G, lead)
     return best[1], best[2]
+
+
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def _dump_outputs(path: str, arrays) -> None:
+    """Write each array as path/<name>.npy in float32.  If they hold more than DUMP_BUDGET_BYTES in
+    all, every array is cut to the same fraction of its elements: a sorted sample of flat indices drawn
+    with a fixed seed, so two runs with the same arguments keep the same elements."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * a.size for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, a.size * DUMP_BUDGET_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main() -> int:
@@ -96,6 +119,16 @@ def main() -> int:
                          "field), for A/B runs; repeatable")
     ap.add_argument("--launch-timeout", type=float, default=1800.0,
                     help="self-launch mode: wall-clock limit of the whole N-rank job in s")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last timed step left a caller -- the "
+                         "loss and every parameter tensor (state_dict) -- as DIR/<name>.npy in float32 "
+                         "(~7 MB at the headline preset).  Inputs and initial weights are seeded, so two "
+                         "builds run with the same arguments can be compared output for output.")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures or checks beyond its headline figure.  "
+                         "Nothing does today: a plain run already only sets up, warms up, times --steps "
+                         "steps and prints the result line (comparators and configurations are options of "
+                         "their own: --impl, --preset, --variant; bench/ holds the other benchmarks)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
@@ -174,10 +207,11 @@ def main() -> int:
         if not (ctx.device.type == "cuda" and hasattr(tr, "steps")):
             G, lead = 1, 0
         final_loss = lambda: tr.loss()                  # noqa: E731
+        state = lambda: tr.state_dict()                 # noqa: E731
         plan = tr.t.plan() if hasattr(tr, "t") else "cpu"
     else:
         comm = None
-        step, final_loss = _torch_gru_step(cfg, ctx, pool)
+        step, final_loss, state = _torch_gru_step(cfg, ctx, pool)
         plan = "torch.nn.GRU (MIOpen)"
 
     def sync():
@@ -214,6 +248,12 @@ def main() -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     loss = final_loss()
+    if args.dump_outputs:
+        # state() is collective with a sharded optimiser (the masters are gathered): every rank calls it
+        arrays = {"loss": np.asarray([loss], dtype=np.float32)}
+        arrays.update({k: v.detach().float().cpu().numpy() for k, v in state().items()})
+        if ctx.is_main:
+            _dump_outputs(args.dump_outputs, arrays)
     if G > 1 and hasattr(tr, "t"):
         # what actually ran: steps() falls back to one graph per step (loudly) if a capture fails
         G = tr.t.graph_steps()
@@ -264,6 +304,7 @@ def _torch_gru_step(cfg, ctx, pool):
             return self.fc(h)
 
     dev = ctx.device
+    torch.manual_seed(cfg.seed)   # the same initial weights on every run (--dump-outputs compares builds)
     m = Model().to(dev)
     model = DDP(m, device_ids=[dev.index]) if ctx.world > 1 else m
     opt = torch.optim.Adam(model.parameters(), lr=cfg.lr)
@@ -280,7 +321,7 @@ def _torch_gru_step(cfg, ctx, pool):
         opt.step()
         state["loss"] = loss.detach()
 
-    return step, lambda: float(state["loss"])
+    return step, lambda: float(state["loss"]), m.state_dict
 
 
 if __name__ == "__main__":

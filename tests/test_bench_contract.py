@@ -45,6 +45,52 @@ def test_bench_contract_world1():
     _lines([sys.executable, "bench.py", "--preset", "cpu_tiny", "--steps", "3", "--warmup", "1"], 1)
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """``--dump-outputs DIR`` writes the loss and every parameter after the last timed step as float32
+    .npy files; the inputs and initial weights are seeded, so a second run with the same arguments
+    (here also with ``--full``, which adds nothing to the outputs) writes the same arrays."""
+    import numpy as np
+    from gru_mpi_cuda_amd.config import preset
+    from gru_mpi_cuda_amd.models.params import init_params, param_shapes
+    cmd = [sys.executable, "bench.py", "--preset", "cpu_tiny", "--steps", "3", "--warmup", "1"]
+    ra = _lines(cmd + ["--dump-outputs", str(tmp_path / "a")], 1)
+    _lines(cmd + ["--full", "--dump-outputs", str(tmp_path / "b")], 1)
+    cfg = preset("cpu_tiny")
+    shapes = {k: tuple(v) for k, v in param_shapes(cfg).items()}
+    assert {f.name for f in (tmp_path / "a").iterdir()} == {k + ".npy" for k in [*shapes, "loss"]}
+    p0 = init_params(cfg)
+    for name in [*shapes, "loss"]:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+        if name != "loss":
+            assert a.shape == shapes[name]
+            assert not np.array_equal(a, p0[name].numpy()), name    # the trained weights, not the initial ones
+    assert round(float(np.load(tmp_path / "a" / "loss.npy")[0]), 4) == ra["final_loss"]
+
+
+def test_bench_dump_outputs_samples_past_its_budget(tmp_path, monkeypatch):
+    """More than the budget in all: every array keeps the same fixed, seeded fraction of its elements."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_main", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 1000)
+    rng = np.random.default_rng(1)
+    arrays = {"w": rng.standard_normal((50, 60)), "b": rng.standard_normal(1000).astype(np.float32)}
+    bench._dump_outputs(str(tmp_path / "a"), arrays)
+    bench._dump_outputs(str(tmp_path / "b"), arrays)
+    total = 0
+    for name, src in arrays.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.size == src.size // 4 and np.array_equal(a, b)
+        assert np.isin(a, src.astype(np.float32)).all()
+        total += a.nbytes
+    assert total <= 4 * 1000
+
+
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_contract_torchrun_gloo(world):
     """The driver's multi-GPU form (torchrun, one rank per device, up to a whole 8-GPU node),
