@@ -2,6 +2,7 @@
 
     python -m gru_mpi_cuda_amd.cli train    --preset h512 --steps 200 --ckpt out/model.bin
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --seed 1
+    python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
 
@@ -143,11 +144,14 @@ def cmd_train(args) -> int:
     data = make_stream(cfg.batch // ctx.world, cfg.seq, cfg.sos, cfg.eos, seed=cfg.seed * 1000 + ctx.rank + start,
                        max_len=cfg.max_len, path=args.data)
     mw = MetricsWriter(args.metrics)
+    evaluate = _Evaluator(args.eval_data, cfg, ctx.device.type == "cuda") if args.eval_data else None
     timer = StepTimer()
     for it in range(start, start + args.steps):
         tr.step(*data.next())
         timer.tick()
-        if (it + 1) % args.log_every == 0 or it + 1 == start + args.steps:
+        last = it + 1 == start + args.steps
+        do_eval = evaluate is not None and (last or (args.eval_every > 0 and (it + 1) % args.eval_every == 0))
+        if (it + 1) % args.log_every == 0 or last or do_eval:
             loss = tr.loss()                # synchronises
             r = timer.rate()
             tok_s = r["steps_per_s"] * cfg.batch * cfg.seq
@@ -165,7 +169,12 @@ def cmd_train(args) -> int:
                         # upper bound of the step share the collectives take if none of it overlaps
                         rec["allreduce_step_fraction_max"] = cs["allreduce_ms_standalone"] / rec["ms_per_step"]
                 timer.rate()                # the probe above is not training time
-            log(f"step {it + 1} loss {loss:.4f} {tok_s / 1e6:.2f} M char-tokens/s")
+            ev = ""
+            if do_eval:
+                rec.update(evaluate(tr))
+                ev = f" eval nll {rec['eval_nll']:.4f} ppl {rec['eval_ppl']:.2f} top1 {rec['eval_top1']:.3f}"
+                timer.rate()                # nor is the evaluation
+            log(f"step {it + 1} loss {loss:.4f} {tok_s / 1e6:.2f} M char-tokens/s{ev}")
             mw.write(**rec)
         if args.ckpt and args.save_every and (it + 1) % args.save_every == 0:
             save_checkpoint(tr, args.ckpt, args.fmt)
@@ -213,6 +222,89 @@ def cmd_generate(args) -> int:
     return 0
 
 
+def _escape(name: str) -> str:
+    return "".join(c if c.isprintable() else f"\\x{ord(c):02x}" for c in name)
+
+
+def _read_names(path: str) -> list:
+    """One name per line, bytes kept as they are (latin-1); an empty line is the empty name."""
+    with open(path, "rb") as f:
+        lines = f.read().split(b"\n")
+    if lines and not lines[-1]:
+        lines.pop()                         # the file's final newline
+    return [ln[:-1] if ln.endswith(b"\r") else ln for ln in lines]
+
+
+def cmd_score(args) -> int:
+    """Teacher-forced log-likelihood of names under a checkpoint: one `name<TAB>logp<TAB>n_tok` line
+    per name, a JSON summary on stderr."""
+    import torch
+    from .engine import generator as G
+    from .models import cpu_ref
+    from .utils import ckpt
+    fmt = args.fmt
+    if fmt == "auto":
+        fmt = "gen" if os.path.exists(args.ckpt + ".json") else "ref"
+    cfg, params = ckpt.load(args.ckpt, _cfg_from(args) if fmt == "ref" else None, fmt)
+    over = {k: getattr(args, k) for k in ("max_len", "sos", "eos") if getattr(args, k) is not None}
+    cfg = cfg.replace(**over)
+    ML = cfg.max_len
+    if args.raw:
+        raw = np.fromfile(args.raw, dtype=np.uint8)
+        if raw.size % (ML + 1):
+            raise SystemExit(f"{args.raw}: {raw.size} bytes is not a whole number of {ML + 1}-byte rows")
+        rows = raw.reshape(-1, ML + 1)
+    else:
+        rows = G.encode_names(_read_names(args.names), cfg)
+    t0 = time.perf_counter()
+    if args.cpu or not torch.cuda.is_available():
+        tok, name, n_tok, rank = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows)
+        res = G.ScoreResult(tok, rank, name, n_tok)
+    else:
+        res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0]))).score(rows)
+    dt = time.perf_counter() - t0
+    lines = []
+    for r, lp, nt in zip(rows, res.name_logp, res.n_tok):
+        # the scored chars without the EOS (a row cut off at max_len has none)
+        k = int(nt) - 1 if r[int(nt) - 1] == cfg.eos else int(nt)
+        lines.append(f"{_escape(bytes(r[:k]).decode('latin-1'))}\t{float(lp):.6f}\t{int(nt)}")
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    else:
+        sys.stdout.write(text)
+    print(json.dumps({"names": int(rows.shape[0]), "tokens": res.tokens, "nll_per_char": res.nll_per_char,
+                      "perplexity": res.perplexity, "top1": res.top1, "seconds": round(dt, 4)}), file=sys.stderr)
+    return 0
+
+
+class _Evaluator:
+    """Held-out evaluation for `train --eval-data`: the file is read once; every call scores the
+    trainer's current weights on all of it (each rank the whole file: no collective of its own)."""
+
+    def __init__(self, path: str, cfg, on_gpu: bool):
+        from .engine import generator as G
+        self.G, self.cfg, self.gen = G, cfg, None
+        self.rows = G.encode_names(_read_names(path), cfg)
+        self.on_gpu = on_gpu
+
+    def __call__(self, tr) -> dict:
+        from .models import cpu_ref
+        params = tr.state_dict()           # collective with shard_optim=2: every rank calls it
+        if self.on_gpu:
+            if self.gen is None:
+                self.gen = self.G.HipGenerator(self.cfg, params, max_batch=max(64, min(4096, self.rows.shape[0])))
+            else:
+                self.gen.load_state(params)
+            res = self.gen.score(self.rows)
+        else:
+            tok, name, n_tok, rank = cpu_ref.score({k: v.float() for k, v in params.items()}, self.cfg, self.rows)
+            res = self.G.ScoreResult(tok, rank, name, n_tok)
+        return dict(eval_nll=res.nll_per_char, eval_ppl=res.perplexity, eval_top1=res.top1,
+                    eval_names=int(self.rows.shape[0]))
+
+
 def cmd_info(args) -> int:
     import torch
     info = {"torch": torch.__version__, "hip": torch.version.hip, "gpu": torch.cuda.is_available()}
@@ -238,7 +330,21 @@ def main(argv=None) -> int:
     t.add_argument("--cpu", action="store_true", help="force the CPU reference path")
     t.add_argument("--data", default=None,
                    help="names file, one per line (default: synthetic names); read by the native loader")
+    t.add_argument("--eval-data", dest="eval_data", default=None,
+                   help="held-out names file, one per line: scored every --eval-every steps and at the end "
+                        "(eval_nll / eval_ppl / eval_top1 in the log line and the metrics record)")
+    t.add_argument("--eval-every", dest="eval_every", type=int, default=0)
     _add_model_args(t)
+    sc = sub.add_parser("score", help="teacher-forced log-likelihood of names under a checkpoint")
+    sc.add_argument("--ckpt", required=True)
+    sc.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")
+    src = sc.add_mutually_exclusive_group(required=True)
+    src.add_argument("--names", default=None, help="names file, one per line")
+    src.add_argument("--raw", default=None, help="raw N x (MAX_LEN+1) bytes, as `generate --raw-out` writes")
+    sc.add_argument("--out", default=None, help="name, log-prob and token count per line, tab-separated")
+    sc.add_argument("--cpu", action="store_true", help="cpu_ref.score in fp32 instead of the HIP generator")
+    sc.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
+    _add_model_args(sc)
     g = sub.add_parser("generate", help="namegen_initialize / namegen / namegen_finalize")
     g.add_argument("--ckpt", required=True)
     g.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")
@@ -263,7 +369,7 @@ def main(argv=None) -> int:
         return bench.main()
     if rest:
         ap.error(f"unrecognized arguments: {rest}")
-    return {"train": cmd_train, "generate": cmd_generate, "info": cmd_info}[args.cmd](args)
+    return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "info": cmd_info}[args.cmd](args)
 
 
 if __name__ == "__main__":

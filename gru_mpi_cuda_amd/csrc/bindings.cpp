@@ -152,6 +152,12 @@ PYBIND11_MODULE(_C, m) {
       .def("generate", [](Generator& g, uintptr_t rf, int N, uintptr_t out, uintptr_t s) {
         g.generate(Pp<const float>(rf), N, Pp<unsigned char>(out), S(s));
       })
+      .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
+                       uintptr_t n_tok, uintptr_t s) {
+        g.score(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
+                Pp<int>(n_tok), S(s));
+      })
+      .def("score_workspace_bytes", &Generator::score_workspace_bytes)
       .def("set_use_graph", &Generator::set_use_graph)
       .def("read_error", &Generator::read_error)
       .def("set_probe", [](Generator& g, uintptr_t p) { g.set_probe(Pp<float>(p)); })

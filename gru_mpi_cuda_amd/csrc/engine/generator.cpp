@@ -76,6 +76,7 @@ bool Generator::uses_persist(int n) const {
 
 Generator::~Generator() {
   graphs_.clear();
+  sgraphs_.clear();
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
 }
@@ -334,6 +335,115 @@ void Generator::generate(const float* rf, int N, unsigned char* out, hipStream_t
       if (d_.fp32) record_steps_f32(n, s); else record_steps(n, s);
     }
     HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ---------------------------------------------------------------------------------- scoring
+// Buffers of the teacher-forced schedule, sized for Bmax_ names: a generator that never scores
+// never allocates them.
+void Generator::score_alloc() {
+  if (sready_) return;
+  const size_t V = d_.V, H = d_.H, ML = d_.max_len, B = Bmax_;
+  const size_t slab_rows = std::max<size_t>(B, kF32SlabRows), all_rows = std::max<size_t>(ML * B, kF32SlabRows);
+  const size_t orows = sarena_.reserve(B * (ML + 1)), on = sarena_.reserve(256);
+  const size_t oids = sarena_.reserve(ML * B * 4), otgt = sarena_.reserve(ML * B * 4), ont = sarena_.reserve(B * 4);
+  const size_t oh0 = sarena_.reserve(B * H * 4);
+  std::vector<size_t> ohs;
+  for (int l = 0; l < d_.L; ++l) ohs.push_back(sarena_.reserve(ML * B * H * 4));
+  const size_t ogh = sarena_.reserve(slab_rows * 3 * H * 4);
+  const size_t ogi = d_.L > 1 ? sarena_.reserve(ML * B * 3 * H * 4) : 0;
+  const size_t olg = sarena_.reserve(all_rows * V * 4);
+  const size_t otok = sarena_.reserve(B * ML * 4), ornk = sarena_.reserve(B * ML * 4);
+  const size_t onm = sarena_.reserve(B * 4), onto = sarena_.reserve(B * 4);
+  sarena_.commit();
+  srows_ = sarena_.get<unsigned char>(orows); sn_ = sarena_.get<int>(on);
+  sids_ = sarena_.get<int>(oids); stgt_ = sarena_.get<int>(otgt); sntok_ = sarena_.get<int>(ont);
+  sh0_ = sarena_.get<float>(oh0);
+  for (int l = 0; l < d_.L; ++l) shs_.push_back(sarena_.get<float>(ohs[l]));
+  sgh_ = sarena_.get<float>(ogh); sgi_ = d_.L > 1 ? sarena_.get<float>(ogi) : nullptr;
+  slogits_ = sarena_.get<float>(olg);
+  stok_ = sarena_.get<float>(otok); srank_ = sarena_.get<int>(ornk);
+  sname_ = sarena_.get<float>(onm); sntok_out_ = sarena_.get<int>(onto);
+  sready_ = true;
+}
+
+// The schedule for a padded batch of Bp rows (the name count is read from sn_ by score_prep, so one
+// recording serves every count that pads to Bp): 2 L ML + L + 2 launches, a single chain.
+void Generator::record_score(int Bp, hipStream_t s) {
+  const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
+  const int cap = std::max(Bmax_, kF32SlabRows);
+  ScorePrepArgs p;
+  p.rows = srows_; p.n_dev = sn_; p.ids = sids_; p.tgt = stgt_; p.ntok = sntok_; p.err = err_;
+  p.Bp = Bp; p.ML = ML; p.V = V; p.sos = d_.sos; p.eos = d_.eos;
+  score_prep(p, s);
+  const long step = (long)Bp * H;   // one step's h rows
+  for (int l = 0; l < L; ++l) {
+    const std::string k = std::to_string(l);
+    if (l > 0) {   // the layer's input projection for every step at once: Gi = h_below W_ih^T + b_ih
+      GemmF32Args g;
+      g.A = shs_[l - 1]; g.lda = H; g.B = P("weight_ih_l" + k); g.ldb = H; g.C = sgi_; g.ldc = 3 * H;
+      g.bias = P("bias_ih_l" + k); g.M = ML * Bp; g.N = 3 * H; g.K = H;
+      gemm_f32_nt(g, s);
+    }
+    for (int st = 0; st < ML; ++st) {
+      const float* hprev = st == 0 ? sh0_ : shs_[l] + (st - 1) * step;
+      GemmF32Args g;   // gh = h W_hh^T + b_hh (bias in slab 0; the gates sum the slabs in order)
+      g.A = hprev; g.lda = H; g.B = P("weight_hh_l" + k); g.ldb = H; g.C = sgh_; g.ldc = 3 * H;
+      g.bias = P("bias_hh_l" + k); g.M = Bp; g.N = 3 * H; g.K = H;
+      g.splits = f32_splits(Bp, 3 * H, H, cap); g.slab = (long)Bp * 3 * H;
+      gemm_f32_nt(g, s);
+      GruGatesF32Args a;
+      if (l == 0) { a.P = Ptab32_; a.ids = sids_ + (long)st * Bp; }
+      else a.Gi = sgi_ + (long)st * Bp * 3 * H;
+      a.Gh = sgh_; a.gh_splits = g.splits; a.gh_slab = g.slab;
+      a.hprev = hprev; a.hout = shs_[l] + st * step;
+      a.Bp = Bp; a.H = H; a.V = V; a.err = err_;
+      gru_gates_f32(a, s);
+    }
+  }
+  GemmF32Args g;   // every step's logits in one product
+  g.A = shs_[L - 1]; g.lda = H; g.B = P("fc.weight"); g.ldb = H; g.C = slogits_; g.ldc = V;
+  g.bias = P("fc.bias"); g.M = ML * Bp; g.N = V; g.K = H;
+  g.splits = f32_splits(ML * Bp, V, H, std::max(ML * Bmax_, kF32SlabRows)); g.slab = (long)ML * Bp * V;
+  gemm_f32_nt(g, s);
+  ScoreLogprobArgs q;
+  q.logits = slogits_; q.splits = g.splits; q.slab = g.slab; q.tgt = stgt_; q.ntok = sntok_;
+  q.tok_logp = stok_; q.rank = srank_; q.name_logp = sname_; q.ntok_out = sntok_out_;
+  q.Bp = Bp; q.V = V; q.ML = ML;
+  score_logprob_f32(q, s);
+  HIP_LAUNCH_CHECK();
+}
+
+void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok,
+                      hipStream_t s) {
+  GK_TRACE("gk.score");
+  if (N <= 0) return;
+  const int ML = d_.max_len;
+  if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::score needs max_len <= 64 and vocab <= 512");
+  score_alloc();   // first call: allocates (and synchronises) before anything is captured
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
+  err_clean_ = false;
+  for (int start = 0; start < N; start += Bmax_) {
+    const int n = std::min(Bmax_, N - start);
+    const int Bp = rup(n, 64);
+    score_set_count(sn_, n, s);
+    HIP_CHECK(hipMemcpyAsync(srows_, rows + (size_t)start * (ML + 1), (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      auto& g = sgraphs_[Bp];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_score(Bp, cap_);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_score(Bp, s);
+    }
+    HIP_CHECK(hipMemcpyAsync(tok_logp + (size_t)start * ML, stok_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(rank + (size_t)start * ML, srank_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(name_logp + start, sname_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + start, sntok_out_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

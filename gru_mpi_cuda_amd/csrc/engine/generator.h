@@ -32,6 +32,14 @@ class Generator {
   void refresh_weights(hipStream_t s);   // bf16 weights + layer-0 table (call after params change)
   // rf: device [N][max_len] uniforms of THIS rank's names; out: device [N][max_len+1]
   void generate(const float* rf, int N, unsigned char* out, hipStream_t s);
+  // Teacher-forced scoring of N output rows (device [N][max_len+1], the generate() format): per token
+  // log softmax(logits)[target] and the target's rank, per name their sum and the token count (all
+  // device pointers: tok_logp / rank [N][max_len], name_logp / n_tok [N]).  Always the exact-fp32
+  // arithmetic, whatever GenDims::fp32 says.  Layer-major schedule (the targets are known): per layer
+  // ONE input-projection GEMM over all max_len * Bp rows, then its steps; ONE logits GEMM; one
+  // log-prob launch.  Buffers are allocated on the first call.
+  void score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok, hipStream_t s);
+  size_t score_workspace_bytes() const { return sarena_.bytes(); }   // 0 until the first score()
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
   void set_probe(float* probs) { probe_ = probs; graphs_.clear(); }
@@ -65,6 +73,8 @@ class Generator {
                   float* C, hipStream_t s);
   bool split3() const { return d_.fp32 == 2; }
   void reset_batch(int Bp, bool bf16, hipStream_t s);
+  void score_alloc();
+  void record_score(int Bp, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
   GenDims d_;
@@ -102,6 +112,17 @@ class Generator {
   float* pws_ = nullptr;        // persistent path: exchange buffers (two sets, by launch parity)
   int ppar_ = -1;               // the next persistent launch's set; -1: workspace not filled yet
   unsigned* psync_ = nullptr;   // persistent path: flags + done counter (self-cleaning, arena-zeroed)
+  // scoring (second arena, committed by the first score() call)
+  Arena sarena_;
+  bool sready_ = false;
+  std::map<int, std::unique_ptr<Graph>> sgraphs_;   // keyed by the padded batch Bp
+  unsigned char* srows_ = nullptr;              // [Bmax][ML + 1] staged input rows
+  int *sn_ = nullptr, *sids_ = nullptr, *stgt_ = nullptr, *sntok_ = nullptr;   // N word, [ML][Bmax] x2, [Bmax]
+  float* sh0_ = nullptr;                        // [Bmax][H] zeros (arena-zeroed, never written): h before step 0
+  std::vector<float*> shs_;                     // per layer [ML][Bp][H]: every step's h
+  float *sgh_ = nullptr, *sgi_ = nullptr, *slogits_ = nullptr;   // step product slabs, [ML*Bp][3H], [ML*Bp][V] slabs
+  float *stok_ = nullptr, *sname_ = nullptr;    // staged outputs [Bmax][ML], [Bmax]
+  int *srank_ = nullptr, *sntok_out_ = nullptr;
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

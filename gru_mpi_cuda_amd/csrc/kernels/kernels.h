@@ -362,6 +362,35 @@ long gen_persist_ws_floats(int H, int L, int V, int ML);
 void gen_persist_fill_ws(float* ws, int H, int L, int V, int ML, hipStream_t s);   // both sets -> kEmpty
 long gen_persist_sync_words(int L);
 void gen_persist_f32(const GenPersistArgs& a, hipStream_t s);
+// Teacher-forced scoring of output rows (score.hip).  A row's token count n_tok = index of the first
+// EOS byte among its first ML bytes + 1, else ML; step l < n_tok has input SOS (l = 0) or c[l-1] and
+// target c[l].
+struct ScorePrepArgs {             // rows -> time-major ids / targets and n_tok, as ONE kernel node
+  const unsigned char* rows = nullptr;   // [N][ML + 1]
+  const int* n_dev = nullptr;      // nullable: N read from this device word (a graph shared by every N of a Bp)
+  int* ids = nullptr;              // [ML][Bp] inputs; masked steps and pad rows (b >= N): sos
+  int* tgt = nullptr;              // [ML][Bp] targets; -1 when masked or a pad row
+  int* ntok = nullptr;             // [Bp]; pad rows 0
+  unsigned* err = nullptr;         // bit 4 set (and the byte clamped) on a target >= V at an unmasked position
+  int N = 0, Bp = 0, ML = 0, V = 0, sos = 0, eos = 0;
+};
+void score_prep(const ScorePrepArgs& a, hipStream_t s);
+// n_dev[0] = n as a kernel on the stream, ahead of a replayed graph whose score_prep reads it (a
+// kernel, not a memset: ordered against the graph's first node like any other launch)
+void score_set_count(int* n_dev, int n, hipStream_t s);
+struct ScoreLogprobArgs {          // per token: log softmax(logits)[target] and the target's rank; per name: the sum
+  const float* logits = nullptr;   // [ML * Bp][V], row l * Bp + b; rows of masked tokens are not read
+  int splits = 1; long slab = 0;   // split-K slabs of the logits, summed in fixed order
+  const float* bias = nullptr;     // nullable: added after the slab sum
+  const int* tgt = nullptr;        // [ML][Bp]
+  const int* ntok = nullptr;       // [Bp]
+  float* tok_logp = nullptr;       // [Bp][ML]; masked positions 0
+  int* rank = nullptr;             // [Bp][ML]: logits above the target's (ties: lower index first); masked -1
+  float* name_logp = nullptr;      // [Bp]: the tokens' sum in step order
+  int* ntok_out = nullptr;         // [Bp]
+  int Bp = 0, V = 0, ML = 0;       // V % 64 == 0, V <= 512, ML <= 64
+};
+void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------ generic GEMM
 // C[M][N] (+)= A[M][K] · B[N][K]^T  (bf16 in, fp32 accumulate), both operands K-contiguous.

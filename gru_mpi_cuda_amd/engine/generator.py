@@ -18,6 +18,7 @@ are not scattered at all -- every rank reads only its own slice of the caller's 
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Dict, Optional
 
 import numpy as np
@@ -87,6 +88,93 @@ class HipGenerator:
         rf = torch.from_numpy(np.ascontiguousarray(rfloats[start * ML:(start + N) * ML], dtype=np.float32))
         rf = rf.to(self.dev)
         return self.generate_device(rf, N).cpu().numpy()
+
+    def load_state(self, params: Dict[str, torch.Tensor]) -> None:
+        """New weights (cfg-shaped tensors) into the flat buffer; every derived copy and table follows."""
+        icfg = pad_config(self.cfg).replace(vocab=self.cfg.vocab)
+        if icfg != self.cfg:
+            params = pad_params(params, self.cfg, icfg)
+        self.flat.copy_(to_flat(icfg, params).to(self.dev))
+        self.g.refresh_weights(self._s())
+
+    def score(self, rows: np.ndarray) -> "ScoreResult":
+        """Teacher-forced log-likelihood of output rows ([N, MAX_LEN+1] or flat uint8, the format
+        ``generate`` writes; semantics: cpu_ref.score_inputs).  Always exact fp32 arithmetic, whatever
+        ``precision`` this generator samples with.  A byte >= vocab at a scored position raises
+        ValueError before anything is launched."""
+        ML = self.cfg.max_len
+        rows, n_tok, _, _ = cpu_ref.score_inputs(self.cfg, rows)
+        N = rows.shape[0]
+        if N == 0:
+            return ScoreResult(np.zeros((0, ML), np.float32), np.zeros((0, ML), np.int32),
+                               np.zeros(0, np.float32), np.zeros(0, np.int32))
+        r = torch.from_numpy(rows).to(self.dev)
+        tok = torch.empty(N, ML, dtype=torch.float32, device=self.dev)
+        rank = torch.empty(N, ML, dtype=torch.int32, device=self.dev)
+        name = torch.empty(N, dtype=torch.float32, device=self.dev)
+        nt = torch.empty(N, dtype=torch.int32, device=self.dev)
+        self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s())
+        err = self.g.read_error()   # synchronises
+        if err:
+            raise RuntimeError(f"HipGenerator.score: device error word {err}")
+        res = ScoreResult(tok.cpu().numpy(), rank.cpu().numpy(), name.cpu().numpy(), nt.cpu().numpy())
+        if not np.array_equal(res.n_tok, n_tok):
+            raise RuntimeError("HipGenerator.score: device token counts differ from the host's")
+        return res
+
+
+@dataclass
+class ScoreResult:
+    """``HipGenerator.score`` / ``cpu_ref.score`` output.  tok_logp [N, ML] (masked positions 0),
+    rank [N, ML] int32 (masked -1), name_logp [N], n_tok [N] int32; the summaries are computed in
+    float64 from tok_logp."""
+    tok_logp: np.ndarray
+    rank: np.ndarray
+    name_logp: np.ndarray
+    n_tok: np.ndarray
+
+    @property
+    def tokens(self) -> int:
+        return int(self.n_tok.sum())
+
+    @property
+    def nll_per_char(self) -> float:
+        return float(-self.tok_logp.astype(np.float64).sum() / max(self.tokens, 1))
+
+    @property
+    def perplexity(self) -> float:
+        return float(np.exp(self.nll_per_char))
+
+    @property
+    def top1(self) -> float:
+        return float((self.rank == 0).sum() / max(self.tokens, 1))
+
+
+def encode_names(names, cfg: GRUConfig) -> np.ndarray:
+    """Names (bytes, or str taken as latin-1) -> rows [N, MAX_LEN+1] uint8 in the ``generate`` format:
+    the chars, the EOS byte when the name is shorter than MAX_LEN (a name of exactly MAX_LEN chars has
+    none, as a generated one that was cut off), NUL padding.  Longer names, chars outside the
+    vocabulary and names that contain the EOS byte raise ValueError."""
+    ML = cfg.max_len
+    rows = np.zeros((len(names), ML + 1), dtype=np.uint8)
+    for i, nm in enumerate(names):
+        try:
+            b = nm.encode("latin-1") if isinstance(nm, str) else bytes(nm)
+        except UnicodeEncodeError as e:
+            raise ValueError(f"name {i} ({nm!r}) is not latin-1") from e
+        if len(b) > ML:
+            raise ValueError(f"name {i} ({nm!r}) has {len(b)} chars, more than max_len = {ML}")
+        a = np.frombuffer(b, dtype=np.uint8)
+        if (a >= cfg.vocab).any():
+            raise ValueError(f"name {i} ({nm!r}) holds a byte >= vocab ({cfg.vocab})")
+        if (a == cfg.eos).any():
+            raise ValueError(f"name {i} ({nm!r}) contains the EOS byte {cfg.eos}")
+        rows[i, :len(b)] = a
+        if len(b) < ML:
+            if cfg.eos >= cfg.vocab:
+                raise ValueError(f"eos {cfg.eos} outside the vocabulary of {cfg.vocab}")
+            rows[i, len(b)] = cfg.eos
+    return rows
 
 
 # --------------------------------------------------------------------------- 3-call API

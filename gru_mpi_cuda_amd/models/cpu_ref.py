@@ -197,6 +197,65 @@ class Adam:
             params[k] -= lr * upd
 
 
+# --------------------------------------------------------------------------- scoring
+def score_inputs(cfg: GRUConfig, rows: np.ndarray):
+    """Teacher-forced schedule of output rows ([N, MAX_LEN+1] or flat uint8, the ``generate`` format).
+
+    ``n_tok`` = index of the first EOS byte among c[0..ML-1] plus one, or ML when there is none -- the
+    generator's stopping rule (EOS written, then stop), which also covers ``eos == 0`` where EOS and
+    the NUL padding are the same byte.  Step l < n_tok has input SOS (l = 0) or c[l-1] and target
+    c[l]; later bytes are ignored.  Returns (rows [N, ML+1], n_tok [N] int32, x [N, ML] int64 with
+    masked steps = SOS, tgt [N, ML] int64 with masked steps = -1).  A byte >= vocab at an unmasked
+    position is a caller error (ValueError)."""
+    ML = cfg.max_len
+    rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, ML + 1)
+    if not 0 <= cfg.sos < cfg.vocab:
+        raise ValueError(f"sos {cfg.sos} outside the vocabulary of {cfg.vocab}")
+    c = rows[:, :ML].astype(np.int64)
+    is_eos = c == cfg.eos
+    n_tok = np.where(is_eos.any(1), is_eos.argmax(1) + 1, ML).astype(np.int32)
+    mask = np.arange(ML)[None, :] < n_tok[:, None]
+    if (c[mask] >= cfg.vocab).any():
+        b = int(np.argwhere(mask & (c >= cfg.vocab))[0][0])
+        raise ValueError(f"row {b} holds a byte >= vocab ({cfg.vocab}) among its {int(n_tok[b])} scored positions")
+    tgt = np.where(mask, c, -1)
+    x = np.full_like(c, cfg.sos)
+    x[:, 1:] = np.where(mask[:, 1:], c[:, :-1], cfg.sos)
+    return rows, n_tok, x, tgt
+
+
+def score(params: Params, cfg: GRUConfig, rows: np.ndarray):
+    """log P of output rows under the model, teacher-forced from a zero hidden state (score_inputs).
+
+    Returns numpy (tok_logp [N, ML], name_logp [N], n_tok [N] int32, rank [N, ML] int32) in the dtype
+    of ``params`` (fp64 params: the oracle).  tok_logp[l] = log softmax(logits_l)[c[l]]; rank[l] = the
+    number of j with logit_j > logit_target, or equal and j < target (0: the arg-max is the target);
+    name_logp = the tokens' sum in step order.  Masked positions: tok_logp 0, rank -1.
+    exp(name_logp) is the probability that ``generate`` emits exactly that row."""
+    rows, n_tok, x, tgt = score_inputs(cfg, rows)
+    N, ML = tgt.shape
+    dt = params["fc.weight"].dtype
+    npdt = np.float64 if dt == torch.float64 else np.float32
+    if N == 0:
+        return (np.zeros((0, ML), npdt), np.zeros(0, npdt), n_tok, np.zeros((0, ML), np.int32))
+    logits = forward(params, cfg, torch.from_numpy(x))
+    if dt != torch.float64:
+        logits = logits.to(torch.float32)
+    t = torch.from_numpy(tgt)
+    mask = t >= 0
+    tc = t.clamp_min(0).unsqueeze(-1)
+    lp = torch.log_softmax(logits, -1).gather(-1, tc).squeeze(-1)
+    lp = torch.where(mask, lp, torch.zeros_like(lp))
+    xt = logits.gather(-1, tc)
+    j = torch.arange(cfg.vocab).view(1, 1, -1)
+    rank = ((logits > xt) | ((logits == xt) & (j < tc))).sum(-1)
+    rank = torch.where(mask, rank, torch.full_like(rank, -1))
+    name = torch.zeros(N, dtype=lp.dtype)
+    for l in range(ML):   # step order, as the device sums
+        name = name + lp[:, l]
+    return lp.numpy(), name.numpy(), n_tok, rank.numpy().astype(np.int32)
+
+
 # --------------------------------------------------------------------------- generation
 def sample_inverse_cdf(prob: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
     """The reference's ``random_select`` (namegensf.cu:322-333): first i with an fp32
