@@ -368,12 +368,17 @@ PYBIND11_MODULE(_C, m) {
     a.cnt = GP(unsigned, d, "cnt"); a.err = GP(unsigned, d, "err");
     a.dbg = GP(unsigned long long, d, "dbg"); a.allow_local = get<int>(d, "allow_local", 1);
     a.xring = get<int>(d, "xring", 0);
+    a.s16 = GP(u16, d, "s16");
+    a.zero_next = GP(unsigned, d, "zero_next"); a.zero_words = get<long>(d, "zero_words", 0);
     a.T = get<int>(d, "T", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
     if (!gru_fwd_seq_supported(a.H, a.Bp)) throw std::runtime_error("fwd_seq: shape not supported");
     gru_fwd_seq(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("bwd_seq_big_supported", &gru_bwd_seq_big_supported);
+  m.def("bwd_seq_big_part_floats", &gru_bwd_seq_big_part_floats);
+  m.def("bwd_seq16_supported", &gru_bwd_seq16_supported);
+  m.def("seq_flag_words", &seq_flag_words);
   m.def("bwd_seq", [](py::dict d, uintptr_t s) {
     SeqBwdArgs a;
     a.dy = GP(const float, d, "dy");
@@ -388,7 +393,16 @@ PYBIND11_MODULE(_C, m) {
     a.dP_part = GP(float, d, "dP_part"); a.V = get<int>(d, "V", 0);
     a.cnt = GP(unsigned, d, "cnt"); a.err = GP(unsigned, d, "err"); a.dbg = GP(unsigned long long, d, "dbg");
     a.allow_local = get<int>(d, "allow_local", 1); a.xring = get<int>(d, "xring", 0);
+    a.s16 = GP(const u16, d, "s16"); a.part = GP(float, d, "part");
+    a.dl = GP(const u16, d, "dl"); a.WfcT = GP(const u16, d, "WfcT");
+    a.dgiT_n_only = get<int>(d, "dgiT_n_only", 0);
+    a.zero_next = GP(unsigned, d, "zero_next"); a.zero_words = get<long>(d, "zero_words", 0);
     a.T = get<int>(d, "T", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
+    if (get<int>(d, "big", 0)) {   // the large-H split-K backward (gru_seq_big.hip): its own argument checks throw
+      gru_bwd_seq_big(a, S(s));
+      HIP_LAUNCH_CHECK();
+      return;
+    }
     // "unchecked": skip the co-residency query and go straight to the dispatch table (tests its
     // unmatched-variant error without launching anything)
     if (get<int>(d, "rows16", 0)) {   // the 16-row-block backward (gru_seq16.hip)
