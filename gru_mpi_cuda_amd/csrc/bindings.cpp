@@ -25,6 +25,24 @@ static T get(const py::dict& d, const char* k, T dflt) {
 }
 #define GP(T, d, k) reinterpret_cast<T*>(get<uintptr_t>(d, k, 0))
 
+// every OptimArgs field from a dict (raw optimiser kernels); `who` names the binding in errors
+static OptimArgs optim_from(const py::dict& d, const std::string& who) {
+  OptimArgs a;
+  a.p = GP(float, d, "p"); a.g = GP(const float, d, "g"); a.m = GP(float, d, "m"); a.v = GP(float, d, "v");
+  a.n = get<long>(d, "n", 0);
+  a.step = GP(int, d, "step"); a.gscale = GP(const float, d, "gscale");
+  a.err = GP(const unsigned, d, "err"); a.err_host = GP(unsigned, d, "err_host");
+  a.lr = get<float>(d, "lr", a.lr); a.b1 = get<float>(d, "b1", a.b1); a.b2 = get<float>(d, "b2", a.b2);
+  a.eps = get<float>(d, "eps", a.eps); a.wd = get<float>(d, "wd", a.wd); a.sgd = get<int>(d, "sgd", 0);
+  a.sched = get<int>(d, "sched", 0); a.warmup = get<int>(d, "warmup", 0); a.total = get<int>(d, "total", 0);
+  a.lr_min = get<float>(d, "lr_min", 0.f);
+  a.keep_g = get<int>(d, "keep_g", 1);
+  if (!a.p || !a.step || a.n < 0) throw std::runtime_error(who + ": p, step and n >= 0 required");
+  if (!a.sgd && (!a.m || !a.v)) throw std::runtime_error(who + ": Adam needs m and v");
+  if (a.sched < 0 || a.sched > 2) throw std::runtime_error(who + ": sched 0 (const), 1 (cosine) or 2 (linear)");
+  return a;
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "gru_mpi_cuda_amd native engine (HIP/CDNA4 kernels, hipGraph executor, RCCL comm)";
 
@@ -212,6 +230,96 @@ PYBIND11_MODULE(_C, m) {
     j.add_cast(GP(const float, d, "src"), get<int>(d, "splits", 1), get<int>(d, "R", 0), get<int>(d, "C", 0),
                GP(float, d, "dst"), GP(u16, d, "bf"), GP(u16, d, "bfT"));
     reduce_slabs_multi(j, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the optimiser tail: fused Adam/SGD + bf16 refresh, the plain Adam kernel, global-norm clipping,
+  // multi-job slab sums, the loss sum and the sharded optimiser's bias pack
+  m.def("adam_cast_multi", [](py::dict o, py::list jobs, uintptr_t s) {
+    const OptimArgs a = optim_from(o, "adam_cast_multi");
+    OptCastJobs j;
+    if (jobs.size() > 32) throw std::runtime_error("adam_cast_multi: at most 32 jobs");
+    if (jobs.size() == 0) throw std::runtime_error("adam_cast_multi: no jobs");
+    bool all_slabs = true;
+    for (auto h : jobs) {
+      py::dict d = h.cast<py::dict>();
+      OptCastJob J{get<long>(d, "off", 0), get<int>(d, "R", 0), get<int>(d, "C", 0), GP(u16, d, "dst"), GP(u16, d, "dstT"),
+                   GP(u16, d, "dstF"), GP(u16, d, "dstTF"), GP(const float, d, "gsl"), get<int>(d, "nsl", 0)};
+      if (J.off < 0 || J.off % 4) throw std::runtime_error("adam_cast_multi: off must be a non-negative multiple of 4");
+      if (J.R < 0 || J.C <= 0) throw std::runtime_error("adam_cast_multi: R >= 0 and C > 0 required");
+      if (J.R == 0) {
+        if (J.C % 4) throw std::runtime_error("adam_cast_multi: flat job needs C % 4 == 0");
+        if (J.dstT || J.dstF || J.dstTF) throw std::runtime_error("adam_cast_multi: a flat job has only the dst copy");
+      } else if (J.R % 64 || J.C % 64) {
+        throw std::runtime_error("adam_cast_multi: matrix job needs R % 64 == 0 and C % 64 == 0");
+      }
+      if (J.off + (J.R ? (long)J.R * J.C : (long)J.C) > a.n) throw std::runtime_error("adam_cast_multi: job runs past n");
+      if (J.gsl && J.nsl < 1) throw std::runtime_error("adam_cast_multi: gsl needs nsl >= 1");
+      all_slabs = all_slabs && J.gsl;
+      j.job[j.n++] = J;
+    }
+    if (!a.g && !(all_slabs && !a.keep_g)) throw std::runtime_error("adam_cast_multi: g required");
+    adam_cast_multi(a, j, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("adam_step", [](py::dict o, uintptr_t s) {   // the plain kernel (shapes off the 64-grid)
+    const OptimArgs a = optim_from(o, "adam_step");
+    if (!a.g) throw std::runtime_error("adam_step: g required");
+    adam_step(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("grad_clip_scale", [](py::dict d, uintptr_t s) {   // scale[0] = min(1, clip / (norm + 1e-6)), scale[1] = norm
+    const float* x = GP(const float, d, "x");
+    float* parts = GP(float, d, "parts");
+    float* scale = GP(float, d, "scale");
+    const long n = get<long>(d, "n", 0);
+    const int nparts = get<int>(d, "nparts", 0);
+    if (!x || !parts || !scale || n < 0 || nparts < 1 || nparts > 4096)
+      throw std::runtime_error("grad_clip_scale: x, parts, scale, n >= 0 and 1 <= nparts <= 4096 required");
+    sumsq_partials(x, n, parts, nparts, S(s));
+    HIP_LAUNCH_CHECK();
+    clip_scale_finalize(parts, nparts, get<float>(d, "clip", 0.f), scale, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("reduce_slabs_multi", [](py::list jobs, uintptr_t bump, uintptr_t s) {
+    SlabJobs j;
+    if (jobs.size() > 24) throw std::runtime_error("reduce_slabs_multi: at most 24 jobs");
+    if (jobs.size() == 0) throw std::runtime_error("reduce_slabs_multi: no jobs");
+    for (auto h : jobs) {
+      py::dict d = h.cast<py::dict>();
+      const float* src = GP(const float, d, "src");
+      const int splits = get<int>(d, "splits", 1);
+      if (!src || splits < 1) throw std::runtime_error("reduce_slabs_multi: src and splits >= 1 required");
+      if (d.contains("bf") || d.contains("bfT") || d.contains("R") || d.contains("C")) {
+        const int R = get<int>(d, "R", 0), C = get<int>(d, "C", 0);
+        if (!GP(u16, d, "bf") && !GP(u16, d, "bfT")) throw std::runtime_error("reduce_slabs_multi: cast job needs bf or bfT");
+        if (R <= 0 || C <= 0) throw std::runtime_error("reduce_slabs_multi: cast job needs R, C > 0");
+        j.add_cast(src, splits, R, C, GP(float, d, "dst"), GP(u16, d, "bf"), GP(u16, d, "bfT"));   // R % 16, C % 64: checked below
+      } else {
+        const long n = get<long>(d, "n", 0);
+        if (n < 1 || !GP(float, d, "dst")) throw std::runtime_error("reduce_slabs_multi: plain job needs n >= 1 and dst");
+        j.add(src, splits, n, GP(float, d, "dst"));
+      }
+    }
+    j.bump = Pp<int>(bump);
+    reduce_slabs_multi(j, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("sum_partials", [](uintptr_t parts, int n, uintptr_t out, uintptr_t bump, uintptr_t s) {
+    if (!parts || !out || n < 0) throw std::runtime_error("sum_partials: parts, out and n >= 0 required");
+    sum_partials(Pp<const float>(parts), n, Pp<float>(out), S(s), Pp<int>(bump));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("flat_pack_u32", [](uintptr_t p, uintptr_t pack, std::vector<std::pair<long, long>> ranges, long lo, long hi,
+                            long tail, int unpack, uintptr_t s) {
+    if (ranges.size() > 16) throw std::runtime_error("flat_pack_u32: at most 16 ranges");
+    if (!p || !pack) throw std::runtime_error("flat_pack_u32: p and pack required");
+    FlatRanges r;
+    for (const auto& [off, n] : ranges) {
+      if (off < 0 || n < 0 || n > (1L << 30)) throw std::runtime_error("flat_pack_u32: bad range");
+      r.off[r.cnt] = off;
+      r.n[r.cnt++] = (int)n;
+    }
+    flat_pack_u32(Pp<float>(p), Pp<unsigned>(pack), r, lo, hi, tail, unpack, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("fwd_step", [](py::dict d, uintptr_t s) {

@@ -229,6 +229,23 @@ __global__ void adam_kernel(OptimArgs a) {
     }
     reinterpret_cast<float4*>(a.p)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
   }
+  // tail: the last n % 4 elements, same update
+  for (long i = n4 * 4 + blockIdx.x * (long)blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
+    float pv = a.p[i];
+    const float gv = a.g[i] * sc;
+    if (a.sgd) {
+      pv -= lr * (gv + a.wd * pv);
+    } else {
+      const float mv = a.b1 * a.m[i] + (1.f - a.b1) * gv;
+      const float vv = a.b2 * a.v[i] + (1.f - a.b2) * gv * gv;
+      float u = (mv * ib1) / (sqrtf(vv * ib2) + a.eps);
+      if (a.wd != 0.f) u += a.wd * pv;
+      pv -= lr * u;
+      a.m[i] = mv;
+      a.v[i] = vv;
+    }
+    a.p[i] = pv;
+  }
 }
 void adam_step(const OptimArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(adam_kernel, dim3(nblocks(a.n / 4, 256, 2048)), dim3(256), 0, s, a);
