@@ -2,6 +2,7 @@
 
     python -m gru_mpi_cuda_amd.cli train    --preset h512 --steps 200 --ckpt out/model.bin
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --seed 1
+    python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --prefix Mar --temperature 0.8 --top-k 40 --top-p 0.95
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
@@ -198,11 +199,28 @@ def cmd_generate(args) -> int:
     ml = args.max_len if args.max_len is not None else (
         cfg.max_len if fmt == "ref" else ckpt.load(args.ckpt, None, "gen")[0].max_len)
     rf = random_floats(N, ml, seed=args.seed)
+    ctl = {}
+    for key in ("temperature", "top_k", "top_p"):
+        if getattr(args, key) is not None:
+            ctl[key] = getattr(args, key)
+    if args.prefix is not None and args.prefix_file is not None:
+        raise SystemExit("--prefix and --prefix-file exclude each other")
+    if args.prefix is not None:
+        ctl["prefix"] = args.prefix
+    elif args.prefix_file is not None:
+        pres = _read_names(args.prefix_file)
+        if not pres:
+            raise SystemExit(f"{args.prefix_file}: no prefixes")
+        ctl["prefix"] = [pres[i % len(pres)] for i in range(N)]   # cycled over the names
+    ctx = None
+    if args.cpu:
+        from .parallel.dist import DistCtx
+        ctx = DistCtx()
     t0 = time.perf_counter()
-    G.namegen_initialize(N, args.seed, args.ckpt, cfg, fmt, precision=args.precision)
+    G.namegen_initialize(N, args.seed, args.ckpt, cfg, fmt, ctx=ctx, precision=args.precision)
     out = np.zeros(N * (ml + 1), dtype=np.uint8)
     t1 = time.perf_counter()
-    G.namegen(N, rf, out)
+    G.namegen(N, rf, out, **ctl)
     t2 = time.perf_counter()
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -356,6 +374,16 @@ def main(argv=None) -> int:
                         "bf16x3: fp32 arithmetic on split-bf16 MFMA products (~2^-16 relative error per "
                         "product, ~2x faster; parity with fp32 unpinned on near-tie samples); "
                         "bf16: MFMA fast mode")
+    g.add_argument("--temperature", type=float, default=None,
+                   help="sampling temperature T >= 0 (0: greedy); any sampling control takes the controlled "
+                        "per-char path (fp32 / bf16x3)")
+    g.add_argument("--top-k", dest="top_k", type=int, default=None, help="keep the k most likely chars (0: off)")
+    g.add_argument("--top-p", dest="top_p", type=float, default=None,
+                   help="keep the smallest top set whose mass reaches p, in (0, 1] (1: off)")
+    g.add_argument("--prefix", default=None, help="every name starts with these chars")
+    g.add_argument("--prefix-file", dest="prefix_file", default=None,
+                   help="one prefix per line, cycled over the names")
+    g.add_argument("--cpu", action="store_true", help="force the CPU reference path (single process)")
     g.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(g)
     g.set_defaults(seed=0)

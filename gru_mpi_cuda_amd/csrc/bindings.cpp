@@ -170,6 +170,14 @@ PYBIND11_MODULE(_C, m) {
       .def("generate", [](Generator& g, uintptr_t rf, int N, uintptr_t out, uintptr_t s) {
         g.generate(Pp<const float>(rf), N, Pp<unsigned char>(out), S(s));
       })
+      .def("generate_ctl", [](Generator& g, uintptr_t rf, int N, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p,
+                              uintptr_t plen, uintptr_t prefix, uintptr_t out, uintptr_t s) {
+        Generator::Ctl c;
+        c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
+        c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
+        g.generate_ctl(Pp<const float>(rf), N, c, Pp<unsigned char>(out), S(s));
+      })
+      .def("ctl_workspace_bytes", &Generator::ctl_workspace_bytes)
       .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
                        uintptr_t n_tok, uintptr_t s) {
         g.score(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
@@ -550,6 +558,32 @@ PYBIND11_MODULE(_C, m) {
     a.step = get<int>(d, "step", 0); a.max_len = get<int>(d, "max_len", 0); a.eos = get<int>(d, "eos", 0);
     if (a.Bp % 32 || a.V % 64 || a.V > 512 || a.H % 32) throw std::runtime_error("fc_sample: bad shape");
     fc_sample(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the fp32 path's samplers on caller-made logits: sample_f32, and sample_ctl with the per-row controls
+  auto sample_args = [](const py::dict& d) {
+    SampleF32Args a;
+    a.logits = GP(const float, d, "logits"); a.splits = get<int>(d, "splits", 1); a.slab = get<long>(d, "slab", 0);
+    a.bias = GP(const float, d, "bias"); a.rf = GP(const float, d, "rf"); a.ids = GP(int, d, "ids");
+    a.out = GP(unsigned char, d, "out"); a.alive = GP(int, d, "alive"); a.probs = GP(float, d, "probs");
+    a.N = get<int>(d, "N", 0); a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0);
+    a.max_len = get<int>(d, "max_len", 0); a.eos = get<int>(d, "eos", 0);
+    if (!a.logits || !a.rf || !a.ids || !a.out || !a.alive || a.N < 0 || a.splits < 1 || a.step < 0 ||
+        a.step >= a.max_len || (a.splits > 1 && a.slab < (long)a.N * a.V))
+      throw std::runtime_error("sample: logits, rf, ids, out, alive, 0 <= step < max_len and slab >= N * V required");
+    return a;
+  };
+  m.def("sample_f32", [sample_args](py::dict d, uintptr_t s) {
+    sample_f32(sample_args(d), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("sample_ctl", [sample_args](py::dict d, uintptr_t s) {
+    SampleCtlArgs c;
+    c.s = sample_args(d);
+    c.inv_temp = GP(const float, d, "inv_temp"); c.top_k = GP(const int, d, "top_k");
+    c.top_p = GP(const float, d, "top_p"); c.plen = GP(const int, d, "plen");
+    c.prefix = GP(const unsigned char, d, "prefix"); c.row0 = get<int>(d, "row0", 0); c.err = GP(unsigned, d, "err");
+    sample_ctl_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("reduce_slabs", [](uintptr_t src, int splits, long n, uintptr_t dst, uintptr_t s) {

@@ -77,6 +77,7 @@ bool Generator::uses_persist(int n) const {
 Generator::~Generator() {
   graphs_.clear();
   sgraphs_.clear();
+  cgraphs_.clear();
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
 }
@@ -224,7 +225,7 @@ int Generator::product_f32(const float* A32, const u16* A3, const float* W32, co
   return g.splits;
 }
 
-void Generator::record_steps_f32(int n, hipStream_t s) {
+void Generator::record_steps_f32(int n, hipStream_t s, bool ctl) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n, 64);
   const bool x3 = split3();
@@ -258,7 +259,14 @@ void Generator::record_steps_f32(int n, hipStream_t s) {
     if (x3 && sf > 1) q.bias = bf;
     q.probs = (st == ML - 1) ? probe_ : nullptr;
     q.N = n; q.V = V; q.step = st; q.max_len = ML; q.eos = d_.eos;
-    sample_f32(q, s);
+    if (ctl) {
+      SampleCtlArgs c;
+      c.s = q; c.inv_temp = cinv_; c.top_k = ctopk_; c.top_p = ctopp_; c.plen = cplen_; c.prefix = cprefix_;
+      c.row0 = 0; c.err = err_;
+      sample_ctl_f32(c, s);
+    } else {
+      sample_f32(q, s);
+    }
   }
   HIP_LAUNCH_CHECK();
 }
@@ -333,6 +341,55 @@ void Generator::generate(const float* rf, int N, unsigned char* out, hipStream_t
       g->launch(s);
     } else {
       if (d_.fp32) record_steps_f32(n, s); else record_steps(n, s);
+    }
+    HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ---------------------------------------------------------------------- controlled sampling
+// The current batch's controls, sized for Bmax_ names: a generator that never samples with controls
+// never allocates them.
+void Generator::ctl_alloc() {
+  if (cready_) return;
+  const size_t B = Bmax_, ML = d_.max_len;
+  const size_t oi = carena_.reserve(B * 4), ok = carena_.reserve(B * 4), op = carena_.reserve(B * 4);
+  const size_t ol = carena_.reserve(B * 4), opre = carena_.reserve(B * ML);
+  carena_.commit();
+  cinv_ = carena_.get<float>(oi); ctopk_ = carena_.get<int>(ok); ctopp_ = carena_.get<float>(op);
+  cplen_ = carena_.get<int>(ol); cprefix_ = carena_.get<unsigned char>(opre);
+  cready_ = true;
+}
+
+void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s) {
+  GK_TRACE("gk.generate_ctl");
+  if (!d_.fp32) throw std::runtime_error("Generator::generate_ctl: sampling controls need precision fp32 or bf16x3");
+  if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix)
+    throw std::runtime_error("Generator::generate_ctl: every control array is required");
+  if (N <= 0) return;
+  const int ML = d_.max_len;
+  ctl_alloc();   // first call: allocates (and synchronises) before anything is captured
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
+  err_clean_ = false;
+  for (int start = 0; start < N; start += Bmax_) {
+    const int n = std::min(Bmax_, N - start);
+    HIP_CHECK(hipMemcpyAsync(rf_, rf + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    // this batch's slice of every control array: the graph reads rows 0 .. n - 1 of the buffers
+    HIP_CHECK(hipMemcpyAsync(cinv_, c.inv_temp + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ctopk_, c.top_k + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ctopp_, c.top_p + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(cplen_, c.plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(cprefix_, c.prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      auto& g = cgraphs_[n];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_steps_f32(n, cap_, true);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_steps_f32(n, s, true);
     }
     HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
   }

@@ -32,6 +32,17 @@ class Generator {
   void refresh_weights(hipStream_t s);   // bf16 weights + layer-0 table (call after params change)
   // rf: device [N][max_len] uniforms of THIS rank's names; out: device [N][max_len+1]
   void generate(const float* rf, int N, unsigned char* out, hipStream_t s);
+  // generate() with per-name sampling controls (docs/DESIGN.md §4b; device arrays of N entries:
+  // inv_temp = 1 / T or 0 for greedy, top_k, top_p, plen, prefix [N][max_len]).  Always the per-char
+  // fp32 / bf16x3 graph with sample_ctl_f32 as its sampler node, never the persistent launch; the
+  // bf16 mode raises.  The graph reads the controls from buffers of an arena of their own (allocated on
+  // the first call) into which each batch's slice is copied, so one recording per n serves every value.
+  struct Ctl {
+    const float* inv_temp = nullptr; const int* top_k = nullptr; const float* top_p = nullptr;
+    const int* plen = nullptr; const unsigned char* prefix = nullptr;
+  };
+  void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
+  size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until the first generate_ctl()
   // Teacher-forced scoring of N output rows (device [N][max_len+1], the generate() format): per token
   // log softmax(logits)[target] and the target's rank, per name their sum and the token count (all
   // device pointers: tok_logp / rank [N][max_len], name_logp / n_tok [N]).  Always the exact-fp32
@@ -42,7 +53,7 @@ class Generator {
   size_t score_workspace_bytes() const { return sarena_.bytes(); }   // 0 until the first score()
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
-  void set_probe(float* probs) { probe_ = probs; graphs_.clear(); }
+  void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); }
   // Small batches (fp32 modes: <= GK_GEN_PERSIST_MAX names, default and at most 64; bf16 mode: <= 24):
   // one persistent launch per batch (gen_persist.hip, exact fp32) instead of the per-char graph.
   // On by default; GK_GEN_PERSIST=0 or set_persist(false) turns it off.
@@ -66,7 +77,7 @@ class Generator {
 
  private:
   void record_steps(int n_active, hipStream_t s);
-  void record_steps_f32(int n_active, hipStream_t s);
+  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false);   // ctl: sample_ctl_f32 as the sampler node
   // one product of the fp32 / bf16x3 path: C = h W^T (+ bias) -> splits (slabs of M x N at C).  fp32
   // reads A32 / W32; bf16x3 the split copies A3 ([hi|hi|lo] rows) / W3 ([hi|lo|hi] rows)
   int product_f32(const float* A32, const u16* A3, const float* W32, const u16* W3, const float* bias, int M, int N,
@@ -74,6 +85,7 @@ class Generator {
   bool split3() const { return d_.fp32 == 2; }
   void reset_batch(int Bp, bool bf16, hipStream_t s);
   void score_alloc();
+  void ctl_alloc();
   void record_score(int Bp, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
@@ -123,6 +135,13 @@ class Generator {
   float *sgh_ = nullptr, *sgi_ = nullptr, *slogits_ = nullptr;   // step product slabs, [ML*Bp][3H], [ML*Bp][V] slabs
   float *stok_ = nullptr, *sname_ = nullptr;    // staged outputs [Bmax][ML], [Bmax]
   int *srank_ = nullptr, *sntok_out_ = nullptr;
+  // sampling controls (third arena, committed by the first generate_ctl() call)
+  Arena carena_;
+  bool cready_ = false;
+  std::map<int, std::unique_ptr<Graph>> cgraphs_;   // controlled per-char graphs, keyed by active-name count
+  float *cinv_ = nullptr, *ctopp_ = nullptr;    // [Bmax] each: the current batch's controls
+  int *ctopk_ = nullptr, *cplen_ = nullptr;
+  unsigned char* cprefix_ = nullptr;            // [Bmax][ML]
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

@@ -1,0 +1,186 @@
+// Controlled sampling for the fp32 / bf16x3 per-char generation graph: forced prefix chars, greedy,
+// temperature, top-k and top-p (docs/DESIGN.md §4b; the CPU twin and oracle is
+// cpu_ref.sample_controlled).  One wave per row like sample_f32_kernel, the same logits / slab / bias
+// inputs and the same ids / out / alive outputs; the per-row controls are read from device memory,
+// so a captured graph bakes no control value in.
+//
+// Both cuts are pure set definitions and need neither a sort nor LDS:
+//   * top-k keeps i iff #{j : y_j > y_i} < k, i.e. y_i >= the k-th largest value.  That value is
+//     found by a 32-step bisection over an order-preserving integer key of the floats; a probe is
+//     V/64 compares per lane plus a ballot popcount;
+//   * top-p keeps i iff sum{q_j : q_j > q_i} < p.  A fixed-order fp32 sum of non-negative terms is
+//     monotone when terms are replaced by 0, so "the mass above a threshold is < p" is monotone in
+//     the threshold and the smallest passing threshold is found by the same bisection over the bits
+//     of the non-negative q (30 steps: q <= 1), a fixed-order wave sum per probe.
+// With nothing filtered every statistic is formed by the operations of softmax_sample_wave in its
+// order, so neutral controls give the plain sampler's bytes.
+#include "kernels.h"
+#include "common.h"
+#include "gen_sample.h"
+
+namespace gk {
+
+// floats -> unsigned keys with the same order (-0 and +0 share a key)
+DEV unsigned order_key(float f) {
+  unsigned b = __float_as_uint(f);
+  if (b == 0x80000000u) b = 0u;
+  return (b >> 31) ? ~b : (b | 0x80000000u);
+}
+
+template <int MAXPER>
+__global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
+#pragma clang fp contract(off)
+  const SampleF32Args& a = c.s;
+  const int b = blockIdx.x, lane = threadIdx.x, V = a.V, per = V / 64;
+  if (b >= a.N) return;
+  const int cb = b + c.row0;   // this row's controls
+  float* prow = a.probs ? a.probs + (size_t)b * V : nullptr;
+  int sel;
+  if (a.step < c.plen[cb]) {   // forced: the uniform of this step is ignored
+    sel = c.prefix[(size_t)cb * a.max_len + a.step];
+    if (sel >= V) {   // never expected (the host checks first): flag it instead of feeding it on
+      if (c.err && lane == 0) {
+        atomicOr(c.err, 16u);
+        c.err[1] = (unsigned)sel;
+        c.err[2] = (unsigned)b;
+      }
+      sel = 0;
+    }
+    if (prow)
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e)
+        if (e < per) prow[lane * per + e] = (lane * per + e == sel) ? 1.f : 0.f;
+  } else {
+    const float* x = a.logits + (size_t)b * V + lane * per;
+    const float it = c.inv_temp[cb];   // 0: greedy
+    const int k = c.top_k[cb];
+    const float tp = c.top_p[cb];
+    const float scale = it == 0.f ? 1.f : it;
+    float y[MAXPER];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < MAXPER; ++e) {
+      if (e < per) {
+        float v = x[e];
+        for (int s2 = 1; s2 < a.splits; ++s2) v += x[s2 * a.slab + e];   // split-K slabs, fixed order
+        if (a.bias) v += a.bias[lane * per + e];
+        y[e] = v * scale;
+      } else {
+        y[e] = -INFINITY;
+      }
+      mx = fmaxf(mx, y[e]);
+    }
+    mx = wave_max_dpp(mx);
+    if (it == 0.f) {   // greedy: the lowest index of the maximum
+      int first = V;
+#pragma unroll
+      for (int e = MAXPER - 1; e >= 0; --e)
+        if (e < per && y[e] == mx) first = lane * per + e;
+      sel = wave_min_dpp(first);
+      if (sel >= V) sel = V - 1;   // (only a row of NaNs gets here)
+      if (prow)
+#pragma unroll
+        for (int e = 0; e < MAXPER; ++e)
+          if (e < per) prow[lane * per + e] = (lane * per + e == sel) ? 1.f : 0.f;
+    } else {
+      bool keep[MAXPER];
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) keep[e] = e < per;
+      if (k > 0 && k < V) {   // t = key of the k-th largest value: the largest t with #{key >= t} >= k
+        unsigned key[MAXPER];
+#pragma unroll
+        for (int e = 0; e < MAXPER; ++e) key[e] = order_key(y[e]);
+        unsigned t = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned cand = t | (1u << bit);
+          int cnt = 0;
+#pragma unroll
+          for (int e = 0; e < MAXPER; ++e) cnt += __popcll(__ballot(e < per && key[e] >= cand));
+          if (cnt >= k) t = cand;
+        }
+#pragma unroll
+        for (int e = 0; e < MAXPER; ++e) keep[e] = e < per && key[e] >= t;
+      }
+      float ex[MAXPER];
+      float se = 0.f;
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) {
+        ex[e] = keep[e] ? expf(y[e] - mx) : 0.f;
+        se += ex[e];
+      }
+      se = wave_sum_dpp(se);
+      if (tp < 1.f) {
+        float q[MAXPER];
+#pragma unroll
+        for (int e = 0; e < MAXPER; ++e) q[e] = ex[e] / se;
+        // above(u) = the mass of the q_j whose bits exceed u; P(u) = above(u) < p is monotone in u.
+        // lo = the smallest u with P(u): i is kept iff bits(q_i) >= lo
+        auto above = [&](unsigned u) {
+          float sacc = 0.f;
+#pragma unroll
+          for (int e = 0; e < MAXPER; ++e) sacc += __float_as_uint(q[e]) > u ? q[e] : 0.f;
+          return wave_sum_dpp(sacc);
+        };
+        unsigned lo = 0u;
+        if (!(above(0u) < tp)) {
+          unsigned u = 0u;   // the largest u with P(u) false; P(bits(1.0f)) holds, so u < 2^30
+          for (int bit = 29; bit >= 0; --bit) {
+            const unsigned cand = u | (1u << bit);
+            if (!(above(cand) < tp)) u = cand;
+          }
+          lo = u + 1u;
+        }
+        se = 0.f;
+#pragma unroll
+        for (int e = 0; e < MAXPER; ++e) {
+          keep[e] = keep[e] && __float_as_uint(q[e]) >= lo;
+          ex[e] = keep[e] ? ex[e] : 0.f;
+          se += ex[e];
+        }
+        se = wave_sum_dpp(se);
+      }
+      // renormalised distribution over the kept set, then softmax_sample_wave's CDF search
+      float p[MAXPER];
+      float loc = 0.f;
+      int last = -1;
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) {
+        p[e] = e < per ? ex[e] / se : 0.f;
+        loc += p[e];
+        if (keep[e]) last = lane * per + e;
+        if (prow && e < per) prow[lane * per + e] = p[e];
+      }
+      const float rnd = a.rf[(size_t)b * a.max_len + a.step];
+      const float inc = wave_scan_incl_dpp(loc);
+      float psum = inc - loc;
+      int hit = V;
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) {
+        psum += p[e];
+        if (e < per && hit == V && psum > rnd) hit = lane * per + e;
+      }
+      hit = wave_min_dpp(hit);
+      last = -wave_min_dpp(-last);   // the highest kept index (V - 1 with nothing filtered)
+      sel = hit >= V ? (last < 0 ? V - 1 : last) : hit;
+    }
+  }
+  if (lane == 0) {
+    if (a.alive[b]) {
+      a.out[(size_t)b * (a.max_len + 1) + a.step] = (unsigned char)sel;
+      if (sel == a.eos) a.alive[b] = 0;
+    }
+    a.ids[b] = sel;
+  }
+}
+
+void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s) {
+  const SampleF32Args& a = c.s;
+  if (a.V % 64 || a.V > 512 || a.V <= 0) throw std::runtime_error("sample_ctl_f32: needs V % 64 == 0 and V <= 512");
+  if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix || c.row0 < 0)
+    throw std::runtime_error("sample_ctl_f32: inv_temp, top_k, top_p, plen and prefix are required");
+  if (a.N <= 0) return;
+  if (a.V == 256) hipLaunchKernelGGL(sample_ctl_f32_kernel<4>, dim3(a.N), dim3(64), 0, s, c);
+  else hipLaunchKernelGGL(sample_ctl_f32_kernel<8>, dim3(a.N), dim3(64), 0, s, c);
+}
+
+}  // namespace gk

@@ -325,6 +325,22 @@ struct SampleF32Args {             // softmax of fp32 logits + inverse-CDF sampl
   const float* bias = nullptr;     // nullable: added after the slab sum (bf16x3 split-K logits)
 };
 void sample_f32(const SampleF32Args& a, hipStream_t s);
+// sample_f32 with per-row sampling controls read from device memory at row b + row0 (gen_ctl.hip,
+// docs/DESIGN.md §4b): step < plen forces prefix[step]; else inv_temp == 0 is greedy (lowest index of
+// the maximum logit); else y = x * inv_temp, top-k (0 or >= V: off), softmax, top-p (>= 1: off),
+// renormalise, `psum > r`, falling back to the highest kept index.  probs (s.probs, nullable) gets
+// the renormalised filtered row.
+struct SampleCtlArgs {
+  SampleF32Args s;
+  const float* inv_temp = nullptr;         // [..]  1 / T, 0 for T == 0
+  const int* top_k = nullptr;              // [..]
+  const float* top_p = nullptr;            // [..]
+  const int* plen = nullptr;               // [..]  forced chars of the row, <= max_len
+  const unsigned char* prefix = nullptr;   // [..][max_len]
+  int row0 = 0;
+  unsigned* err = nullptr;                 // nullable: bit 4 set (and the char clamped) on a prefix byte >= V
+};
+void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s);
 // bf16x3 operands: an fp32 value x = hi + lo with hi = bf16(x), lo = bf16(x - hi).  Weights become
 // [R][3K] = [hi | lo | hi] rows and activations [hi | hi | lo] rows, so ONE bf16 MFMA GEMM over 3K
 // accumulates hi*hi + hi*lo + lo*hi in fp32 (the lo*lo term, ~2^-16 relative, is dropped).

@@ -75,19 +75,40 @@ class HipGenerator:
     def _s(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
 
-    def generate_device(self, rf_dev: torch.Tensor, n: int) -> torch.Tensor:
+    def generate_device(self, rf_dev: torch.Tensor, n: int, *, temperature=None, top_k=None, top_p=None,
+                        prefix=None) -> torch.Tensor:
+        """``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (scalars or one value per name; semantics:
+        cpu_ref.make_controls, docs/DESIGN.md §4b): any that is not None -- a neutral value too -- takes
+        the controlled per-char graph (fp32 / bf16x3 only; never the persistent launch).  Bad values
+        raise ValueError before anything is launched."""
         ML = self.cfg.max_len
+        ctl = None
+        if any(v is not None for v in (temperature, top_k, top_p, prefix)):
+            if self.precision == "bf16":
+                raise ValueError('sampling controls need precision "fp32" or "bf16x3" (the bf16 mode samples '
+                                 "inside its fused FC kernel)")
+            ctl = cpu_ref.make_controls(self.cfg, max(n, 0), temperature, top_k, top_p, prefix)
         out = torch.empty(max(n, 1), ML + 1, dtype=torch.uint8, device=self.dev)   # every row written
-        if n > 0:
+        if n > 0 and ctl is None:
             self.g.generate(rf_dev.data_ptr(), n, out.data_ptr(), self._s())
+        elif n > 0:
+            dev = [torch.from_numpy(a).to(self.dev) for a in (ctl.inv_temp, ctl.top_k, ctl.top_p, ctl.plen, ctl.prefix)]
+            self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s())
+            err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
+            if err:
+                raise RuntimeError(f"HipGenerator.generate: device error word {err}")
         return out[:n]
 
-    def generate(self, rfloats: np.ndarray, start: int = 0, count: Optional[int] = None) -> np.ndarray:
+    def generate(self, rfloats: np.ndarray, start: int = 0, count: Optional[int] = None, *, temperature=None,
+                 top_k=None, top_p=None, prefix=None) -> np.ndarray:
+        """Names ``start .. start+count-1`` of the job.  The controls are generate_device's; per-name values
+        are indexed by the generated names (``count`` entries)."""
         ML = self.cfg.max_len
         N = (rfloats.size // ML - start) if count is None else count
         rf = torch.from_numpy(np.ascontiguousarray(rfloats[start * ML:(start + N) * ML], dtype=np.float32))
         rf = rf.to(self.dev)
-        return self.generate_device(rf, N).cpu().numpy()
+        return self.generate_device(rf, N, temperature=temperature, top_k=top_k, top_p=top_p,
+                                    prefix=prefix).cpu().numpy()
 
     def load_state(self, params: Dict[str, torch.Tensor]) -> None:
         """New weights (cfg-shaped tensors) into the flat buffer; every derived copy and table follows."""
@@ -148,6 +169,9 @@ class ScoreResult:
     @property
     def top1(self) -> float:
         return float((self.rank == 0).sum() / max(self.tokens, 1))
+
+
+encode_prefixes = cpu_ref.encode_prefixes   # (rows [N, MAX_LEN] uint8, plen [N] int32), validated
 
 
 def encode_names(names, cfg: GRUConfig) -> np.ndarray:
@@ -229,16 +253,31 @@ def namegen_initialize(N: int, rng_seed: int, parameter_fname: str, cfg: Optiona
     _S = s
 
 
-def namegen(N: int, random_floats: np.ndarray, output: np.ndarray) -> None:
-    """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place."""
+def _slice_control(v, N: int, start: int, count: int):
+    """This rank's part of a control given for the N names of the job (scalars and a single str / bytes
+    prefix apply to every name)."""
+    if v is None or isinstance(v, (str, bytes)) or np.ndim(v) == 0:
+        return v
+    if len(v) != N:
+        raise ValueError(f"a per-name control needs {N} entries, got {len(v)}")
+    return v[start:start + count]
+
+
+def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
+            prefix=None) -> None:
+    """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
+    ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
+    scalars or one value per name of the job; every rank takes its names' slice."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len
     start, count = shard(N, ctx.rank, ctx.world)
     per = -(-N // ctx.world)          # ceil: fixed slab size for the all-gather
+    ctl = {k: _slice_control(v, N, start, count) for k, v in
+           (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("prefix", prefix)) if v is not None}
     if _S.gen is not None:
         _S.gen.g.set_global_names(N)   # bf16 mode: the same arithmetic path at every world size
-        mine = _S.gen.generate(random_floats, start, count)
+        mine = _S.gen.generate(random_floats, start, count, **ctl)
         if ctx.world > 1:
             dev = ctx.device
             slab = torch.zeros(per, ML + 1, dtype=torch.uint8, device=dev)
@@ -250,7 +289,7 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray) -> None:
         else:
             allv = mine[None]
     else:
-        mine = cpu_ref.generate(_S.params, cfg, random_floats, start, count)
+        mine = cpu_ref.generate(_S.params, cfg, random_floats, start, count, **ctl)
         if ctx.world > 1:
             import torch.distributed as dist
             slab = torch.zeros(per, ML + 1, dtype=torch.uint8)

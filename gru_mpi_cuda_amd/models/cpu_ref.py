@@ -275,18 +275,181 @@ def sample_inverse_cdf(prob: torch.Tensor, r: torch.Tensor) -> torch.Tensor:
     return torch.where(hit.any(-1), idx, torch.full_like(idx, prob.shape[-1] - 1))
 
 
+# Sampling controls (docs/DESIGN.md §4b).  Per name: temperature T >= 0, top_k >= 0 (0: off), top_p in
+# (0, 1] (1: off) and a prefix pre[0..plen) with plen <= max_len, no EOS byte and no byte >= vocab.
+# At step l, with logits x[V]:
+#   1. forced: l < plen -> the char is pre[l]; the uniform of the step is ignored (name n still owns
+#      rfloats[n*MAX_LEN + l] by position), the char is written and fed back like a sampled one;
+#   2. greedy: T == 0 -> the lowest index of the maximum logit; the uniform is ignored;
+#   3. temperature: y = x * (1/T), 1/T rounded to fp32 once (T == 1 leaves y bitwise x);
+#   4. top-k: keep i iff #{j : y_j > y_i} < k (ties with the k-th value all kept; k == 0 or k >= V: all);
+#   5. softmax: q = max-subtracted softmax of y over the kept set, 0 elsewhere;
+#   6. top-p: keep i iff sum{q_j : q_j > q_i} < p -- the smallest top set whose mass reaches p, ties
+#      at the edge all kept, never empty (the maximum has mass 0 above it); p == 1: all;
+#   7. sample: the softmax of y over the final kept set (= q renormalised), the first index in index
+#      order whose running sum exceeds r, else the highest kept index (V - 1 with nothing filtered).
+# Every rule is a set definition (no sort order), so ties give the same result in fp32 and fp64.
+class Controls:
+    """Validated per-name controls of ``count`` names: inv_temp float32 (1/T; 0 encodes T == 0),
+    top_k int32, top_p float32, plen int32, prefix uint8 [count, max_len] (NUL past plen)."""
+
+    def __init__(self, inv_temp, top_k, top_p, plen, prefix):
+        self.inv_temp, self.top_k, self.top_p, self.plen, self.prefix = inv_temp, top_k, top_p, plen, prefix
+
+
+def encode_prefixes(prefixes, cfg: GRUConfig) -> Tuple[np.ndarray, np.ndarray]:
+    """Prefixes -> (rows [N, MAX_LEN] uint8, plen [N] int32).  ``prefixes``: a list of str (taken as
+    latin-1) or bytes, or uint8 rows [N, MAX_LEN+1] as ``encode_names`` makes them (chars, then the EOS
+    byte unless the row is full).  A prefix longer than max_len, one that holds the EOS byte or a byte
+    >= vocab raises ValueError."""
+    ML = cfg.max_len
+    if isinstance(prefixes, np.ndarray):
+        src = np.ascontiguousarray(prefixes, dtype=np.uint8).reshape(-1, ML + 1)[:, :ML]
+        is_eos = src == cfg.eos
+        plen = np.where(is_eos.any(1), is_eos.argmax(1), ML).astype(np.int32)
+        rows = np.where(np.arange(ML)[None, :] < plen[:, None], src, 0).astype(np.uint8)
+    else:
+        rows = np.zeros((len(prefixes), ML), dtype=np.uint8)
+        plen = np.zeros(len(prefixes), dtype=np.int32)
+        for i, nm in enumerate(prefixes):
+            try:
+                b = nm.encode("latin-1") if isinstance(nm, str) else bytes(nm)
+            except UnicodeEncodeError as e:
+                raise ValueError(f"prefix {i} ({nm!r}) is not latin-1") from e
+            if len(b) > ML:
+                raise ValueError(f"prefix {i} ({nm!r}) has {len(b)} chars, more than max_len = {ML}")
+            rows[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+            plen[i] = len(b)
+    mask = np.arange(ML)[None, :] < plen[:, None]
+    if (mask & (rows >= cfg.vocab)).any():
+        i = int(np.argwhere(mask & (rows >= cfg.vocab))[0][0])
+        raise ValueError(f"prefix {i} holds a byte >= vocab ({cfg.vocab})")
+    if (mask & (rows == cfg.eos)).any():
+        i = int(np.argwhere(mask & (rows == cfg.eos))[0][0])
+        raise ValueError(f"prefix {i} contains the EOS byte {cfg.eos}")
+    return rows, plen
+
+
+def _per_name(v, n: int, dtype, what: str) -> np.ndarray:
+    a = np.asarray(v, dtype=dtype)
+    if a.ndim == 0:
+        return np.full(n, a, dtype=dtype)
+    if a.shape != (n,):
+        raise ValueError(f"{what}: a scalar or {n} values expected, got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def make_controls(cfg: GRUConfig, count: int, temperature=None, top_k=None, top_p=None, prefix=None) -> Controls:
+    """Scalars or per-name arrays of ``count`` entries (None: the neutral value) -> Controls.  ``prefix``:
+    one str / bytes for every name, or ``encode_prefixes`` input for ``count`` names.  Raises ValueError
+    for T < 0 or not finite (or so extreme that 1/T is not a finite non-zero fp32), top_k < 0, top_p
+    outside (0, 1] and a bad prefix."""
+    T = _per_name(1.0 if temperature is None else temperature, count, np.float64, "temperature")
+    if not np.isfinite(T).all() or (T < 0).any():
+        raise ValueError("temperature must be finite and >= 0")
+    with np.errstate(divide="ignore", over="ignore", under="ignore"):
+        inv = np.where(T == 0, 0.0, 1.0 / np.where(T == 0, 1.0, T)).astype(np.float32)
+    if (~np.isfinite(inv)).any() or ((inv == 0) & (T != 0)).any():
+        raise ValueError("temperature: 1/T must be a finite non-zero fp32 value (or T == 0 for greedy)")
+    kraw = np.asarray(0 if top_k is None else top_k)
+    if kraw.dtype.kind == "f" and (kraw != np.floor(kraw)).any():
+        raise ValueError("top_k must be an integer")
+    k = _per_name(kraw, count, np.int64, "top_k")
+    if (k < 0).any():
+        raise ValueError("top_k must be >= 0 (0: off)")
+    k = np.minimum(k, cfg.vocab).astype(np.int32)   # k >= V keeps everything
+    p = _per_name(1.0 if top_p is None else top_p, count, np.float64, "top_p")
+    if not ((p > 0) & (p <= 1)).all():
+        raise ValueError("top_p must lie in (0, 1] (1: off)")
+    p32 = p.astype(np.float32)
+    if (p32 <= 0).any():
+        raise ValueError("top_p must be a positive fp32 value")
+    if prefix is None:
+        rows, plen = np.zeros((count, cfg.max_len), np.uint8), np.zeros(count, np.int32)
+    else:
+        if isinstance(prefix, (str, bytes)):
+            prefix = [prefix] * count
+        rows, plen = encode_prefixes(prefix, cfg)
+        if rows.shape[0] != count:
+            raise ValueError(f"prefix: {count} prefixes expected, got {rows.shape[0]}")
+    return Controls(inv, k, p32, plen, rows)
+
+
+def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray):
+    """Steps 2-7 on logits x [N, V] with Controls arrays of N entries -> (probs [N, V], keep [N, V])."""
+    N, V = x.shape
+    dt = x.dtype
+    inv_t = torch.from_numpy(inv)
+    greedy = inv_t == 0
+    y = x * torch.where(greedy, torch.ones_like(inv_t), inv_t).to(dt).unsqueeze(-1)
+    keep = torch.ones(N, V, dtype=torch.bool)
+    k = torch.from_numpy(top_k.astype(np.int64))
+    kact = (k > 0) & (k < V)
+    if kact.any():   # y_i >= the k-th largest value  <=>  fewer than k values above y_i
+        kth = torch.sort(y, -1, descending=True).values.gather(-1, (k.clamp(1, V) - 1).unsqueeze(-1))
+        keep = torch.where(kact.unsqueeze(-1), y >= kth, keep)
+    ninf = torch.full_like(y, -math.inf)
+    p = torch.from_numpy(top_p).to(dt)
+    pact = p < 1
+    if pact.any():
+        q = torch.softmax(torch.where(keep, y, ninf), -1)
+        qs, order = torch.sort(q, -1, descending=True)
+        before = torch.cumsum(qs, -1) - qs                     # mass sorted ahead of each entry
+        first = torch.ones_like(keep)
+        first[:, 1:] = qs[:, 1:] != qs[:, :-1]                 # an entry's ties share the first one's mass
+        above_s = torch.cummax(torch.where(first, before, torch.full_like(before, -1.0)), -1).values
+        above = torch.empty_like(above_s).scatter_(-1, order, above_s)
+        keep = torch.where(pact.unsqueeze(-1), keep & (above < p.unsqueeze(-1)), keep)
+    top = (y == y.max(-1, keepdim=True).values).to(torch.int64).argmax(-1)   # lowest index of the maximum
+    keep = torch.where(greedy.unsqueeze(-1), torch.arange(V).unsqueeze(0) == top.unsqueeze(-1), keep)
+    return torch.softmax(torch.where(keep, y, ninf), -1), keep
+
+
+def filter_probs(logits: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0) -> torch.Tensor:
+    """The distribution step 7 samples from: logits [N, V] (or [V]) in fp32 or fp64 (fp64: the oracle),
+    the controls scalars or N values.  T == 0 gives the one-hot row of the lowest arg-max."""
+    x = logits.unsqueeze(0) if logits.dim() == 1 else logits
+    c = make_controls(GRUConfig(vocab=x.shape[-1]), x.shape[0], temperature, top_k, top_p)
+    probs, _ = _filter(x, c.inv_temp, c.top_k, c.top_p)
+    return probs[0] if logits.dim() == 1 else probs
+
+
+def sample_controlled(logits: torch.Tensor, r: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0,
+                      controls: Optional[Controls] = None) -> torch.Tensor:
+    """Steps 2-7: logits [N, V], uniforms r [N] -> chosen index [N] (int64)."""
+    c = controls or make_controls(GRUConfig(vocab=logits.shape[-1]), logits.shape[0], temperature, top_k, top_p)
+    probs, keep = _filter(logits, c.inv_temp, c.top_k, c.top_p)
+    V = probs.shape[-1]
+    cs = torch.empty_like(probs)
+    acc = torch.zeros_like(probs[..., 0])
+    for i in range(V):   # strictly left to right, as sample_inverse_cdf
+        acc = acc + probs[..., i]
+        cs[..., i] = acc
+    hit = cs > r.to(probs.dtype).unsqueeze(-1)
+    idx = hit.to(torch.int64).argmax(-1)
+    last = V - 1 - keep.flip(-1).to(torch.int64).argmax(-1)   # the highest kept index
+    return torch.where(hit.any(-1), idx, last)
+
+
 def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0,
-             count: Optional[int] = None) -> np.ndarray:
+             count: Optional[int] = None, temperature=None, top_k=None, top_p=None, prefix=None) -> np.ndarray:
     """Batched version of the reference's per-name loop (namegensf.cu:649-884).
 
     Names ``start .. start+count-1`` of the global job; name n at step l consumes
     ``rfloats[n*MAX_LEN + l]`` (SURVEY §3.2 invariant) -- the global index, so the
     result is independent of how names are split across ranks.  Returns uint8
     [count, MAX_LEN+1]; the EOS char *is* written before stopping
-    (namegensf.cu:877-882) and the rest stays NUL."""
+    (namegensf.cu:877-882) and the rest stays NUL.
+
+    ``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (see ``make_controls``; scalars or one value per
+    generated name, i.e. ``count`` entries): any that is not None takes the controlled sampler above
+    (neutral values give the plain path's bytes).  fp64 params give the oracle."""
     ML = cfg.max_len
     N = (rfloats.size // ML - start) if count is None else count
     out = np.zeros((N, ML + 1), dtype=np.uint8)
+    ctl = None
+    if any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        ctl = make_controls(cfg, max(N, 0), temperature, top_k, top_p, prefix)
     if N <= 0:
         return out
     H = cfg.hidden
@@ -303,8 +466,15 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
             hs[k], _ = _gates(gi, gh, hs[k])
             inp = hs[k]
         logits = inp @ params["fc.weight"].T + params["fc.bias"]
-        prob = torch.softmax(logits if dt == torch.float64 else logits.to(torch.float32), -1)
-        sel = sample_inverse_cdf(prob, rf[:, l].to(prob.dtype))
+        if dt != torch.float64:
+            logits = logits.to(torch.float32)
+        if ctl is None:
+            prob = torch.softmax(logits, -1)
+            sel = sample_inverse_cdf(prob, rf[:, l].to(prob.dtype))
+        else:
+            sel = sample_controlled(logits, rf[:, l], controls=ctl)
+            forced = torch.from_numpy(ctl.plen > l)
+            sel = torch.where(forced, torch.from_numpy(ctl.prefix[:, l].astype(np.int64)), sel)
         out[alive.numpy(), l] = sel[alive].numpy().astype(np.uint8)
         alive &= sel != cfg.eos
         cur = sel
