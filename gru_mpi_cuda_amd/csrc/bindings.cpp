@@ -533,7 +533,7 @@ PYBIND11_MODULE(_C, m) {
     gru_bwd_seq(a, S(s));
     HIP_LAUNCH_CHECK();
   });
-  m.def("fc_xent", [](py::dict d, uintptr_t s) {
+  auto fc_xent_args = [](const py::dict& d) {
     FcXentArgs a;
     a.X = GP(const u16, d, "X"); a.W = GP(const u16, d, "W"); a.b = GP(const float, d, "b");
     a.labels = GP(const int, d, "labels"); a.inv_count = GP(const float, d, "inv_count");
@@ -543,9 +543,23 @@ PYBIND11_MODULE(_C, m) {
     a.WT = GP(const u16, d, "WT"); a.dy = GP(float, d, "dy");
     a.dbg = GP(unsigned long long, d, "dbg");
     a.Wf = GP(const u16, d, "Wf"); a.WTf = GP(const u16, d, "WTf");
+    return a;
+  };
+  m.def("fc_xent", [fc_xent_args](py::dict d, uintptr_t s) {
+    const FcXentArgs a = fc_xent_args(d);
     if (a.M % 32 || a.V % 64 || a.V > 512 || a.H % 32 || a.ldT % 8 || a.colT % 8)
       throw std::runtime_error("fc_xent: bad shape");
     fc_xent(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the row-wise softmax-xent of the large-H plans on caller-made fp32 logits [M][V]: the fc_xent dict
+  // without X / W / b / H; softmax_xent itself throws on a shape it does not serve
+  m.def("softmax_xent", [fc_xent_args](uintptr_t logits, py::dict d, uintptr_t s) {
+    const FcXentArgs a = fc_xent_args(d);
+    if (!logits || !a.labels || !a.inv_count || !a.dlT || !a.loss_part || a.M <= 0 || a.V <= 0 ||
+        a.ldT < a.colT + a.M)
+      throw std::runtime_error("softmax_xent: logits, labels, inv_count, dlT, loss_part and ldT >= colT + M required");
+    softmax_xent(reinterpret_cast<const float*>(logits), a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("fc_sample", [](py::dict d, uintptr_t s) {

@@ -976,6 +976,14 @@ void fc_xent(const FcXentArgs& a, hipStream_t s) {
     throw std::runtime_error("fc_xent: fused dH needs H % (V/4) == 0, V % 128 == 0 and W_fc^T");
   const size_t shm = (2 * NW * 32 + 64) * 4 + (size_t)a.V * 40 * 2 + (size_t)FROWS * (a.V + 8) * 2;
   const int nks = a.H / 32;
+  // V = 512 asks for 76.5 KB of dynamic LDS: above the 64 KB a launch may ask for without the
+  // attribute (as the V = 256 eight-wave kernels above)
+  static bool attr = false;
+  if (!attr && shm > 64 * 1024) {
+    for (const void* k : {(const void*)fc_xent_kernel<4>, (const void*)fc_xent_kernel<2>, (const void*)fc_xent_kernel<1>})
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
   dim3 grid(a.M / FROWS), block(64 * NW);
   if (nks % 8 == 0) hipLaunchKernelGGL(fc_xent_kernel<4>, grid, block, shm, s, a);
   else if (nks % 2 == 0) hipLaunchKernelGGL(fc_xent_kernel<2>, grid, block, shm, s, a);
@@ -998,6 +1006,12 @@ void fc_sample(const FcSampleArgs& a, hipStream_t s) {
   const int NW = a.V / 64;
   const size_t shm = (2 * NW * 32) * 4 + (size_t)a.V * FROWS * 4;
   const int nks = a.H / 32;
+  static bool gattr = false;   // V = 512: 68 KB of dynamic LDS, as fc_xent above
+  if (!gattr && shm > 64 * 1024) {
+    (void)hipFuncSetAttribute((const void*)fc_sample_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)fc_sample_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    gattr = true;
+  }
   dim3 grid(a.Bp / FROWS), block(64 * NW);
   if (nks % 2 == 0) hipLaunchKernelGGL(fc_sample_kernel<2>, grid, block, shm, s, a);
   else hipLaunchKernelGGL(fc_sample_kernel<1>, grid, block, shm, s, a);

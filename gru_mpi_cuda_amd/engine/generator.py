@@ -240,7 +240,11 @@ def namegen_initialize(N: int, rng_seed: int, parameter_fname: str, cfg: Optiona
                 else torch.zeros(lay.total)).to(s.ctx.device)
         if s.comm is not None:
             s.comm.broadcast_f32(flat.data_ptr(), lay.total, 0, torch.cuda.current_stream().cuda_stream)
-        s.gen = HipGenerator(s.cfg, {}, device=s.ctx.device, flat=flat,
+        # E / H off the 64-grid: the generator pads the parameters itself, so it takes them as views of
+        # the (broadcast) buffer instead of sharing it
+        off_grid = pad_config(s.cfg).replace(vocab=s.cfg.vocab) != s.cfg
+        s.gen = HipGenerator(s.cfg, lay.views(flat.cpu()) if off_grid else {}, device=s.ctx.device,
+                             flat=None if off_grid else flat,
                              max_batch=max(64, min(8192, N // max(1, s.ctx.world) + 1)), precision=precision)
     else:
         lay = flat_layout(s.cfg)
