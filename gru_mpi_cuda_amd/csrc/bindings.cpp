@@ -43,6 +43,44 @@ static OptimArgs optim_from(const py::dict& d, const std::string& who) {
   return a;
 }
 
+// every GemmArgs field from a dict (raw GEMM kernels and their predicates); `who` names the binding in errors
+static GemmArgs gemm_from(const py::dict& d, const std::string& who) {
+  GemmArgs a;
+  a.A = GP(const u16, d, "A"); a.lda = get<int>(d, "lda", 0);
+  a.A32 = GP(const float, d, "A32"); a.a32_trans = get<int>(d, "a32_trans", 0);
+  a.onehot_ids = GP(const int, d, "onehot_ids");
+  a.B2 = GP(const u16, d, "B2"); a.b2_row = get<int>(d, "b2_row", 0);
+  a.B = GP(const u16, d, "B"); a.ldb = get<int>(d, "ldb", 0);
+  a.C = GP(float, d, "C"); a.ldc = get<int>(d, "ldc", 0);
+  a.bias = GP(const float, d, "bias"); a.rowsumA = GP(float, d, "rowsumA");
+  a.M = get<int>(d, "M", 0); a.N = get<int>(d, "N", 0); a.K = get<int>(d, "K", 0);
+  a.splits = get<int>(d, "splits", 1); a.accumulate = get<int>(d, "accumulate", 0);
+  a.raster = get<int>(d, "raster", 0);
+  a.algo = get<int>(d, "algo", 0);
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.splits < 1 || a.K % a.splits)
+    throw std::runtime_error(who + ": M, N, K > 0 and K a multiple of splits >= 1 required");
+  if (a.raster != 0 && a.raster != 1) throw std::runtime_error(who + ": raster 0 (auto) or 1 (column-fast)");
+  if (a.A32 && (a.A || a.onehot_ids)) throw std::runtime_error(who + ": A32 excludes A and onehot_ids");
+  return a;
+}
+
+// what every generic kernel needs (the streaming one-hot kernel has its own, narrower column blocks)
+static void gemm_tiles64(const GemmArgs& a, const std::string& who) {
+  if (a.M % 64 || a.N % 64 || (a.K / a.splits) % 32)
+    throw std::runtime_error(who + ": M, N must be multiples of 64 and K/splits a multiple of 32");
+}
+
+// PrepJob from a dict; rows up to Bp are read from a slot of Bmax rows (kernels.h prep_batch)
+static PrepJob prep_from(const py::dict& d, const std::string& who) {
+  PrepJob p;
+  p.in = GP(const int, d, "in"); p.Bmax = get<int>(d, "Bmax", 0); p.T = get<int>(d, "T", 0); p.Bp = get<int>(d, "Bp", 0);
+  p.ids = GP(int, d, "ids"); p.labels = GP(int, d, "labels"); p.inv_count = GP(float, d, "inv_count");
+  if (!p.in || !p.ids || !p.labels || !p.inv_count || p.T < 1 || p.Bp < 1)
+    throw std::runtime_error(who + ": in, ids, labels, inv_count and T, Bp >= 1 required");
+  if (p.Bp > p.Bmax) throw std::runtime_error(who + ": Bp > Bmax would read past the staging slot");
+  return p;
+}
+
 PYBIND11_MODULE(_C, m) {
   m.doc() = "gru_mpi_cuda_amd native engine (HIP/CDNA4 kernels, hipGraph executor, RCCL comm)";
 
@@ -207,20 +245,81 @@ PYBIND11_MODULE(_C, m) {
     gemm_f32_nt(a, S(s));
   });
   m.def("gemm_nt", [](py::dict d, uintptr_t s) {
-    GemmArgs a;
-    a.A = GP(const u16, d, "A"); a.lda = get<int>(d, "lda", 0);
-    a.onehot_ids = GP(const int, d, "onehot_ids");
-    a.B2 = GP(const u16, d, "B2"); a.b2_row = get<int>(d, "b2_row", 0);
-    a.B = GP(const u16, d, "B"); a.ldb = get<int>(d, "ldb", 0);
-    a.C = GP(float, d, "C"); a.ldc = get<int>(d, "ldc", 0);
-    a.bias = GP(const float, d, "bias"); a.rowsumA = GP(float, d, "rowsumA");
-    a.M = get<int>(d, "M", 0); a.N = get<int>(d, "N", 0); a.K = get<int>(d, "K", 0);
-    a.splits = get<int>(d, "splits", 1); a.accumulate = get<int>(d, "accumulate", 0);
-    a.algo = get<int>(d, "algo", 0);
-    if (a.M % 64 || a.N % 64 || (a.K / a.splits) % 32 || a.K % a.splits)
-      throw std::runtime_error("gemm_nt: M, N must be multiples of 64 and K/splits a multiple of 32");
+    const GemmArgs a = gemm_from(d, "gemm_nt");
+    if (a.A32 && a.algo != 3) throw std::runtime_error("gemm_nt: A32 (fp32-staged A) is read by algo 3 (gemm_small) only");
+    const bool stream = a.onehot_ids && (a.algo == 0 || a.algo == 2) && gemm_variants().onehot && onehot_dp_ok(a);
+    if (!stream) gemm_tiles64(a, "gemm_nt");
+    if (!a.onehot_ids && !a.A && !a.A32) throw std::runtime_error("gemm_nt: no A operand");
+    if (!a.B || !a.C) throw std::runtime_error("gemm_nt: B and C required");
     gemm_nt(a, S(s));
     HIP_LAUNCH_CHECK();
+  });
+  // several products in one launch: kind "small" (gemm_small_group) or "lds" (gemm_lds_group), 1-4 jobs
+  m.def("gemm_group", [](const std::string& kind, py::list jobs, uintptr_t s) {
+    if (jobs.size() < 1 || jobs.size() > 4) throw std::runtime_error("gemm_group: 1..4 jobs");
+    GemmArgs j[4];
+    int n = 0;
+    for (auto h : jobs) j[n++] = gemm_from(h.cast<py::dict>(), "gemm_group");
+    if (kind == "small") {
+      if (!gemm_small_group_depth(j, n)) throw std::runtime_error("gemm_group: the jobs share no small-kernel chunk depth");
+      gemm_small_group(j, n, S(s));
+    } else if (kind == "lds") {
+      for (int k = 0; k < n; ++k)
+        if (j[k].A32 || j[k].onehot_ids) throw std::runtime_error("gemm_group: lds jobs take a bf16 A only");
+      gemm_lds_group(j, n, S(s));
+    } else {
+      throw std::runtime_error("gemm_group: kind is \"small\" or \"lds\"");
+    }
+    HIP_LAUNCH_CHECK();
+  });
+  // the layer-0 table product with the batch transpose on trailing blocks of the same launch
+  m.def("gemm_with_prep", [](py::dict g, py::dict p, uintptr_t s) {
+    const GemmArgs a = gemm_from(g, "gemm_with_prep");
+    if (a.A32 || a.onehot_ids || !a.A || !a.B || !a.C) throw std::runtime_error("gemm_with_prep: a bf16 A, B and C only");
+    gemm_tiles64(a, "gemm_with_prep");
+    gemm_with_prep(a, prep_from(p, "gemm_with_prep"), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("prep_batch", [](py::dict p, uintptr_t s) {
+    const PrepJob j = prep_from(p, "prep_batch");
+    prep_batch(j.in, j.Bmax, j.T, j.Bp, j.ids, j.labels, j.inv_count, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("colsum", [](uintptr_t in, int R, int C, uintptr_t out, uintptr_t s) {
+    if (!in || !out || R < 1 || C < 1) throw std::runtime_error("colsum: in, out and R, C >= 1 required");
+    colsum(Pp<const float>(in), R, C, Pp<float>(out), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("rowsum_bf16", [](uintptr_t A, int lda, int M, int K, uintptr_t out, uintptr_t s) {
+    if (!A || !out || M < 1 || K < 8 || K % 8 || lda % 8 || lda < K || A % 16)
+      throw std::runtime_error("rowsum_bf16: needs K % 8 == 0, lda % 8 == 0, lda >= K and a 16-B aligned A");
+    rowsum_bf16(Pp<const u16>(A), lda, M, K, Pp<float>(out), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("split_bf16x3", [](uintptr_t src, int R, int K, uintptr_t dst, uintptr_t s) {
+    if (!src || !dst || R < 1 || K < 1) throw std::runtime_error("split_bf16x3: src, dst and R, K >= 1 required");
+    split_bf16x3(Pp<const float>(src), R, K, Pp<u16>(dst), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // which kernel takes a product (the gemm_nt dict): tests assert support instead of skipping
+  m.def("gemm_small_kblocks", [](py::dict d) { return gemm_small_kblocks(gemm_from(d, "gemm_small_kblocks")); });
+  m.def("gemm_small_group_depth", [](py::list jobs) {
+    if (jobs.size() < 1 || jobs.size() > 4) throw std::runtime_error("gemm_small_group_depth: 1..4 jobs");
+    GemmArgs j[4];
+    int n = 0;
+    for (auto h : jobs) j[n++] = gemm_from(h.cast<py::dict>(), "gemm_small_group_depth");
+    return gemm_small_group_depth(j, n);
+  });
+  m.def("gemm_lds_ok", [](py::dict d) { return gemm_lds_ok(gemm_from(d, "gemm_lds_ok")); });
+  m.def("gemm256_ok", [](py::dict d) { return gemm256_ok(gemm_from(d, "gemm256_ok")); });
+  m.def("gemm256_tile_rows", [](py::dict d) {
+    const GemmArgs a = gemm_from(d, "gemm256_tile_rows");
+    return gemm256_tile_rows(a.M, a.N, a.K, a.splits);
+  });
+  m.def("onehot_dp_ok", [](py::dict d) { return onehot_dp_ok(gemm_from(d, "onehot_dp_ok")); });
+  m.def("onehot_dp_splits", [](py::dict d) {
+    const GemmArgs a = gemm_from(d, "onehot_dp_splits");
+    return onehot_dp_splits(a.N, a.K);
   });
   m.def("cast_multi", [](py::list jobs, uintptr_t s) {
     CastJobs j;

@@ -171,7 +171,13 @@ bool gemm_library(const GemmArgs& a, hipStream_t s) {
   return true;
 }
 
-void gemm_nt(const GemmArgs& a, hipStream_t s) {
+void gemm_nt(const GemmArgs& a0, hipStream_t s) {
+  // one bias contract for every kernel (kernels.h: non-split only): a split product's slabs are summed
+  // by the caller, so a bias added per slab would count `splits` times; the LDS and one-shot kernels
+  // already drop it; dropped here, neither the register kernel below nor gemm256 (whose own entry
+  // rejects the combination) ever sees one.  No engine caller passes a bias with splits > 1.
+  GemmArgs a = a0;
+  if (a.splits > 1) a.bias = nullptr;
   if (a.B2 && !gemm_lds_ok(a) && !(gemm_variants().onehot && onehot_dp_ok(a)))
     throw std::runtime_error("gemm_nt: a split B operand (B2) needs a one-hot LDS / streaming kernel");
   // large plain products: hipBLASLt (bf16 in, fp32 out), when it has an algorithm for the shape

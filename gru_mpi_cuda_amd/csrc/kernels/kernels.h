@@ -415,7 +415,7 @@ struct GemmArgs {
   const int* onehot_ids = nullptr; // if set, A[m][k] = (ids[k] == m) generated on the fly
   const u16* B = nullptr; int ldb = 0;
   float* C = nullptr; int ldc = 0;
-  const float* bias = nullptr;     // [N] added in the epilogue (non-split only)
+  const float* bias = nullptr;     // [N] added in the epilogue (non-split only: gemm_nt ignores it when splits > 1)
   float* rowsumA = nullptr;        // [splits][M] partial row sums of A (nullable)
   int M = 0, N = 0, K = 0;
   int splits = 1;                  // split-K: slab s written at C + s*M*ldc (ldc == N)
@@ -570,6 +570,8 @@ void block_cus(int nblocks, int us, hipStream_t s);
 // Batch preparation on device: in = [hdr 16 ints: B, float-bits of 1/#valid][x Bmax*T][y Bmax*T]
 // batch-major int32 (may be pinned host memory, read zero-copy); out ids/labels time-major [T][Bp]
 // (pad rows: id 0, label -1) and inv_count.
+// Contract: Bp <= Bmax.  The kernel reads x[b * T + t], y[b * T + t] for every b < Bp before it selects
+// on b < B, so a Bp above Bmax reads past the slot (the trainer passes Bmax == Bp; the bindings throw).
 void prep_batch(const int* in, int Bmax, int T, int Bp, int* ids, int* labels, float* inv_count, hipStream_t s);
 inline int prep_batch_blocks(int T, int Bp) {
   const int n = (T * Bp + 255) / 256;
