@@ -478,7 +478,7 @@ PYBIND11_MODULE(_C, m) {
     const StepLdsVariants& v = step_lds_variants();
     py::dict d;
     d["fwd64"] = v.fwd64; d["bwd_sk_min_h"] = v.bwd_sk_min_h; d["dwfc_group"] = v.dwfc_group;
-    d["bwd_big"] = v.bwd_big; d["bwd16"] = v.bwd16; d["bwd_xring"] = v.bwd_xring; d["fwd_xring"] = v.fwd_xring; d["fwd_fc"] = v.fwd_fc; d["fc_flash"] = v.fc_flash; d["save16"] = v.save16; d["big_dy"] = v.big_dy; d["ld_pad"] = v.ld_pad;
+    d["bwd_big"] = v.bwd_big; d["bwd16"] = v.bwd16; d["bwd_xring"] = v.bwd_xring; d["fwd_xring"] = v.fwd_xring; d["fwd_fc"] = v.fwd_fc; d["fc_flash"] = v.fc_flash; d["fc_tail"] = v.fc_tail; d["save16"] = v.save16; d["big_dy"] = v.big_dy; d["ld_pad"] = v.ld_pad;
     return d;
   });
   m.def("set_step_lds_variants", [](py::dict d) {
@@ -495,6 +495,7 @@ PYBIND11_MODULE(_C, m) {
       else if (k == "fwd_xring") v.fwd_xring = x;
       else if (k == "fwd_fc") v.fwd_fc = x;
       else if (k == "fc_flash") v.fc_flash = x;
+      else if (k == "fc_tail") v.fc_tail = x;
       else if (k == "big_dy") v.big_dy = x;
       else if (k == "ld_pad") v.ld_pad = x;
       else if (k == "save16") v.save16 = x;
@@ -649,6 +650,29 @@ PYBIND11_MODULE(_C, m) {
     if (a.M % 32 || a.V % 64 || a.V > 512 || a.H % 32 || a.ldT % 8 || a.colT % 8)
       throw std::runtime_error("fc_xent: bad shape");
     fc_xent(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the one-layer persistent forward with the fused FC head as its tail: the fwd_seq dict and the fc_xent
+  // dict (X = HSb + Bp * H, M = T * Bp, fused dH); scripts/probe_seq.py TAIL=1
+  m.def("fwd_seq_tail_supported", &gru_fwd_seq_tail_supported);
+  m.def("fwd_seq_tail", [fc_xent_args](py::dict d, py::dict fd, uintptr_t s) {
+    SeqFwdArgs a;
+    a.HSb = GP(u16, d, "HSb"); a.HSf = GP(float, d, "HSf"); a.HT = GP(u16, d, "HT"); a.ldT = get<int>(d, "ldT", 0);
+    a.HF = GP(u16, d, "HF"); a.xch = GP(u16, d, "xch");
+    a.sr = GP(float, d, "sr"); a.sz = GP(float, d, "sz"); a.sn = GP(float, d, "sn"); a.sghn = GP(float, d, "sghn");
+    a.Whh = GP(const u16, d, "Whh"); a.bhh = GP(const float, d, "bhh");
+    a.P = GP(const float, d, "P"); a.ids = GP(const int, d, "ids"); a.Gi = GP(const float, d, "Gi");
+    a.h0 = GP(const float, d, "h0");
+    a.cnt = GP(unsigned, d, "cnt"); a.err = GP(unsigned, d, "err");
+    a.dbg = GP(unsigned long long, d, "dbg"); a.allow_local = get<int>(d, "allow_local", 1);
+    a.xring = get<int>(d, "xring", 0);
+    a.s16 = GP(u16, d, "s16");
+    a.zero_next = GP(unsigned, d, "zero_next"); a.zero_words = get<long>(d, "zero_words", 0);
+    a.T = get<int>(d, "T", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
+    const FcXentArgs f = fc_xent_args(fd);
+    if (!a.xch || !a.cnt || !a.HSb || !a.HSf || !a.Whh || !a.bhh) throw std::runtime_error("fwd_seq_tail: HSb/HSf/xch/cnt/Whh/bhh required");
+    if (!gru_fwd_seq_tail_supported(a.H, a.Bp, f.V)) throw std::runtime_error("fwd_seq_tail: shape not supported");
+    gru_fwd_seq_tail(a, f, S(s));
     HIP_LAUNCH_CHECK();
   });
   // the row-wise softmax-xent of the large-H plans on caller-made fp32 logits [M][V]: the fc_xent dict

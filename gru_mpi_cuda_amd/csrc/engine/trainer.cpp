@@ -224,6 +224,12 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
   fc_in_fwd_ = persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !seq_.empty() &&
                seq_[0].bwd && seq_[0].fuse_w && seq_[0].HF && step_lds_variants().fwd_fc &&
                Bp_ / 32 <= kFcSplitsMax && gru_fwd_seq_fc_supported(d_.H, Bp_, d_.V);
+  // (the shape test is the one record_fb_seq launches the fused V = 256 head under)
+  // (and the packed saves: the tail kernel is built for them alone, which is what keeps its step loop free
+  // of scalar spills)
+  fc_tail_ = persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !fc_in_fwd_ && seq_[0].s16 &&
+             d_.V % 128 == 0 && d_.H % (16 * (d_.V / 64)) == 0 && step_lds_variants().fc_tail &&
+             step_lds_variants().fc_flash == 0 && gru_fwd_seq_tail_supported(d_.H, Bp_, d_.V);
 }
 
 Trainer::~Trainer() {

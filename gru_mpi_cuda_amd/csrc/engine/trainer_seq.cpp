@@ -174,6 +174,18 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     if (!seq_[l].bwd) fill_f32(reinterpret_cast<float*>(a.cnt), fw, 0.f, s);
     return a;
   };
+  // the FC head's arguments: fc_xent's after the forward, or the forward's own with the head as its tail
+  auto fc_args = [&]() {
+    FcXentArgs f;
+    f.X = Ls_[L - 1].HSb + (size_t)B * H; f.W = Wfc; f.b = P("fc.bias");
+    f.labels = labels_; f.inv_count = inv_count_;
+    f.dl = dl_; f.dlT = dlT_; f.ldT = (int)ldG_; f.colT = 0;
+    f.loss_part = loss_part_; f.M = (int)tok; f.H = H; f.V = V;
+    return f;
+  };
+  auto fc_fuse_dh = [&](FcXentArgs& f) {   // dy_top = dlogits · W_fc inside the head (dlogits never leave LDS)
+    f.dl = nullptr; f.WT = WfcT; f.dy = Ls_[L - 1].dy; f.Wf = WfcF; f.WTf = WfcTF;
+  };
   for (int l = 0; l < L; ++l) {
     Layer& y = Ls_[l];
     if (l > 0) {
@@ -202,6 +214,11 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       f.Wf = WfcF; f.WTf = WfcTF; f.b = P("fc.bias"); f.labels = labels_; f.inv_count = inv_count_;
       f.dy = y.dy; f.dlF = dlT_; f.loss_part = loss_part_; f.dW = slab_fc2_; f.db = rs_fc2_; f.V = V;
       gru_fwd_seq_fc(a, f, s);
+    } else if (persist_fwd_ && fc_tail_) {
+      // the fused FC head's blocks as the tail of this launch (no fc_xent node below)
+      FcXentArgs f = fc_args();
+      fc_fuse_dh(f);
+      gru_fwd_seq_tail(fwd_args(l), f, s);
     } else if (persist_fwd_) {
       gru_fwd_seq(fwd_args(l), s);
     } else {
@@ -216,12 +233,10 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     tail.add(slab_fc2_, B / 32, (long)V * H, G("fc.weight"));
     tail.add(rs_fc2_, B / 32, V, G("fc.bias"));
   } else {
-    FcXentArgs f;
-    f.X = top.HSb + (size_t)B * H; f.W = Wfc; f.b = P("fc.bias");
-    f.labels = labels_; f.inv_count = inv_count_;
-    f.dl = dl_; f.dlT = dlT_; f.ldT = (int)ldG_; f.colT = 0;
-    f.loss_part = loss_part_; f.M = (int)tok; f.H = H; f.V = V;
-    if (fc_split_) {
+    FcXentArgs f = fc_args();
+    if (fc_tail_) {
+      // done as the tail of the forward launch: loss partials, dl^T, dy
+    } else if (fc_split_) {
       // large H: logits and dH as LDS GEMMs around a row-wise softmax-xent (the fused FC kernel
       // stages a 32 x H tile of X per workgroup; at H = 2048 that leaves it at ~0.2 PF)
       GemmArgs lg;   // logits = X · W_fc^T + b_fc
@@ -237,7 +252,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       }
     } else if (V % 128 == 0 && H % (16 * (V / 64)) == 0) {
       // dy_top = dlogits · W_fc fused into the softmax-xent kernel (dlogits never leave LDS)
-      f.dl = nullptr; f.WT = WfcT; f.dy = top.dy; f.Wf = WfcF; f.WTf = WfcTF;
+      fc_fuse_dh(f);
       fc_xent(f, s);
     } else {
       fc_xent(f, s);
@@ -584,6 +599,7 @@ std::string Trainer::plan() const {
   bool any_step = !persist_fwd_;
   for (const SeqPlan& q : seq_) any_step |= !q.bwd;
   if (any_step) p += std::string(" step=") + (gru_step_picks_lds(step_algo_, d_.H, Bp_) ? "lds" : "reg");
+  if (fc_tail_) p += " head=fwd-tail";
   p += overlap_ ? " overlap(chunks=" + std::to_string(C_) + ")" : " serial";
   return p;
 }

@@ -24,6 +24,8 @@
 #include "kernels.h"
 #include "mma_tile.h"
 #include "seq_sync.h"
+#include "fc_block.h"
+#include <type_traits>
 
 namespace gk {
 
@@ -369,9 +371,93 @@ DEV void fwd_fc_consumer(const SeqFwdArgs& a, const SeqFcArgs& f, unsigned char*
 }
 
 
-template <int NKW, int RS, bool FC, int WPE = FC ? 4 : 1>
-__global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, SeqFcArgs fc) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[FC ? (kFwdFcLds > kFwdRecLds ? kFwdFcLds : kFwdRecLds) : kFwdRecLds];
+// X tile policy of the tail (fc_block.h): the block's W_fc chunks go out first, then the wait for the
+// row block's producers (epoch T + 1: every h of the row block is in HSb), then the X loads.  X is a
+// hand-off inside the launch, so every load of it is an L1-bypassing sc1 load behind a poll that saw the
+// flags -- the consumer side of both exchange protocols (seq_sync.h row_block_local): served by the
+// XCD's own L2 where the row block is local and HSb was written with plain stores, by memory where it
+// went out write-through.  (No agent acquire: its vmcnt(0) would wait for the W_fc chunks in flight.)
+struct FcXTail {
+  static constexpr bool kWeightsFirst = true;
+  const unsigned* fl;
+  int nunit;
+  unsigned epoch;
+  unsigned* err;
+  DEV bool sc1() const { return true; }
+  DEV void ready() const { wait_flags_keep(fl, nunit, epoch, err); }
+  // opaque: every per-thread address of the block is a function of the thread index alone, and the
+  // compiler computed them ahead of the step loop, where their registers pushed scalars into VGPR lanes
+  DEV int tid() const {
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  }
+};
+
+// The tail itself.  It takes nothing from the step loop but `loc`: the launch's arguments are read again
+// from the kernel-argument segment, through a pointer the compiler cannot see through (explicit
+// arguments lie in order at their natural alignment: a at 0, the head's FcXentArgs behind it), and the
+// thread index is opaque too.  Taken from the kernel's parameters, the head's ~40 SGPRs and the values the
+// tail shares with the loop were live across the step loop, which then parked scalars in VGPR lanes
+// (96 v_readlane / v_writelane per step against the plain kernel's 17); per-thread addresses of the
+// block were computed ahead of the loop; and, as invariants of the item loop, the 64-bit address of
+// every weight fragment load (42 VGPR pairs) was hoisted out of it and spilled to scratch.
+// What this buys depends on the kernel-argument layout (asserted below and at the kernel) and on the
+// compiler's register allocation: the figures here and at the saves (no lane spill, 381 against 414
+// instructions per step, 200-201 VGPRs, no scratch) are those of AMD clang 22.0.0git (ROCm 7.2.0) and
+// want checking again (-Rpass-analysis=kernel-resource-usage, the loop's ISA) at a compiler upgrade.
+static_assert(std::is_trivially_copyable<SeqFwdArgs>::value && std::is_trivially_copyable<FcXentArgs>::value,
+              "the tail reads both argument structs back from the kernel-argument segment byte for byte");
+DEV void fwd_fc_tail(bool loc, unsigned char* smem) {
+  typedef const __attribute__((address_space(4))) char* kptr_t;
+  kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  const SeqFwdArgs& a = *(const SeqFwdArgs*)kp;
+  constexpr size_t fc_off = (sizeof(SeqFwdArgs) + alignof(FcXentArgs) - 1) / alignof(FcXentArgs) * alignof(FcXentArgs);
+  const int T = a.T, nrb = a.Bp / 32, nunit = a.H / 16;
+  const int ut = seq_unit_tile(nrb), rbk = seq_row_block(nrb);
+  unsigned* const fl = a.cnt + (size_t)rbk * nunit * kFlagStride;   // the row block's producer lines
+  const FcXTail xp{fl, nunit, (unsigned)(T + 1), a.err};
+  const int tid = xp.tid();
+  // h of the last step in HSb -> epoch T + 1.  Only wave 0 wrote HSb, and each of its publish drains
+  // covered the step before, so its own drain is the only one needed; the other waves go on to their
+  // weight loads at once (none of them sits in front of a poll of the step loop or in this drain).
+  stamp(a.dbg, T + 1, 5);
+  if (tid < 64) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tid == 0) {
+      if (loc) signal_flag_local(fl + (size_t)ut * kFlagStride, (unsigned)(T + 1));
+      else signal_flag(fl + (size_t)ut * kFlagStride, (unsigned)(T + 1));
+    }
+  }
+  // (the first block's wait_flags_keep barrier also separates the last step's staging reads from the
+  // block's LDS writes: one union)
+  for (int t = ut; t < T; t += nunit) {
+    kptr_t kf = kp + fc_off;
+    asm volatile("" : "+s"(kf));
+    const FcXentArgs f = *(const FcXentArgs*)kf;
+    fc_xent_v256_block<512, true>(f, reinterpret_cast<float*>(smem), t * nrb + rbk, xp);
+  }
+  stamp(a.dbg, T + 1, 6);
+}
+
+// TAIL = true (gru_fwd_seq_tail): the recurrence's own grid and step loop; after its last timestep each
+// workgroup signals epoch T + 1 and runs the FC head's 32-token blocks (t, rbk), t = ut, ut + nunit, ..
+// of its own row block -- fc_xent_v256_block, the body of the stand-alone fc_xent launch -- before
+// it exits.  The second kernel argument is then the FcXentArgs of that launch.
+template <bool TAIL> struct FwdFcArg { typedef SeqFcArgs type; };
+template <> struct FwdFcArg<true> { typedef FcXentArgs type; };
+static constexpr size_t kFwdTailLds = fc_xent_v256_lds(512) > kFwdRecLds ? fc_xent_v256_lds(512) : kFwdRecLds;
+
+template <int NKW, int RS, bool FC, int WPE = FC ? 4 : 1, bool TAIL = false>
+__global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, typename FwdFcArg<TAIL>::type fc) {
+  static_assert(!(FC && TAIL), "the FC consumers and the FC tail exclude each other");
+  static_assert(!TAIL || (NKW == 4 && RS == 2), "the tail is built for H = 512");
+  // (fwd_fc_tail's hand-computed offset: the parameter list is exactly these two, in this order)
+  static_assert(std::is_same<decltype(&gru_fwd_seq_kernel<NKW, RS, FC, WPE, TAIL>),
+                             void (*)(SeqFwdArgs, typename FwdFcArg<TAIL>::type)>::value,
+                "gru_fwd_seq_kernel takes (SeqFwdArgs, FC arguments) and nothing else");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[TAIL ? kFwdTailLds : FC ? (kFwdFcLds > kFwdRecLds ? kFwdFcLds : kFwdRecLds) : kFwdRecLds];
   auto& part = *reinterpret_cast<float(*)[8][6][256]>(smem);
   // padded rows (48 B / 80 B, still 16-B aligned for the vector reads): the epilogue's per-item
   // u16 writes -- rows 4 apart within a wave -- land in distinct banks (unpadded: 2-way / 4-way)
@@ -428,8 +514,11 @@ __global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, Seq
   stamp(a.dbg, T + 1, 0);   // prologue stamps in the (unused) step slot T + 1
   zero_next_flags(a.zero_next, a.zero_words);
   // (probe 3: consumers leave before the census, which then covers the producers only)
-  const int cens = FC && (fc.probe & 7) == 3 ? (int)nunit : (int)rb_lines;
-  if (FC && (fc.probe & 8)) __builtin_amdgcn_s_setprio(2);
+  int cens = (int)rb_lines;
+  if constexpr (FC) {
+    if ((fc.probe & 7) == 3) cens = (int)nunit;
+    if (fc.probe & 8) __builtin_amdgcn_s_setprio(2);
+  }
   const bool loc = a.allow_local && row_block_local(a.cnt + (size_t)rbk * rb_lines * kFlagStride, ut, cens, a.err);
   stamp(a.dbg, T + 1, 4);
 
@@ -534,7 +623,14 @@ __global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, Seq
       stamp(a.dbg, t, 4);
       const size_t hs = ((size_t)(t + 1) * Bp + b0 + (lane >> 1)) * H + j0 + (lane & 1) * 8;
       if (FC && !loc) st16_sc1(rH, (unsigned)(hs * 2), v);   // write-through: FC consumers on other XCDs
-      else *reinterpret_cast<u32x4*>(a.HSb + hs) = v;
+      else if (TAIL && !loc) {
+        // write-through for tail blocks on other XCDs: four agent-scope dword stores (sc1) at the plain
+        // store's address.  (As one sc1 buffer store through rH the branch cost the step loop ~80
+        // v_readlane / v_writelane per step -- scalars parked in VGPR lanes -- against the plain kernel's 17.)
+        unsigned* hp = reinterpret_cast<unsigned*>(a.HSb + hs);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) __hip_atomic_store(hp + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else *reinterpret_cast<u32x4*>(a.HSb + hs) = v;
       stamp(a.dbg, t, 5);
     } else if (w == 1 && a.HT) {
       const u32x4 v = *reinterpret_cast<const u32x4*>(&stgT[lane >> 2][(lane & 3) * 8]);
@@ -552,7 +648,10 @@ __global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, Seq
     load_gi(t + 1, gin);
     const int sstep = __builtin_amdgcn_readfirstlane(t * Bp * H * 4);   // uniform: no waterfall loop
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(h), rHSf, sv_lane, sstep + Bp * H * 4, 0);
-    if (a.s16) {   // packed bf16 (r, z, n, gh_n): one 8-B store at twice the fp32 offsets
+    // (TAIL: built for the packed saves only -- without the four fp32 save descriptors the step loop
+    // keeps every scalar in SGPRs: no v_readlane / v_writelane at all, 381 instructions per step against
+    // the plain kernel's 414 with 17 of them)
+    if (TAIL || a.s16) {   // packed bf16 (r, z, n, gh_n): one 8-B store at twice the fp32 offsets
       typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
       const u32x2_ pv = {(unsigned)f2bf(r) | ((unsigned)f2bf(z) << 16), (unsigned)f2bf(n) | ((unsigned)f2bf(gh[2]) << 16)};
       __builtin_amdgcn_raw_buffer_store_b64(pv, rS16, sv_lane * 2u, sstep * 2, 0);
@@ -573,6 +672,7 @@ __global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, Seq
       else signal_flag(fl, (unsigned)(T + 1));
     }
   }
+  if constexpr (TAIL) fwd_fc_tail(loc, smem);
 }
 
 // ==================================================================== two-layer wavefront forward
@@ -1173,6 +1273,25 @@ void gru_fwd_seq_fc(const SeqFwdArgs& a, const SeqFcArgs& f, hipStream_t s) {
     hipLaunchKernelGGL((gru_fwd_seq_kernel<4, 2, true, 1>), grid, block, 0, s, a, f);
   else
     hipLaunchKernelGGL((gru_fwd_seq_kernel<4, 2, true>), grid, block, 0, s, a, f);
+}
+
+// The one-layer forward with the FC head as its tail (H = 512, V = 256): the recurrence's own grid.
+// (H = 1024 is not built: no plan of the trainer would take it untested.)
+bool gru_fwd_seq_tail_supported(int H, int Bp, int V) {
+  if (H != 512 || V != 256 || Bp % 32 || fwd_rs(H) != 2) return false;
+  const int cap = resident_blocks(gru_fwd_seq_kernel<4, 2, false, 1, true>);
+  return cap >= (H / 16) * (Bp / 32);
+}
+
+void gru_fwd_seq_tail(const SeqFwdArgs& a, const FcXentArgs& f, hipStream_t s) {
+  if (a.H != 512 || f.H != 512 || f.V != 256 || f.M != a.T * a.Bp || f.X != a.HSb + (size_t)a.Bp * a.H || !f.Wf || !f.WTf ||
+      !f.dy || f.dl || !f.dlT || !f.loss_part || !f.labels || !f.inv_count || !f.b || !a.s16)
+    throw std::runtime_error("gru_fwd_seq_tail: needs H = 512, V = 256, the packed saves (s16), X = HSb + Bp * H and the "
+                             "fused-dH FC arguments");
+  if ((size_t)(a.T + 1) * a.Bp * a.H * (a.s16 ? 8 : 4) >= (1ull << 31))
+    throw std::runtime_error("gru_fwd_seq_tail: saves exceed the 2 GB buffer-offset range");
+  dim3 grid((a.H / 16) * (a.Bp / 32)), block(512);
+  hipLaunchKernelGGL((gru_fwd_seq_kernel<4, 2, false, 1, true>), grid, block, 0, s, a, f);
 }
 
 #define FWD2_VARIANTS(X) X(256, 1) X(512, 2) X(1024, 4)

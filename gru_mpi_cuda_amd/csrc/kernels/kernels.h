@@ -96,6 +96,8 @@ struct StepLdsVariants {
                          // softmax over 4 vocabulary chunks, fc.hip); 0: the 8-wave two-stream kernel
   int fwd_fc = 0;        // one-layer H = 512, V = 256: the FC head (fc_xent + dW_fc) as consumer
                          // workgroups inside the persistent forward launch (gru_fwd_seq_fc); 0: after it
+  int fc_tail = 1;       // one-layer H = 512, V = 256: the fused FC head (fc_xent's 32-token blocks) as the tail
+                         // of the persistent forward launch (gru_fwd_seq_tail); 0: its own launch after it
   int big_dy = 1;        // top layer on the persistent large-H backward, V = 256: dy = dl · W_fc inside it
                          // (SeqBwdArgs::dl) instead of the dH GEMM + an fp32 dy in memory
   int ld_pad = -1;       // padding of the dGh^T / dGi^T / dl^T leading dimension: -1 = 64 elements where
@@ -183,6 +185,15 @@ struct SeqFcArgs {
 };
 bool gru_fwd_seq_fc_supported(int H, int Bp, int V);
 void gru_fwd_seq_fc(const SeqFwdArgs& a, const SeqFcArgs& f, hipStream_t s);
+// The FC head as the tail of the one-layer persistent forward: the recurrence's own grid (no extra
+// workgroups, the step loop untouched); after its last timestep workgroup (row block rbk, unit tile ut)
+// runs the fc_xent blocks of steps t = ut, ut + H/16, .. of its row block (fc_block.h: the body of the
+// stand-alone fc_xent launch, bit-for-bit the same results).  f is the FcXentArgs that launch would
+// take (fused dH: dy, Wf, WTf, no dl; X = a.HSb + Bp * H, M = T * Bp).  The saves must be the packed
+// ones (a.s16).
+struct FcXentArgs;
+bool gru_fwd_seq_tail_supported(int H, int Bp, int V);
+void gru_fwd_seq_tail(const SeqFwdArgs& a, const FcXentArgs& f, hipStream_t s);
 
 
 // Two-layer wavefront forward (gru_seq.hip gru_fwd_seq2_kernel): ONE persistent launch runs layer

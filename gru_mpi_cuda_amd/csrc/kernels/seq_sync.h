@@ -70,7 +70,7 @@ struct SpinBudget {
 // per hop (32 atomic adders + 256 pollers on one line; scripts/probe_seq.py).
 static constexpr int kFlagStride = 16;   // uints (64 B)
 
-DEV void wait_flags(const unsigned* flags, int nprod, unsigned epoch, unsigned* err) {
+DEV void sweep_flags(const unsigned* flags, int nprod, unsigned epoch, unsigned* err) {   // wave 0's part
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     SpinBudget spin(err);
@@ -86,7 +86,17 @@ DEV void wait_flags(const unsigned* flags, int nprod, unsigned epoch, unsigned* 
       }
     }
   }
+}
+DEV void wait_flags(const unsigned* flags, int nprod, unsigned epoch, unsigned* err) {
+  sweep_flags(flags, nprod, epoch, err);
   __syncthreads();
+}
+// The same wait for a workgroup whose waves have prefetches in flight: the closing barrier carries no
+// release fence (that fence is an s_waitcnt vmcnt(0) in every wave, which would wait for the
+// prefetches).  Loads issued after it follow, in program order, a poll that saw the flags.
+DEV void wait_flags_keep(const unsigned* flags, int nprod, unsigned epoch, unsigned* err) {
+  sweep_flags(flags, nprod, epoch, err);
+  lds_barrier();
 }
 // Wave-level variant: a wave's K-slice of the recurrent GEMM only reads the columns produced by
 // a few unit-tile workgroups, so each wave waits for exactly those (lane p polls producer

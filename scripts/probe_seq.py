@@ -1,6 +1,8 @@
 """Phase timing of the persistent forward sequence kernel (diagnostic stamps, 100 MHz clock).
 
 Prints per-step durations of: wait (poll), A-load+MFMA+LDS partials, epilogue, publish.
+TAIL=1: the launch with the FC head as its tail (fwd_seq_tail); adds tail_us, the time from the end of
+the step loop to the end of the workgroup's FC block (stamps 5 and 6 of slot T + 1).
 """
 import os, sys, json, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,7 +31,28 @@ d = dict(allow_local=int(os.environ.get("LOCAL", 1)), HSb=HSb.data_ptr(), xch=xc
          Whh=Whh.data_ptr(), bhh=bhh.data_ptr(), P=P.data_ptr(), ids=ids.data_ptr(),
          cnt=cnt.data_ptr(), err=err.data_ptr(), T=T, Bp=Bp, H=H,
          xring=int(os.environ.get("XR", 4)), tag=int(os.environ.get("TAG", 0)))
-res = {}
+TAIL = int(os.environ.get("TAIL", 0))
+S16 = int(os.environ.get("S16", TAIL))   # packed bf16 saves (the tail launch takes no others)
+if S16:
+    s16 = torch.zeros(T, Bp, H, 4, device=dev, dtype=torch.bfloat16)
+    d["s16"] = s16.data_ptr()
+    for k in ("sr", "sz", "sn", "sghn"):
+        d.pop(k)
+if TAIL:
+    from gru_mpi_cuda_amd.ops import ft_layout
+    Wfc = (torch.randn(V, H, device=dev) / H ** 0.5).bfloat16()
+    WfcT = Wfc.T.contiguous()
+    Wf, WTf = ft_layout(Wfc), ft_layout(WfcT)
+    bfc = torch.zeros(V, device=dev)
+    labels = torch.randint(0, V, (T, Bp), device=dev, dtype=torch.int32)
+    inv = torch.full((1,), 1.0 / (T * Bp), device=dev)
+    dlT = torch.zeros(V, T * Bp, device=dev, dtype=torch.bfloat16)
+    lp = torch.zeros(T * Bp // 32, device=dev)
+    dy = torch.zeros(T * Bp, H, device=dev)
+    fd = dict(X=HSb[1:].data_ptr(), W=Wfc.data_ptr(), b=bfc.data_ptr(), labels=labels.data_ptr(), inv_count=inv.data_ptr(),
+              dlT=dlT.data_ptr(), loss_part=lp.data_ptr(), M=T * Bp, H=H, V=V, ldT=T * Bp, colT=0,
+              WT=WfcT.data_ptr(), dy=dy.data_ptr(), Wf=Wf.data_ptr(), WTf=WTf.data_ptr())
+res = {"tail": TAIL, "s16": S16}
 for mode in ("plain", "dbg"):
     if mode == "dbg":
         d["dbg"] = dbg.data_ptr()
@@ -40,7 +63,10 @@ for mode in ("plain", "dbg"):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        C.fwd_seq(d, s)
+        if TAIL:
+            C.fwd_seq_tail(d, fd, s)
+        else:
+            C.fwd_seq(d, s)
         e1.record()
         torch.cuda.synchronize()
         times.append(e0.elapsed_time(e1) * 1000)
@@ -54,4 +80,8 @@ for wg in (0, 1):
           "pub": x[1:, 4] - x[1:, 3], "hsb": x[1:, 5] - x[1:, 4], "saves": x[1:, 6] - x[1:, 5],
           "loop": x[2:, 0] - x[1:-1, 6], "step": x[2:, 0] - x[1:-1, 0]}
     res[f"wg{wg}"] = {k: round(float(np.median(v)) / 1000, 3) for k, v in ph.items()}
+if TAIL:
+    tl = dbg.view(2, 4096, 8)[:, T + 1, :].cpu().numpy().astype(np.float64) * 10.0   # ns
+    res["tail_us"] = [round(float(tl[wg, 6] - tl[wg, 5]) / 1000, 3) for wg in (0, 1)]
+    res["last_step_to_tail_us"] = [round(float(tl[wg, 5] - st[wg, T - 1, 6]) / 1000, 3) for wg in (0, 1)]
 print(json.dumps(res))
