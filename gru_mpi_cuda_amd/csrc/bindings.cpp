@@ -723,6 +723,99 @@ PYBIND11_MODULE(_C, m) {
     sample_ctl_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
+  // the generation path's kernels on caller-owned buffers (tests/test_gen_gpu.py): the persistent
+  // launch with its workspace (layout: kernels.h, GenPersistArgs::ws), the fp32 gates, the batch
+  // reset and the scorer's two kernels
+  m.def("gen_persist_supported", &gen_persist_supported);
+  m.def("gen_persist_ws_floats", &gen_persist_ws_floats);
+  m.def("gen_persist_sync_words", &gen_persist_sync_words);
+  m.def("gen_persist_fill_ws", [](uintptr_t ws, int H, int L, int V, int ML, uintptr_t s) {
+    if (!ws) throw std::runtime_error("gen_persist_fill_ws: ws required");
+    gen_persist_fill_ws(Pp<float>(ws), H, L, V, ML, S(s));
+  });
+  m.def("gen_persist", [](py::dict d, uintptr_t s) {
+    GenPersistArgs a;
+    a.N = get<int>(d, "N", 0); a.H = get<int>(d, "H", 0); a.L = get<int>(d, "L", 0); a.V = get<int>(d, "V", 0);
+    a.ML = get<int>(d, "ML", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    a.par = get<int>(d, "par", 0);
+    if (a.L < 1 || a.L > 4) throw std::runtime_error("gen_persist: 1 <= L <= 4");
+    if (a.sos < 0 || a.sos >= a.V) throw std::runtime_error("gen_persist: 0 <= sos < V");
+    auto ptrs = [&](const char* k, const float* (&dst)[4], int first) {
+      const auto v = get<std::vector<uintptr_t>>(d, k, {});
+      if ((int)v.size() != a.L) throw std::runtime_error(std::string("gen_persist: ") + k + " needs L pointers");
+      for (int l = first; l < a.L; ++l) dst[l] = Pp<const float>(v[l]);
+    };
+    ptrs("Whh", a.Whh, 0); ptrs("bhh", a.bhh, 0); ptrs("Wih", a.Wih, 1); ptrs("bih", a.bih, 1);
+    a.Wfc = GP(const float, d, "Wfc"); a.bfc = GP(const float, d, "bfc"); a.P = GP(const float, d, "P");
+    a.rf = GP(const float, d, "rf"); a.out = GP(unsigned char, d, "out"); a.probs = GP(float, d, "probs");
+    a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
+    gen_persist_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("gru_gates_f32", [](py::dict d, uintptr_t s) {
+    GruGatesF32Args a;
+    a.P = GP(const float, d, "P"); a.ids = GP(const int, d, "ids"); a.Gi = GP(const float, d, "Gi");
+    a.Gh = GP(const float, d, "Gh");
+    a.gi_splits = get<int>(d, "gi_splits", 1); a.gh_splits = get<int>(d, "gh_splits", 1);
+    a.gi_slab = get<long>(d, "gi_slab", 0); a.gh_slab = get<long>(d, "gh_slab", 0);
+    a.hprev = GP(const float, d, "hprev"); a.hout = GP(float, d, "hout");
+    a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0); a.V = get<int>(d, "V", 0);
+    a.err = GP(unsigned, d, "err"); a.bgh = GP(const float, d, "bgh"); a.bgi = GP(const float, d, "bgi");
+    a.hsplit = GP(unsigned short, d, "hsplit");
+    const long row = 3L * a.H * a.Bp;
+    if (a.Bp <= 0 || a.H <= 0 || !a.Gh || !a.hprev || !a.hout || (a.P ? !a.ids || a.V <= 0 : !a.Gi) ||
+        a.gi_splits < 1 || a.gh_splits < 1 || (a.gh_splits > 1 && a.gh_slab < row) ||
+        (!a.P && a.gi_splits > 1 && a.gi_slab < row))
+      throw std::runtime_error("gru_gates_f32: Gh, hprev, hout, (P, ids, V) or Gi, and slabs >= Bp * 3H required");
+    gru_gates_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("gen_reset", [](py::dict d, uintptr_t s) {
+    GenResetArgs a;
+    a.L = get<int>(d, "L", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0); a.ML = get<int>(d, "ML", 0);
+    a.sos = get<int>(d, "sos", 0); a.hb_cols = get<int>(d, "hb_cols", 0);
+    const auto hf = get<std::vector<uintptr_t>>(d, "hf", {}), hb = get<std::vector<uintptr_t>>(d, "hb", {});
+    if (a.L < 1 || a.L > 4 || (int)hf.size() != a.L || (!hb.empty() && (int)hb.size() != a.L))
+      throw std::runtime_error("gen_reset: 1 <= L <= 4, L hf pointers and no or L hb pointers");
+    for (int l = 0; l < a.L; ++l) {
+      a.hf[l] = Pp<float>(hf[l]);
+      if (!hb.empty()) a.hb[l] = Pp<unsigned short>(hb[l]);
+      if (!a.hf[l]) throw std::runtime_error("gen_reset: null hf");
+    }
+    a.ids = GP(int, d, "ids"); a.alive = GP(int, d, "alive"); a.out = GP(unsigned char, d, "out");
+    if (!a.ids || !a.alive || !a.out || a.Bp <= 0 || a.H <= 0 || a.ML <= 0)
+      throw std::runtime_error("gen_reset: ids, alive, out, Bp, H, ML required");
+    gen_reset(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("score_set_count", [](uintptr_t n_dev, int n, uintptr_t s) {
+    if (!n_dev) throw std::runtime_error("score_set_count: n_dev required");
+    score_set_count(Pp<int>(n_dev), n, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("score_prep", [](py::dict d, uintptr_t s) {
+    ScorePrepArgs a;
+    a.rows = GP(const unsigned char, d, "rows"); a.n_dev = GP(const int, d, "n_dev");
+    a.ids = GP(int, d, "ids"); a.tgt = GP(int, d, "tgt"); a.ntok = GP(int, d, "ntok"); a.err = GP(unsigned, d, "err");
+    a.N = get<int>(d, "N", 0); a.Bp = get<int>(d, "Bp", 0); a.ML = get<int>(d, "ML", 0); a.V = get<int>(d, "V", 0);
+    a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    if (!a.rows || !a.ids || !a.tgt || !a.ntok || a.N < 0 || a.N > a.Bp)
+      throw std::runtime_error("score_prep: rows, ids, tgt, ntok and 0 <= N <= Bp required");
+    score_prep(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("score_logprob", [](py::dict d, uintptr_t s) {
+    ScoreLogprobArgs a;
+    a.logits = GP(const float, d, "logits"); a.splits = get<int>(d, "splits", 1); a.slab = get<long>(d, "slab", 0);
+    a.bias = GP(const float, d, "bias"); a.tgt = GP(const int, d, "tgt"); a.ntok = GP(const int, d, "ntok");
+    a.tok_logp = GP(float, d, "tok_logp"); a.rank = GP(int, d, "rank"); a.name_logp = GP(float, d, "name_logp");
+    a.ntok_out = GP(int, d, "ntok_out");
+    a.Bp = get<int>(d, "Bp", 0); a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0);
+    if (!a.logits || !a.tgt || !a.ntok || !a.tok_logp || !a.rank || !a.name_logp || !a.ntok_out)
+      throw std::runtime_error("score_logprob: logits, tgt, ntok, tok_logp, rank, name_logp, ntok_out required");
+    score_logprob_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
   m.def("reduce_slabs", [](uintptr_t src, int splits, long n, uintptr_t dst, uintptr_t s) {
     reduce_slabs(Pp<const float>(src), splits, n, Pp<float>(dst), S(s));
     HIP_LAUNCH_CHECK();

@@ -233,6 +233,10 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
 }
 
 Trainer::~Trainer() {
+  // first: the watchdog thread polls (hipEventQuery) the stage_done_ / group_done_ event of the last
+  // launched step and reads err_host_; it must have stopped before any of them is destroyed (a poll
+  // between the hipEventDestroy below and a later join queried a destroyed event)
+  wd_.reset();
   if (pbf_) (void)hipFree(pbf_);
   if (bpack_) (void)hipFree(bpack_);
   for (auto& g : g_fb_) g.reset();
@@ -245,7 +249,6 @@ Trainer::~Trainer() {
   for (auto& e : group_done_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {copy_done_[0], copy_done_[1], group_copy_done_[0], group_copy_done_[1]})
     if (e) (void)hipEventDestroy(e);
-  wd_.reset();   // the watchdog thread reads err_host_
   if (h_stage_) (void)hipHostFree(h_stage_);
   if (err_host_) (void)hipHostFree(err_host_);
   if (s0_) (void)hipStreamDestroy(s0_);

@@ -176,9 +176,10 @@ __global__ void gru_gates_f32_kernel(GruGatesF32Args a) {
   if (a.P) {
     int id = a.ids[b];
     if (id < 0 || id >= a.V) {   // never expected: flag it instead of reading outside the table
-      if (a.err && j == 0) {
-        atomicOr(a.err, 16u);
-        a.err[1] = (unsigned)id;   // diagnostics: the offending value and row
+      // diagnostics: the offending value and row, written by the row that sets the bit first (with
+      // several bad rows, each storing both words, err[1] and err[2] could name different rows)
+      if (a.err && j == 0 && !(atomicOr(a.err, 16u) & 16u)) {
+        a.err[1] = (unsigned)id;
         a.err[2] = (unsigned)b;
       }
       id = 0;

@@ -319,7 +319,9 @@ struct GruGatesF32Args {           // h' = GRU gates from gi (or P[ids]) and gh 
   long gi_slab = 0, gh_slab = 0;
   const float* hprev = nullptr; float* hout = nullptr;   // [Bp][H]
   int Bp = 0, H = 0, V = 0;
-  unsigned* err = nullptr;         // layer 0: bit 4 set (and the row clamped) on a char id outside [0, V)
+  // layer 0: bit 4 set on a char id outside [0, V); such a row reads table row 0.  err[1], err[2] = the
+  // id and the row of ONE offender: the row that set the bit first since err[0] was cleared
+  unsigned* err = nullptr;
   // bf16x3 mode: biases not folded into split-K slabs (nullable), and the bf16 split copy of h'
   // written as the next products' A operand: hsplit[b] = [hi | hi | lo] of h'[b] ([Bp][3H])
   const float* bgh = nullptr; const float* bgi = nullptr;
@@ -369,6 +371,30 @@ void gen_reset(const GenResetArgs& a, hipStream_t s);
 // Persistent fp32 generation for small batches (gen_persist.hip): ONE launch runs every char of up to
 // 64 names with the fp32 recurrent weights resident in VGPRs across 256 workgroups (exchange
 // buffers in `ws`).
+//
+// The workspace (tests/test_gen_gpu.py reads it back; models/gen_ref.py: ws_decode).  `ws` holds two
+// sets of S = L ML 64 H + ML 64 (V + 1) floats; a launch exchanges through set `par` only, and every
+// char has its own slots there (nothing is reused inside a launch), so after the launch set `par`
+// holds the whole trajectory.  In floats from the start of a set:
+//   * states, plain layout: h_l(t)[n][c] at ((l ML + t) 64 + n) H + c;
+//   * states, tagged layout (H = 1024 and N <= 8): producer p's line of 32 floats at
+//     ((l ML + t) 256 + p) 32, name n's units 4p .. 4p + 3 at n 4 (the rest of the line is not written);
+//   * logits(t)[n][v] at L ML 64 H + (t 64 + n) V + v;
+//   * ids, N > 16 only: the char sampled from logits(t), as id | alive-after << 16, at
+//     L ML 64 H + ML 64 V + t 64 + n for t < ML - 1 (the last char's id is not published).
+// A launch that runs T chars (T = ML, or see `probs`) writes, for t < T: rows n < N (N <= 16) or
+// n < Np = roundup(N, 16) (N > 16) of the states and logits, and the ids of rows n < N.  Rows n < N are
+// defined; rows N <= n < Np may be written and are unspecified; rows n >= Np, chars t >= T and every
+// other word of set `par` are not written.  In the OTHER set the launch stores the fill word
+// 0xFFFFFFFF over the first L ML 256 32 floats of the states and over all ML 64 V logits (what a
+// launch polls as "not yet written" when it hands off without flags) and nothing else; before the
+// first launch the caller fills both sets (gen_persist_fill_ws).  `sync` is all zero again after
+// every launch.
+// A name's output row stops at its EOS byte (bytes after it and byte ML stay 0; rows n >= N are not
+// written; a char id is stored as its low eight bits), but the sampled id feeds the next char's
+// layer 0 whether or not the name has ended, so the states of an ended name follow its samples.
+// With probs == nullptr the launch stops before the first char t >= 1 at which every name has ended
+// (T = t); with probs set it runs all ML chars and writes rows n < N of the last char's softmax.
 struct GenPersistArgs {
   const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
   const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
