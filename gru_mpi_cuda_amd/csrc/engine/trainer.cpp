@@ -230,6 +230,12 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
   fc_tail_ = persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !fc_in_fwd_ && seq_[0].s16 &&
              d_.V % 128 == 0 && d_.H % (16 * (d_.V / 64)) == 0 && step_lds_variants().fc_tail &&
              step_lds_variants().fc_flash == 0 && gru_fwd_seq_tail_supported(d_.H, Bp_, d_.V);
+  // (the tail kernel is built for the packed saves, the HF copy and no transposed dG copies: the fused
+  // dW_hh + dP plan of a persistent forward)
+  bwd_tail_ok_ = d_.L == 1 && !overlap_ && seq_[0].bwd && seq_[0].fuse_w && seq_[0].fuse_p && !seq_[0].rows16 &&
+                 seq_[0].s16 && seq_[0].HF && step_lds_variants().bwd_tail && d_.V % seq_[0].nrb == 0 &&
+                 (d_.V / seq_[0].nrb) % 8 == 0 && gru_bwd_seq_tail_supported(d_.H, Bp_, d_.V);
+  bwd_tail_ = bwd_tail_ok_ && use_graph_ && o_.clip <= 0.f;   // what a single-GPU step() will take (record_fb_seq)
 }
 
 Trainer::~Trainer() {
@@ -763,6 +769,7 @@ void Trainer::optimizer_step(hipStream_t s) {
 void Trainer::set_comm(RcclComm* c, const std::vector<std::pair<long, long>>& buckets, long min_bucket_floats) {
   comm_ = c;
   if (!c) shard_opt_ = false;
+  if (c) bwd_tail_ = false;   // data-parallel steps keep the reduce launch (record_fb_seq)
   buckets_ = buckets;
   min_bucket_ = std::max(1L, min_bucket_floats);
   // the overlapped path relies on the readiness order of the flat layout (models/params.py)
@@ -879,6 +886,7 @@ void Trainer::step(hipStream_t s) {
     } catch (...) {
       defer_slabs_ = false;
       deferred_.n = 0;
+      in_step_ = false;
       hipGraph_t broken = nullptr;          // leave the stream out of capture mode, then rethrow
       (void)hipStreamEndCapture(s0_, &broken);
       if (broken) (void)hipGraphDestroy(broken);
@@ -925,6 +933,7 @@ void Trainer::step_group(hipStream_t s) {
     } catch (...) {
       defer_slabs_ = false;
       deferred_.n = 0;
+      in_step_ = false;
       hipGraph_t broken = nullptr;
       (void)hipStreamEndCapture(s0_, &broken);
       if (broken) (void)hipGraphDestroy(broken);
@@ -940,11 +949,13 @@ void Trainer::step_group(hipStream_t s) {
 }
 
 void Trainer::record_step_body() {
+  in_step_ = true;   // (record_fb_seq notes what this step does with the backward's tail, for plan())
   if (shard_opt_) {
     // sharded optimiser: whole backward first (slab sums into the flat gradient), then
     // reduce-scatter -> Adam on the owned slice -> all-gather -> bf16 refresh
     deferred_.n = 0;
     if (overlap_) record_fb(s0_); else record_fb_seq(s0_);
+    in_step_ = false;
     record_sharded_opt(s0_);
     return;
   }
@@ -954,11 +965,13 @@ void Trainer::record_step_body() {
     // readiness-ordered collectives on the comm stream, overlapped with the rest of the
     // backward; joined before the optimiser (the embedding-side tail runs after the join)
     record_fb_seq(s0_, /*dp=*/true);
+    in_step_ = false;
     if (opt_in_fb_) { opt_in_fb_ = false; return; }   // the pipelined tail recorded its own Adam launches
   } else {
     defer_slabs_ = !overlap_ && !comm_ && o_.clip <= 0.f;
     if (overlap_) record_fb(s0_); else record_fb_seq(s0_);
     defer_slabs_ = false;
+    in_step_ = false;
     record_allreduce(s0_);
   }
   record_opt(s0_);

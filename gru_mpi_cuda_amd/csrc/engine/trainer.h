@@ -50,7 +50,7 @@ class Trainer {
   int get_step();                                       // optimiser step counter (device)
   void set_step(int v);                                 // for resume
   void set_lr(float lr);
-  void set_use_graph(bool g) { use_graph_ = g; }
+  void set_use_graph(bool g) { use_graph_ = g; if (!g) bwd_tail_ = false; }   // (eager steps keep the reduce launch)
   // Truncated BPTT over a continuous stream: with carry on, each step starts from
   // the previous step's final hidden state (HS[T] -> HS[0] copies at the head of the step graph;
   // no gradient flows into it).  reset_hidden zeroes the carried state.
@@ -248,6 +248,14 @@ class Trainer {
   // (gru_fwd_seq_tail): no fc_xent launch; everything behind it (dW_fc K-slices, slabs, HT) unchanged;
   // decided per trainer (StepLdsVariants::fc_tail)
   bool fc_tail_ = false;
+  // one-layer H = 512, V = 256: the persistent backward also sums its dP row-block partials, the loss
+  // partials and bumps the step counter (gru_bwd_seq_tail), so the single-GPU one-graph step records no
+  // reduce_multi launch (StepLdsVariants::bwd_tail).  bwd_tail_ok_: the trainer's shape and plan allow it
+  // (constructor); the step itself decides per recording (record_fb_seq: only where that launch would hold
+  // exactly these three jobs).  bwd_tail_: what step() takes -- predicted from the options at construction,
+  // then what the last recorded step did (plan()).
+  bool bwd_tail_ok_ = false, bwd_tail_ = false;
+  bool in_step_ = false;       // record_fb_seq is recording a step (record_step_body), not forward_backward()
   bool dy_in_bwd_ = false;     // the top layer's large-H backward computes dy = dl · W_fc itself (big_dy)
   bool fwd_wave_ = false;      // layer pairs (0,1), (2,3).. forward as one wavefront launch (gru_fwd_seq2)
   float* bpart_ = nullptr;     // split-K partial tiles of the persistent large-H backward

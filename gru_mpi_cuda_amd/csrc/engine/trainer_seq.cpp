@@ -5,7 +5,8 @@
 //   -> [per layer, top-down: backward sequence kernel with fused dW_hh / dP / bias partials
 //       -> (l>0) dW_ih GEMM + dX GEMM]
 //   -> one multi-tensor reduction of all partial slabs (+ loss) -> dW_ih0 / dEmb GEMMs (single GPU:
-//      with the dW_fc K-slices in the same launch).
+//      with the dW_fc K-slices in the same launch).  One layer, H = 512, V = 256, single-GPU one-graph step:
+//      that reduction runs as the tail of the backward sequence kernel instead (gru_bwd_seq_tail).
 //
 // Every layer falls back to the per-timestep kernels when its shape cannot be made
 // co-resident (gru_*_seq_supported), so any config still runs -- just slower.
@@ -121,11 +122,12 @@ void Trainer::wgrad_gemm(const u16* A, int lda, const u16* Bm, int ldb, int M, i
   reduce_slabs_multi(j, s);
 }
 
+// deep split-K slabs (32) stay with the reduce kernel: summed inside the Adam launch they serialise
+// 32 loads per element on its few tile blocks (16: two batches of 8 in flight)
+static constexpr int kDeferMaxSplits = 16;
+
 void Trainer::slab_job(SlabJobs& j, const float* src, int splits, long n, float* dst) {
-  // deep split-K slabs (32) stay with the reduce kernel: summed inside the Adam launch they serialise
-  // 32 loads per element on its few tile blocks (16: two batches of 8 in flight)
-  constexpr int max_splits = 16;
-  SlabJobs& t = (defer_slabs_ && splits <= max_splits) ? deferred_ : j;
+  SlabJobs& t = (defer_slabs_ && splits <= kDeferMaxSplits) ? deferred_ : j;
   if (t.n >= 24) throw std::runtime_error("slab job list full");
   t.add(src, splits, n, dst);
 }
@@ -305,6 +307,13 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     tail.add(slab_fc2_, sp, (long)V * H, G("fc.weight"));
     tail.add(rs_fc2_, sp, V, G("fc.bias"));
   }
+  // The dP cast job, the loss partials and the step-counter bump as the tail of layer 0's persistent
+  // backward (gru_bwd_seq_tail) where the reduce launch after it would hold exactly these three: the
+  // single-GPU one-graph step with every other slab job of layer 0 (and the dW_fc / db_fc slabs) summed
+  // inside Adam.  Decided here, before the backward launch is recorded; anything else takes the reduce.
+  bool bwd_tail = bwd_tail_ok_ && !dp && defer_slabs_ && seq_[0].nrb <= kDeferMaxSplits;
+  for (int k2 = 0; k2 < tail.n; ++k2) bwd_tail = bwd_tail && tail.job[k2].splits <= kDeferMaxSplits;
+  if (in_step_) bwd_tail_ = bwd_tail;
   // ------------------------------------------------------------------ backward (BPTT)
   for (int l = L - 1; l >= 0; --l) {
     Layer& y = Ls_[l];
@@ -326,7 +335,12 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       a.T = T; a.Bp = B; a.H = H;
       if (!persist_fwd_) fill_f32(reinterpret_cast<float*>(a.cnt), fw, 0.f, s);
       a.xring = step_lds_variants().bwd_xring;
-      if (q.rows16) gru_bwd_seq16(a, s); else gru_bwd_seq(a, s);
+      if (bwd_tail && l == 0) {
+        BwdTailArgs t;
+        t.dP_bf = dP_bf_; t.dPT_bf = dPT_bf_; t.loss_part = loss_part_; t.nloss = nloss_; t.loss = loss_; t.step = step_;
+        gru_bwd_seq_tail(a, t, s);
+      } else if (q.rows16) gru_bwd_seq16(a, s);
+      else gru_bwd_seq(a, s);
     } else if (q.big) {
       SeqBwdArgs a;
       a.dy = y.dy; a.HSf = y.HSf;
@@ -355,7 +369,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     // tail runs after the data-parallel all-reduce, to fp32 dP (the tensor that is all-reduced)
     if (l == 0 && q.fuse_p) {
       if (dp) j.add(dP_part_, q.nrb, (long)V * H3, dP_target());
-      else j.add_cast(dP_part_, q.nrb, V, H3, nullptr, dP_bf_, dPT_bf_);
+      else if (!bwd_tail) j.add_cast(dP_part_, q.nrb, V, H3, nullptr, dP_bf_, dPT_bf_);
     }
     if (l == 0 && (q.bwd || q.big)) slab_job(j, q.dbih_part, q.nrb, H3, G("bias_ih_l0"));
     // dW_fc / db_fc slabs: with the top layer's group when data-parallel (the FC group is
@@ -364,7 +378,9 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     if ((dp ? l == L - 1 : l == 0) && !pipe)
       for (int k2 = 0; k2 < tail.n; ++k2)
         slab_job(j, tail.job[k2].src, tail.job[k2].splits, tail.job[k2].n, tail.job[k2].dst);
-    if (l == 0) {   // + the loss partials and the optimiser step counter
+    if (l == 0 && bwd_tail) {   // the backward's tail did all three: no reduce launch in this step
+      if (j.n) throw std::runtime_error("record_fb_seq: a slab job is left for the reduce launch the backward's tail replaced");
+    } else if (l == 0) {   // + the loss partials and the optimiser step counter
       j.add(loss_part_, nloss_, 1, loss_);
       j.bump = step_;
     }
@@ -601,6 +617,7 @@ std::string Trainer::plan() const {
   if (any_step) p += std::string(" step=") + (gru_step_picks_lds(step_algo_, d_.H, Bp_) ? "lds" : "reg");
   if (fc_tail_) p += " head=fwd-tail";
   p += overlap_ ? " overlap(chunks=" + std::to_string(C_) + ")" : " serial";
+  if (bwd_tail_) p += " dP=bwd-tail";
   return p;
 }
 

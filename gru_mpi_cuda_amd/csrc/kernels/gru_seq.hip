@@ -18,13 +18,15 @@
 //   * backward additionally accumulates the weight gradients dW_hh = Σ_t dGh_t^T h_{t-1} and
 //     the embedding-side dP = Σ_t onehot(x_t)^T dGi_t (layer 0) plus both bias gradients in
 //     registers, using the MFMA pipe that the latency-bound recurrence leaves idle; partial
-//     sums per row block are reduced by one small kernel afterwards (no float atomics).
+//     sums per row block are reduced by one small kernel afterwards, or -- the dP ones, in the one-layer
+//     H = 512 step -- by the backward itself as its tail (gru_bwd_seq_tail); no float atomics.
 // Reference mapping: this is the whole per-char hot loop of /root/reference/namegensf.cu:661-872
 // (for all names at once), plus the BPTT half the reference does not have.
 #include "kernels.h"
 #include "mma_tile.h"
 #include "seq_sync.h"
 #include "fc_block.h"
+#include "optim_dev.h"
 #include <type_traits>
 
 namespace gk {
@@ -961,8 +963,165 @@ __global__ void __launch_bounds__(512, 1) gru_fwd_seq2_kernel(SeqFwd2Args a) {
 // NTP : 16-col tiles per wave of the fused dP accumulator (V / 128); 0 = not fused
 // (Rejected and removed in round 4: dy = dl · W_fc inside this kernel, and the fused weight-gradient
 // MFMAs inside the publish drain; docs/DESIGN.md §3.4, §6.3.)
-template <int NKW3, int NTW, int NTP>
-__global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
+//
+// TAIL = true (gru_bwd_seq_tail): the same grid and step loop; the end of the kernel also does the work of
+// the single-GPU step's reduce_multi launch (bwd_dp_tail below).  The kernel argument is then
+// SeqBwdTailK: the SeqBwdArgs with the tail's own behind them.
+struct SeqBwdTailK : SeqBwdArgs { BwdTailArgs t; };
+template <bool TAIL> struct BwdKArg { typedef SeqBwdArgs type; };
+template <> struct BwdKArg<true> { typedef SeqBwdTailK type; };
+
+// The end of the TAIL kernel, in this order (with 2. behind 4. the step measured the same, docs/DESIGN.md §6.9):
+//  1. every wave's dP partials to slab rbk as 16-B write-through stores (accP[g][nt] is 4 consecutive
+//     columns of one row), the bias sums to LDS; drain (s_waitcnt vmcnt(0)), workgroup barrier, one lane
+//     signals epoch T + 1 on the workgroup's own flag line (the step loop's last signal was T);
+//  2. the bias partials and the dW_hh partials as plain stores (Adam reads them after the launch): they
+//     drain while the flags of the partners travel;
+//  3. wave 0 polls epoch T + 1 of the nrb workgroups (0 .. nrb-1, ut) -- the writers of this unit tile's 48
+//     columns in every slab, one lane each, bounded like every wait here -- then a barrier;
+//  4. rows [rbk * V / nrb, (rbk + 1) * V / nrb) x the 48 columns, 32 rows at a time: thread (row, gate,
+//     half) loads its 8 columns of every slab with L1-bypassing sc1 loads (its own slab included), all in
+//     flight at once, sums them in reduce_multi's order (slab 0, += 1, 2, ..: sum_slabs4), rounds, writes
+//     16 B of dP_bf and stages them in LDS (the dead `part`); then dPT_bf in 16-B pieces of 8 rows;
+//  5. workgroup 0: the loss partials (reduce_multi's tiny-job sum) and the step counter.
+// The hand-off is MI355X_MICROARCH.md 'Valid forms' row 1 in every cell and does not depend on where the
+// workgroups run.  Like fwd_fc_tail it takes nothing from the step loop but the accumulators: arguments
+// re-read from the kernel-argument segment through an opaque pointer, the thread index opaque.
+static_assert(std::is_trivially_copyable<SeqBwdTailK>::value, "the tail reads its arguments back from the kernel-argument segment");
+template <int NTW, int NTP>
+DEV void bwd_dp_tail(const f32x4 (&accW)[3][NTW], const f32x4 (&accP)[3][NTP], const float (&dbh)[3], float dbi,
+                     float (*red)[16][33], unsigned char* stage /* >= 32 * 56 u16 */) {
+  typedef const __attribute__((address_space(4))) char* kptr_t;
+  kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(kp));
+  const SeqBwdTailK& k = *(const SeqBwdTailK*)kp;
+  const SeqBwdArgs& a = k;
+  int tid = (int)threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
+  const int H = a.H, H3 = 3 * H, V = a.V, T = a.T, nrb = a.Bp / 32;
+  const int nunit = H / 16, ut = seq_unit_tile(nrb), rbk = seq_row_block(nrb), j0 = ut * 16;
+  const unsigned slab_bytes = (unsigned)((size_t)V * H3 * 4);
+  const rsrc_t rP = make_rsrc(a.dP_part, (unsigned)nrb * slab_bytes);   // <= 8 slabs of 1.5 MB
+  stamp(a.dbg, T + 1, 0);
+  // ---- 1. dP partials out write-through, then the signal
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+#pragma unroll
+    for (int nt = 0; nt < NTP; ++nt) {
+      const unsigned o = (unsigned)rbk * slab_bytes +
+                         (unsigned)((((w * NTP + nt) * 16 + lr) * H3 + g * H + j0 + lq * 4) * 4);
+      st16_sc1(rP, o, __builtin_bit_cast(u32x4, accP[g][nt]));
+    }
+  {
+    const int rb = tid >> 8, reg = (tid >> 6) & 3, ln = tid & 63;
+    const int row = rb * 16 + (ln >> 4) * 4 + reg, col = ln & 15;
+    red[0][col][row] = dbh[0]; red[1][col][row] = dbh[1]; red[2][col][row] = dbh[2];
+    red[3][col][row] = dbh[0]; red[4][col][row] = dbh[1]; red[5][col][row] = dbi;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  lds_barrier();
+  if (tid == 0) signal_flag(a.cnt + ((size_t)rbk * nunit + ut) * kFlagStride, (unsigned)(T + 1));
+  stamp(a.dbg, T + 1, 1);
+  // ---- 2. bias and dW_hh partials of this row block (plain)
+  if (tid < 96) {
+    const int kk = tid >> 4, c = tid & 15;
+    float sum = 0.f;
+    for (int rr = 0; rr < 32; ++rr) sum += red[kk][c][rr];
+    float* dst = (kk < 3 ? a.dbhh_part : a.dbih_part);
+    if (dst) dst[(size_t)rbk * H3 + (kk % 3) * H + j0 + c] = sum;
+  }
+  {
+    float* W = a.dWhh_part + (size_t)rbk * H3 * H;
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          W[(size_t)(g * H + j0 + lq * 4 + i) * H + (w * NTW + nt) * 16 + lr] = accW[g][nt][i];
+  }
+  // ---- 3. the partners: every writer of these 48 columns
+  if (tid < 64) {
+    SpinBudget spin(a.err);
+    for (;;) {
+      bool ok = true;
+      if (lane < nrb)
+        ok = __hip_atomic_load(a.cnt + ((size_t)lane * nunit + ut) * kFlagStride, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)(T + 1);
+      if (__all(ok)) break;
+      __builtin_amdgcn_s_sleep(GK_POLL_SLEEP);
+      if (spin.expired()) {
+        if (lane == 0) __hip_atomic_fetch_or(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        break;
+      }
+    }
+  }
+  lds_barrier();   // (no vmcnt wait: the plain stores above stay in flight)
+  stamp(a.dbg, T + 1, 2);
+  // ---- 4. sum the slabs of this workgroup's share, write the bf16 operands
+  constexpr int LDS_P = 56;   // u16 per staged row: 48 columns, 16-B aligned rows
+  u16* const tile = reinterpret_cast<u16*>(stage);
+  const int rows = V / nrb, v0 = rbk * rows;
+  const int irow = tid / 6, ipc = tid % 6;           // item: row of the chunk, 8-column piece (gate, half)
+  const int icol = (ipc >> 1) * H + j0 + (ipc & 1) * 8;
+  const int tcol = tid >> 2, tseg = tid & 3;         // transposed piece: column, 8-row segment
+  for (int r0 = 0; r0 < rows; r0 += 32) {
+    if (tid < 192 && r0 + irow < rows) {
+      const size_t e = (size_t)(v0 + r0 + irow) * H3 + icol;
+      f32x4 x[8][2];
+#pragma unroll
+      for (int s = 0; s < 8; ++s)
+        if (s < nrb) {
+          const unsigned o = (unsigned)s * slab_bytes + (unsigned)(e * 4);
+          x[s][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rP, o, 0, 16));
+          x[s][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rP, o + 16u, 0, 16));
+        }
+      f32x4 s0 = x[0][0], s1 = x[0][1];
+#pragma unroll
+      for (int s = 1; s < 8; ++s)
+        if (s < nrb) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { s0[i] += x[s][0][i]; s1[i] += x[s][1][i]; }
+        }
+      u32x4 pv;
+      pv[0] = (unsigned)f2bf(s0[0]) | ((unsigned)f2bf(s0[1]) << 16);
+      pv[1] = (unsigned)f2bf(s0[2]) | ((unsigned)f2bf(s0[3]) << 16);
+      pv[2] = (unsigned)f2bf(s1[0]) | ((unsigned)f2bf(s1[1]) << 16);
+      pv[3] = (unsigned)f2bf(s1[2]) | ((unsigned)f2bf(s1[3]) << 16);
+      *reinterpret_cast<u32x4*>(k.t.dP_bf + e) = pv;
+      *reinterpret_cast<u32x4*>(tile + irow * LDS_P + ipc * 8) = pv;
+    }
+    lds_barrier();
+    if (tid < 192 && r0 + tseg * 8 < rows) {
+      u16 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = tile[(tseg * 8 + q) * LDS_P + tcol];
+      const int gcol = (tcol >> 4) * H + j0 + (tcol & 15);
+      *reinterpret_cast<u32x4*>(k.t.dPT_bf + (size_t)gcol * V + v0 + r0 + tseg * 8) = *reinterpret_cast<const u32x4*>(v);
+    }
+    if (r0 + 32 < rows) lds_barrier();   // the tile is written again
+  }
+  // ---- 5. the loss and the step counter
+  if (blockIdx.x == 0 && tid < 64) {
+    const float l = wave_strided_sum(k.t.loss_part, k.t.nloss, 1, 0, lane);
+    if (tid == 0) {
+      k.t.loss[0] = l;
+      *k.t.step += 1;
+    }
+  }
+  stamp(a.dbg, T + 1, 3);
+}
+
+template <int NKW3, int NTW, int NTP, bool TAIL = false>
+__global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(typename BwdKArg<TAIL>::type a) {
+  static_assert(!TAIL || (NKW3 == 6 && NTW == 4 && NTP == 2), "the tail is built for H = 512, V = 256");
+  // (bwd_dp_tail reads the argument back from offset 0 of the kernel-argument segment)
+  static_assert(std::is_same<decltype(&gru_bwd_seq_kernel<NKW3, NTW, NTP, TAIL>), void (*)(typename BwdKArg<TAIL>::type)>::value,
+                "gru_bwd_seq_kernel takes one argument struct and nothing else");
+  // (TAIL: built for the plan that takes it alone -- packed saves, the HF copy, no transposed or row-major
+  // dG copies -- so the step loop carries none of the other forms' pointers: with them its scalars were
+  // parked in VGPR lanes, ~50 v_readlane per step against the plain kernel's 4)
   __shared__ __attribute__((aligned(16))) float part[8][2][256];      // 16 KB
   __shared__ __attribute__((aligned(16))) u16 srow[3][32][24];        // dGh tile, gate-major (exchange; 48-B rows)
   __shared__ __attribute__((aligned(16))) u16 sgT[4][16][40];         // dGh^T gates r,z,n + dGi_n^T (padded rows)
@@ -1018,7 +1177,7 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
   auto load_saves = [&](int t) {
     const size_t o = ((size_t)t * Bp + b) * H + j;
     sv[0] = a.dy[o];
-    if (a.s16) ld_save16_raw(a.s16 + o * 4, sv[1], sv[2]);   // unpacked at use
+    if (TAIL || a.s16) ld_save16_raw(a.s16 + o * 4, sv[1], sv[2]);   // unpacked at use
     else { sv[1] = a.sr[o]; sv[2] = a.sz[o]; sv[3] = a.sn[o]; sv[4] = a.sghn[o]; }
     sv[5] = a.HSf[o];   // HS[t] = h_{t-1}
     if constexpr (NTP > 0) svid = a.ids[(size_t)t * Bp + b];   // this thread's row id (fused dP)
@@ -1066,12 +1225,12 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
     float sr = sv[1], sz = sv[2], sn = sv[3], sghn = sv[4];
     const float dy = sv[0], hprev = sv[5];
     if (t > 0) load_saves(t - 1);
-    if (a.s16) unpack_save16(sr, sz, sr, sz, sn, sghn);
+    if (TAIL || a.s16) unpack_save16(sr, sz, sr, sz, sn, sghn);
     // operands of the fused weight-gradient MFMAs (independent of other workgroups): issued after
     // the hand-off so the poll above does not wait behind them; first used after the publish
     bf16x8 hB[NTW > 0 ? NTW : 1];
     if constexpr (NTW > 0) {
-      if (a.HF) {   // whole 1-KB fragment blocks (8 lines each) instead of 16 rows x 64 B
+      if (TAIL || a.HF) {   // whole 1-KB fragment blocks (8 lines each) instead of 16 rows x 64 B
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt)
           hB[nt] = ld8(a.HF + (((size_t)t * nunit + w * NTW + nt) * nrb + rbk) * 512 + lane * 8);
@@ -1156,7 +1315,7 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
         else signal_flag(fl, (unsigned)(s + 1));
       }
       stamp(a.dbg, s, 4);
-    } else if (w <= 4 && a.dghT) {
+    } else if (!TAIL && w <= 4 && a.dghT) {
       // transposed copies for the (non-fused) weight-gradient GEMMs: 16 units x 32 rows per gate
       const int g = w - 1;          // 0..3 : dGh r, z, n and dGi n
       const u32x4 v = *reinterpret_cast<const u32x4*>(&sgT[g][lane >> 2][(lane & 3) * 8]);
@@ -1166,7 +1325,7 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
       if (g < 3) *reinterpret_cast<u32x4*>(a.dghT + rowsel) = v;
       if (g != 2) *reinterpret_cast<u32x4*>(a.dgiT + rowsel) = v;
     }
-    if (a.dgi) {   // row-major dGi for the layer below, after the publish (not in wave 0's drain)
+    if (!TAIL && a.dgi) {   // row-major dGi for the layer below, after the publish (not in wave 0's drain)
       const size_t og = ((size_t)t * Bp + b) * H3 + j;
       a.dgi[og] = br; a.dgi[og + H] = bz; a.dgi[og + 2 * H] = bi;
     }
@@ -1175,6 +1334,10 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(SeqBwdArgs a) {
     stamp(a.dbg, s, 6);
   }
 
+  if constexpr (TAIL) {   // the partials, their dP sum, the loss and the step counter
+    bwd_dp_tail<NTW, NTP>(accW, accP, dbh, dbi, red, reinterpret_cast<unsigned char*>(&part[0][0][0]));
+    return;
+  }
   // ---- partial weight gradients of this row block
   if constexpr (NTW > 0) {
     float* W = a.dWhh_part + (size_t)rbk * H3 * H;
@@ -1351,6 +1514,28 @@ void gru_bwd_seq(const SeqBwdArgs& a, hipStream_t s) {
   // an unmatched (H, fuse dW_hh, fuse dP) must not silently leave the gradients untouched
   throw std::runtime_error("gru_bwd_seq: no kernel variant for H=" + std::to_string(a.H) +
                            " fuse_w=" + std::to_string(fw) + " fuse_p=" + std::to_string(fp));
+}
+
+// The fused backward with the dP / loss / step-counter sums as its tail (H = 512, V = 256; at most 8 row
+// blocks: the tail keeps one 8-column piece of every slab in registers).
+bool gru_bwd_seq_tail_supported(int H, int Bp, int V) {
+  if (H != 512 || V != 256 || Bp < 32 || Bp % 32 || Bp / 32 > 8) return false;
+  const int nrb = Bp / 32;
+  if (V % nrb || (V / nrb) % 8) return false;
+  const int cap = resident_blocks(gru_bwd_seq_kernel<6, 4, 2, true>);
+  return cap >= (H / 16) * nrb;
+}
+
+void gru_bwd_seq_tail(const SeqBwdArgs& a, const BwdTailArgs& t, hipStream_t s) {
+  const int nrb = a.Bp / 32;
+  if (a.H != 512 || a.V != 256 || a.Bp < 32 || a.Bp % 32 || nrb > 8 || a.V % nrb || (a.V / nrb) % 8 || !a.dWhh_part || !a.dP_part ||
+      !a.s16 || !a.HF || a.dghT || a.dgiT || a.dgi || !a.ids || !a.cnt || !a.err || !t.dP_bf || !t.dPT_bf || !t.loss_part || !t.loss || !t.step || t.nloss <= 0)
+    throw std::runtime_error("gru_bwd_seq_tail: needs H = 512, V = 256, at most 8 row blocks dividing V into multiples "
+                             "of 8 rows, the packed saves (s16), the HF copy, no dG copies, the fused dW_hh / dP "
+                             "partials and every tail buffer");
+  dim3 grid((a.H / 16) * nrb), block(512);
+  SeqBwdTailK k{a, t};
+  hipLaunchKernelGGL((gru_bwd_seq_kernel<6, 4, 2, true>), grid, block, 0, s, k);
 }
 
 }  // namespace gk

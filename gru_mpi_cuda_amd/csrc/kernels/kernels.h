@@ -98,6 +98,9 @@ struct StepLdsVariants {
                          // workgroups inside the persistent forward launch (gru_fwd_seq_fc); 0: after it
   int fc_tail = 1;       // one-layer H = 512, V = 256: the fused FC head (fc_xent's 32-token blocks) as the tail
                          // of the persistent forward launch (gru_fwd_seq_tail); 0: its own launch after it
+  int bwd_tail = 1;      // one-layer H = 512, V = 256 single-GPU one-graph step: the dP row-block partials, the
+                         // loss partials and the step counter summed as the tail of the persistent backward
+                         // launch (gru_bwd_seq_tail); 0: the reduce_multi launch after it
   int big_dy = 1;        // top layer on the persistent large-H backward, V = 256: dy = dl · W_fc inside it
                          // (SeqBwdArgs::dl) instead of the dH GEMM + an fp32 dy in memory
   int ld_pad = -1;       // padding of the dGh^T / dGi^T / dl^T leading dimension: -1 = 64 elements where
@@ -246,6 +249,21 @@ struct SeqBwdArgs {
 };
 bool gru_bwd_seq_supported(int H, int Bp, bool fuse_w, bool fuse_p);
 void gru_bwd_seq(const SeqBwdArgs& a, hipStream_t s);
+// The fused dW_hh / dP backward (H = 512, V = 256) with the sum of its dP row-block partials as its tail:
+// the step loop untouched; after it the dP partials leave write-through, workgroup (row block rbk, unit
+// tile ut) signals epoch T + 1, waits for the Bp/32 workgroups of its unit tile and sums rows
+// [rbk * V / nrb, (rbk + 1) * V / nrb) x its 48 columns over the slabs in reduce_multi's order into the
+// bf16 GEMM operands dP_bf / dPT_bf; workgroup 0 also sums the loss partials and bumps the step counter
+// (everything the single-GPU step's reduce_multi launch did).  Needs V % nrb == 0, (V / nrb) % 8 == 0.
+struct BwdTailArgs {
+  u16* dP_bf = nullptr;            // [V][3H] bf16 sum of the slabs
+  u16* dPT_bf = nullptr;           // [3H][V] its transpose
+  const float* loss_part = nullptr; int nloss = 0;   // the forward's per-32-row loss partials
+  float* loss = nullptr;           // their sum
+  int* step = nullptr;             // optimiser step counter, incremented once
+};
+bool gru_bwd_seq_tail_supported(int H, int Bp, int V);
+void gru_bwd_seq_tail(const SeqBwdArgs& a, const BwdTailArgs& t, hipStream_t s);
 // The same backward on 16-row row blocks x 32 units (gru_seq16.hip): 8 XCD-local row blocks at
 // Bp = 128, half the streamed dGh per workgroup; H = 1024, no fused dW_hh.  Bias / dP partials are
 // per 16-row block: dbhh_part / dbih_part [Bp/16][3H], dP_part [Bp/16][V][3H].

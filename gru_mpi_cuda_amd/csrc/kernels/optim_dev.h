@@ -269,6 +269,16 @@ DEV void adam_cast_unit(const OptimArgs& a, const OptCastJob& J, int t, const Ad
   }
 }
 
+// Element i of a tiny job (`splits` partials of n floats each, e.g. the loss: many one-float partials)
+// summed by one whole wave in a fixed order: lane-strided partial sums, then wave_sum.  Every lane of
+// the wave calls it with its lane index; all return the sum.  (reduce_multi_body and the persistent
+// backward's tail, gru_seq.hip bwd_dp_tail: one function, so the loss is bitwise the same in both.)
+DEV float wave_strided_sum(const float* src, int splits, long n, long i, int lane) {
+  float acc = 0.f;
+  for (int s = lane; s < splits; s += 64) acc += src[(size_t)s * n + i];
+  return wave_sum(acc);
+}
+
 // One block's share of a multi-tensor slab reduction (reduce_slabs_multi): block b of the prefix sum
 // over the jobs' block counts; tile: 16 x kRedTileP u16 of LDS for the transposed bf16 copies.  Blocks
 // past the last job do nothing.
@@ -316,9 +326,7 @@ DEV void reduce_multi_body(const SlabJobs& j, int b, u16 (*tile)[kRedTileP]) {
     if (J.n < 4) {   // tiny job (e.g. the loss: many one-float partials): one wave, fixed order
       if (threadIdx.x < 64)
         for (long i = 0; i < J.n; ++i) {
-          float acc = 0.f;
-          for (int s = threadIdx.x; s < J.splits; s += 64) acc += J.src[(size_t)s * J.n + i];
-          acc = wave_sum(acc);
+          const float acc = wave_strided_sum(J.src, J.splits, J.n, i, threadIdx.x);
           if (threadIdx.x == 0) J.dst[i] = acc;
         }
     } else {
