@@ -429,7 +429,7 @@ PYBIND11_MODULE(_C, m) {
     flat_pack_u32(Pp<float>(p), Pp<unsigned>(pack), r, lo, hi, tail, unpack, S(s));
     HIP_LAUNCH_CHECK();
   });
-  m.def("fwd_step", [](py::dict d, uintptr_t s) {
+  auto fwd_step_args = [](py::dict d) {
     FwdStepArgs a;
     a.hprev_bf = GP(const u16, d, "hprev_bf"); a.hprev_f = GP(const float, d, "hprev_f");
     a.Whh = GP(const u16, d, "Whh"); a.bhh = GP(const float, d, "bhh");
@@ -439,12 +439,12 @@ PYBIND11_MODULE(_C, m) {
     a.h_f = GP(float, d, "h_f"); a.h_bf = GP(u16, d, "h_bf"); a.hT = GP(u16, d, "hT");
     a.ldT = get<int>(d, "ldT", 0); a.colT = get<int>(d, "colT", 0);
     a.sr = GP(float, d, "sr"); a.sz = GP(float, d, "sz"); a.sn = GP(float, d, "sn"); a.sghn = GP(float, d, "sghn");
+    a.s16 = GP(u16, d, "s16");
     a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0); a.algo = get<int>(d, "algo", 0);
     if (a.Bp % 32 || a.H % 64) throw std::runtime_error("fwd_step: Bp % 32 and H % 64 required");
-    gru_fwd_step(a, S(s));
-    HIP_LAUNCH_CHECK();
-  });
-  m.def("bwd_step", [](py::dict d, uintptr_t s) {
+    return a;
+  };
+  auto bwd_step_args = [](py::dict d) {
     BwdStepArgs a;
     a.dgh_next = GP(const u16, d, "dgh_next"); a.WhhT = GP(const u16, d, "WhhT");
     a.carry_in = GP(const float, d, "carry_in"); a.dy = GP(const float, d, "dy");
@@ -459,9 +459,25 @@ PYBIND11_MODULE(_C, m) {
     a.err = GP(unsigned, d, "err");
     a.dgiT_n_only = get<int>(d, "dgiT_n_only", 0);
     if (a.Bp % 32 || a.H % 64) throw std::runtime_error("bwd_step: Bp % 32 and H % 64 required");
-    gru_bwd_step(a, S(s));
+    return a;
+  };
+  m.def("fwd_step", [fwd_step_args](py::dict d, uintptr_t s) {
+    gru_fwd_step(fwd_step_args(d), S(s));
     HIP_LAUNCH_CHECK();
   });
+  m.def("bwd_step", [bwd_step_args](py::dict d, uintptr_t s) {
+    gru_bwd_step(bwd_step_args(d), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the kernel fwd_step / bwd_step would launch for the same dict (the plan the launcher switches on)
+  auto plan_dict = [](const StepPlan& p) {
+    py::dict o;
+    o["name"] = step_kernel_name(p.kernel);
+    o["ks"] = p.ks; o["kb"] = p.kb; o["nks_i"] = p.nks_i; o["splits"] = p.splits; o["sk_map"] = p.sk_map;
+    return o;
+  };
+  m.def("fwd_step_variant", [fwd_step_args, plan_dict](py::dict d) { return plan_dict(gru_fwd_step_plan(fwd_step_args(d))); });
+  m.def("bwd_step_variant", [bwd_step_args, plan_dict](py::dict d) { return plan_dict(gru_bwd_step_plan(bwd_step_args(d))); });
   m.def("spin_delay", [](int us, uintptr_t s) { spin_delay(us, S(s)); HIP_LAUNCH_CHECK(); });
   // tests: copy an internal device buffer (Trainer::buffer) into a caller tensor
   m.def("copy_d2d", [](uintptr_t dst, uintptr_t src, size_t bytes) {
@@ -535,6 +551,8 @@ PYBIND11_MODULE(_C, m) {
       a.cnt = GP(unsigned, d, "cnt"); a.err = GP(unsigned, d, "err");
       a.dbg = GP(unsigned long long, d, "dbg"); a.allow_local = get<int>(d, "allow_local", 1);
       a.xring = get<int>(d, "xring", 0);
+      a.s16 = GP(u16, d, "s16");
+      a.zero_next = GP(unsigned, d, "zero_next"); a.zero_words = get<long>(d, "zero_words", 0);
       a.T = get<int>(d, "T", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
       if (!a.xch || !a.cnt || !a.HSb || !a.HSf || !a.Whh || !a.bhh) throw std::runtime_error("fwd_seq2: HSb/HSf/xch/cnt/Whh/bhh required");
       return a;

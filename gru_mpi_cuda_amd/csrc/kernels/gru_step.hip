@@ -209,7 +209,8 @@ __global__ void __launch_bounds__(512) gru_bwd_step_kernel(BwdStepArgs a, int nk
     const int col = rem >> 5, row = rem & 31;
     const size_t off = (size_t)(g * H + j0 + col) * a.ldT + a.colT + b0 + row;
     const u16 vh = st[(g * TUNITS + col) * TROWS + row];
-    a.dghT[off] = vh;
+    if (a.dghT) a.dghT[off] = vh;
+    if (!a.dgiT) continue;   // nullable, as in the LDS-staged kernels
     if (g == 2) a.dgiT[off] = st[(3 * TUNITS + col) * TROWS + row];
     else if (!a.dgiT_n_only) a.dgiT[off] = vh;
   }
@@ -235,21 +236,43 @@ static bool use_lds(int algo, int H, int Bp, bool fused, int Kin, int ldT, int c
   return ok && gru_step_picks_lds(algo, H, Bp);
 }
 
-void gru_fwd_step(const FwdStepArgs& a, hipStream_t s) {
-  if (use_lds(a.algo, a.H, a.Bp, a.x_bf != nullptr, a.Kin, a.ldT, a.colT)) { gru_fwd_step_lds(a, s); return; }
+const char* step_kernel_name(int kernel) {
+  switch (kernel) {
+    case kStepReg: return "reg";
+    case kStepLds128: return "lds128";
+    case kStepLds64: return "lds64";
+    case kStepBig: return "big";
+    case kStepLds8: return "lds8";
+    case kStepSk2: return "sk2";
+    case kStepSk4: return "sk4";
+  }
+  return "?";
+}
+
+StepPlan gru_fwd_step_plan(const FwdStepArgs& a) {
+  if (use_lds(a.algo, a.H, a.Bp, a.x_bf != nullptr, a.Kin, a.ldT, a.colT)) return gru_fwd_step_lds_plan(a);
   if (a.s16) throw std::runtime_error("gru_fwd_step: packed bf16 saves need the LDS-staged step kernels");
+  StepPlan p;
   const int nks = a.H / 32;
-  int ks, kb;
-  pick_split(nks, ks, kb);
-  const bool fuse = a.x_bf != nullptr;
-  int nks_i = 0;
-  if (fuse) {
+  pick_split(nks, p.ks, p.kb);
+  if (a.x_bf != nullptr) {
     const int nki = a.Kin / 32;
+    int ks = p.ks, kb = p.kb;
     // both K ranges must split over the same wave count
     while (ks > 1 && (nki % ks != 0 || (nki / ks) % kb != 0 || (nks / ks) % kb != 0)) ks >>= 1;
     while (kb > 1 && ((nks / ks) % kb != 0 || (nki / ks) % kb != 0)) kb >>= 1;
-    nks_i = nki / ks;
+    p.ks = ks; p.kb = kb;
+    p.nks_i = nki / ks;
   }
+  return p;
+}
+
+void gru_fwd_step(const FwdStepArgs& a, hipStream_t s) {
+  const StepPlan p = gru_fwd_step_plan(a);
+  if (p.kernel != kStepReg) { gru_fwd_step_lds(a, s); return; }
+  const int nks = a.H / 32;
+  const int ks = p.ks, kb = p.kb, nks_i = p.nks_i;
+  const bool fuse = a.x_bf != nullptr;
   dim3 grid(a.H / TUNITS, a.Bp / TROWS);
   const int NT = fuse ? 12 : 6;
   const size_t shm = (size_t)ks * NT * 256 * 4 + TROWS * TUNITS * 2;
@@ -263,11 +286,18 @@ void gru_fwd_step(const FwdStepArgs& a, hipStream_t s) {
 #undef FWD_LAUNCH
 }
 
+StepPlan gru_bwd_step_plan(const BwdStepArgs& a) {
+  if (use_lds(a.algo, a.H, a.Bp, false, 0, a.ldT, a.colT)) return gru_bwd_step_lds_plan(a);
+  StepPlan p;
+  pick_split(3 * a.H / 32, p.ks, p.kb);
+  return p;
+}
+
 void gru_bwd_step(const BwdStepArgs& a, hipStream_t s) {
-  if (use_lds(a.algo, a.H, a.Bp, false, 0, a.ldT, a.colT)) { gru_bwd_step_lds(a, s); return; }
+  const StepPlan p = gru_bwd_step_plan(a);
+  if (p.kernel != kStepReg) { gru_bwd_step_lds(a, s); return; }
   const int nks = 3 * a.H / 32;
-  int ks, kb;
-  pick_split(nks, ks, kb);
+  const int ks = p.ks, kb = p.kb;
   dim3 grid(a.H / TUNITS, a.Bp / TROWS);
   const size_t shm = (size_t)ks * 2 * 256 * 4 + 4 * TROWS * TUNITS * 2;
   const int nk = nks / ks;

@@ -891,40 +891,67 @@ StepLdsVariants& step_lds_variants() {
 
 bool gru_step_lds_ok(int H, int Bp) { return H >= 256 && H % 64 == 0 && Bp % 128 == 0; }
 
-void gru_fwd_step_lds(const FwdStepArgs& a, hipStream_t s) {
+StepPlan gru_fwd_step_lds_plan(const FwdStepArgs& a) {
+  StepPlan p;
   // big tile: only with the fused input phase on a full round of tiles (without it, the P-table
   // gather moves behind the K loop and it measured slower: profiles/r1_generate_step_kernel_ab.json)
   if (a.x_bf && a.Kin % 64 == 0 && a.Bp % 256 == 0 && a.H % 64 == 0 && (a.H / 64) * (a.Bp / 256) >= 256) {
-    hipLaunchKernelGGL(gru_fwd_step_big_kernel<true>, dim3(a.H / 64, a.Bp / 256), dim3(512), 0, s, a);
-    return;
+    p.kernel = kStepBig;
+    return p;
   }
-  const dim3 grid(a.H / 32, a.Bp / 128), block(256);
   // grids of >= 512 128-row tiles: the 2-deep 128-row kernel, two workgroups per CU (the 64-row tile
   // there measured 74-75 -> 88 us per char at 2048 names, profiles/r2_generate_fwd64_all_ab.txt).
   // Smaller grids: the 64-row tile, two workgroups per CU, 3-deep ring (h2048 9.72 -> 9.43-9.47 ms,
   // profiles/r2_h2048_fwd64_ab.jsonl; fused input phase 55.8 -> 54.3-54.9 us per char at 1024 names,
   // r2_generate_fwd64_fused_ab.txt).  StepLdsVariants::fwd64 = 0 keeps the 128-row kernel everywhere.
-  const bool small_grid = grid.x * grid.y < 512;
-  if (small_grid && step_lds_variants().fwd64 && a.Bp % 64 == 0 && (!a.x_bf || a.Kin % 64 == 0)) {
-    if (a.x_bf) hipLaunchKernelGGL((gru_fwd_step_lds64_kernel<3, true>), dim3(a.H / 32, a.Bp / 64), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(gru_fwd_step_lds64_kernel<3>, dim3(a.H / 32, a.Bp / 64), dim3(256), 0, s, a);
-    return;
-  }
-  if (a.x_bf) hipLaunchKernelGGL((gru_fwd_step_lds_kernel<true, 2>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((gru_fwd_step_lds_kernel<false, 2>), grid, block, 0, s, a);
+  const bool small_grid = (a.H / 32) * (a.Bp / 128) < 512;
+  const bool f64 = small_grid && step_lds_variants().fwd64 && a.Bp % 64 == 0 && (!a.x_bf || a.Kin % 64 == 0);
+  p.kernel = f64 ? kStepLds64 : kStepLds128;
+  return p;
 }
-void gru_bwd_step_lds(const BwdStepArgs& a, hipStream_t s) {
+
+void gru_fwd_step_lds(const FwdStepArgs& a, hipStream_t s) {
+  switch (gru_fwd_step_lds_plan(a).kernel) {
+    case kStepBig:
+      hipLaunchKernelGGL(gru_fwd_step_big_kernel<true>, dim3(a.H / 64, a.Bp / 256), dim3(512), 0, s, a);
+      return;
+    case kStepLds64:
+      if (a.x_bf) hipLaunchKernelGGL((gru_fwd_step_lds64_kernel<3, true>), dim3(a.H / 32, a.Bp / 64), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(gru_fwd_step_lds64_kernel<3>, dim3(a.H / 32, a.Bp / 64), dim3(256), 0, s, a);
+      return;
+    default: {
+      const dim3 grid(a.H / 32, a.Bp / 128), block(256);
+      if (a.x_bf) hipLaunchKernelGGL((gru_fwd_step_lds_kernel<true, 2>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((gru_fwd_step_lds_kernel<false, 2>), grid, block, 0, s, a);
+    }
+  }
+}
+
+StepPlan gru_bwd_step_lds_plan(const BwdStepArgs& a) {
+  StepPlan p;
+  p.kernel = kStepLds8;
   if (const int S = gru_bwd_step_sk_splits(a.H, a.Bp)) {
     const int tiles = (a.H / 128) * (a.Bp / 128);
     if (a.sk_part && a.sk_cnt && a.sk_part_floats >= (long)a.H * a.Bp * S && a.sk_cnt_words >= (long)tiles * 16) {
-      BwdStepArgs b = a;
+      p.kernel = S == 4 ? kStepSk4 : kStepSk2;
+      p.splits = S;
       // splits across XCDs where whole unit-tile groups fit per XCD (h2048 9.46-9.47 vs 9.49 ms,
       // profiles/r4_h2048_skmap.jsonl), else the splits of a tile 8 blocks apart
-      b.sk_map = (a.H / 128) % (8 / S) == 0 ? 1 : 0;
-      if (S == 4) hipLaunchKernelGGL((gru_bwd_step_sk_kernel<4, SKNS, true>), dim3(tiles * 4), dim3(512), 0, s, b);
-      else hipLaunchKernelGGL(gru_bwd_step_sk_kernel<2>, dim3(tiles * 2), dim3(512), 0, s, b);
-      return;
+      p.sk_map = (a.H / 128) % (8 / S) == 0 ? 1 : 0;
     }
+  }
+  return p;
+}
+
+void gru_bwd_step_lds(const BwdStepArgs& a, hipStream_t s) {
+  const StepPlan p = gru_bwd_step_lds_plan(a);
+  if (p.kernel != kStepLds8) {
+    const int tiles = (a.H / 128) * (a.Bp / 128);
+    BwdStepArgs b = a;
+    b.sk_map = p.sk_map;
+    if (p.splits == 4) hipLaunchKernelGGL((gru_bwd_step_sk_kernel<4, SKNS, true>), dim3(tiles * 4), dim3(512), 0, s, b);
+    else hipLaunchKernelGGL(gru_bwd_step_sk_kernel<2>, dim3(tiles * 2), dim3(512), 0, s, b);
+    return;
   }
   hipLaunchKernelGGL(gru_bwd_step_lds8_kernel, dim3(a.H / 64, a.Bp / 64), dim3(512), 0, s, a);
 }

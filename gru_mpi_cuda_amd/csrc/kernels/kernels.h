@@ -126,6 +126,20 @@ bool gru_step_lds_ok(int H, int Bp);
 bool gru_step_picks_lds(int algo, int H, int Bp);
 void gru_fwd_step_lds(const FwdStepArgs& a, hipStream_t s);
 void gru_bwd_step_lds(const BwdStepArgs& a, hipStream_t s);
+// The kernel a step launcher takes for its arguments.  The launchers switch on these plans and the
+// bindings report them (fwd_step_variant / bwd_step_variant), so what a test reads is what ran.
+// They throw what the launchers throw for an unsupported request.
+//   forward : kStepReg   gru_fwd_step_kernel<kb, fused> on ks waves (nks_i: input k-steps per wave)
+//             kStepLds128 / kStepLds64 / kStepBig: the 128-row, 64-row and 256-row LDS tiles
+//   backward: kStepReg   gru_bwd_step_kernel<kb> on ks waves
+//             kStepLds8  the 64 x 64 LDS tile;  kStepSk2 / kStepSk4: split-K with `splits`, `sk_map`
+enum StepKernel { kStepReg = 0, kStepLds128, kStepLds64, kStepBig, kStepLds8, kStepSk2, kStepSk4 };
+struct StepPlan { int kernel = kStepReg; int ks = 0, kb = 0, nks_i = 0; int splits = 0, sk_map = 0; };
+const char* step_kernel_name(int kernel);
+StepPlan gru_fwd_step_plan(const FwdStepArgs& a);
+StepPlan gru_bwd_step_plan(const BwdStepArgs& a);
+StepPlan gru_fwd_step_lds_plan(const FwdStepArgs& a);   // the LDS launchers' own choice
+StepPlan gru_bwd_step_lds_plan(const BwdStepArgs& a);
 
 // ------------------------------------------------------------------ persistent sequence kernels
 // One launch per layer runs all T steps (gru_seq.hip).  Requires 512-thread co-residency of

@@ -90,9 +90,12 @@ def deviation(got: torch.Tensor, ref: torch.Tensor, rtol: float = 0.0) -> float:
     return max(float(d.max()), 0.0) if d.numel() else 0.0
 
 
-def mismatch(got: torch.Tensor, ref: torch.Tensor, family: str) -> Optional[str]:
+def mismatch(got: torch.Tensor, ref: torch.Tensor, family: str, ATOL=None, RTOL=None) -> Optional[str]:
     """None when |got - ref| <= ATOL[family] + RTOL[family] |ref| everywhere, else a description
-    of the worst element.  A NaN in ``got`` is a mismatch."""
+    of the worst element.  A NaN in ``got`` is a mismatch.  ATOL / RTOL: another module's tables
+    (step_ref's families) instead of the ones above."""
+    ATOL = globals()["ATOL"] if ATOL is None else ATOL
+    RTOL = globals()["RTOL"] if RTOL is None else RTOL
     g, r = got.to(torch.float64), ref.to(torch.float64)
     if g.shape != r.shape:
         return f"shape {tuple(g.shape)} vs reference {tuple(r.shape)}"
@@ -107,8 +110,8 @@ def mismatch(got: torch.Tensor, ref: torch.Tensor, family: str) -> Optional[str]
             f"{RTOL[family]:.3g}); worst at {idx}: got {float(g[idx]):.6g}, reference {float(r[idx]):.6g}")
 
 
-def assert_close(got: torch.Tensor, ref: torch.Tensor, family: str, what: str = "") -> None:
-    m = mismatch(got, ref, family)
+def assert_close(got: torch.Tensor, ref: torch.Tensor, family: str, what: str = "", ATOL=None, RTOL=None) -> None:
+    m = mismatch(got, ref, family, ATOL, RTOL)
     assert m is None, f"{what}: {m}"
 
 
