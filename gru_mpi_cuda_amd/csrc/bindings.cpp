@@ -229,6 +229,8 @@ PYBIND11_MODULE(_C, m) {
       .def("set_persist_max", &Generator::set_persist_max)
       .def("set_persist_dbg", [](Generator& g, uintptr_t p) { g.set_persist_dbg(reinterpret_cast<unsigned long long*>(p)); })
       .def("uses_persist", &Generator::uses_persist)
+      .def("uses_persist_ctl", &Generator::uses_persist_ctl)
+      .def("set_persist_ctl_max", &Generator::set_persist_ctl_max)
       .def("set_global_names", &Generator::set_global_names)
       .def("inject_persist_error", &Generator::inject_persist_error)
       .def("dump_graph", &Generator::dump_graph);
@@ -746,6 +748,7 @@ PYBIND11_MODULE(_C, m) {
   // launch with its workspace (layout: kernels.h, GenPersistArgs::ws), the fp32 gates, the batch
   // reset and the scorer's two kernels
   m.def("gen_persist_supported", &gen_persist_supported);
+  m.def("gen_persist_ctl_supported", &gen_persist_ctl_supported);
   m.def("gen_persist_ws_floats", &gen_persist_ws_floats);
   m.def("gen_persist_sync_words", &gen_persist_sync_words);
   m.def("gen_persist_fill_ws", [](uintptr_t ws, int H, int L, int V, int ML, uintptr_t s) {
@@ -768,6 +771,10 @@ PYBIND11_MODULE(_C, m) {
     a.Wfc = GP(const float, d, "Wfc"); a.bfc = GP(const float, d, "bfc"); a.P = GP(const float, d, "P");
     a.rf = GP(const float, d, "rf"); a.out = GP(unsigned char, d, "out"); a.probs = GP(float, d, "probs");
     a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
+    // sampling controls (all five or none: gen_persist_f32 throws on a mixture)
+    a.inv_temp = GP(const float, d, "inv_temp"); a.top_k = GP(const int, d, "top_k");
+    a.top_p = GP(const float, d, "top_p"); a.plen = GP(const int, d, "plen");
+    a.prefix = GP(const unsigned char, d, "prefix");
     gen_persist_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });

@@ -61,6 +61,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   if (const char* sa = std::getenv("GK_STEP_ALGO")) step_algo_ = std::atoi(sa);   // 0 auto, 1 reg, 2 LDS
   const char* gp = std::getenv("GK_GEN_PERSIST");
   if (gp && gp[0] == '0') persist_ = false;
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_CTL_MAX")) persist_ctl_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -72,6 +73,11 @@ bool Generator::uses_persist(int n) const {
   // then picks the same arithmetic on every world size.  fp32 mode: both paths are fp32.
   if (!d_.fp32 && std::max(n, global_n_) > persist_max_bf16_) return false;
   return persist_ && n <= persist_max_ && gen_persist_supported(d_.H, d_.L, d_.V, n, d_.max_len);
+}
+
+bool Generator::uses_persist_ctl(int n) const {
+  // both paths are fp32-class here (generate_ctl raises in the bf16 mode), so the count alone decides
+  return persist_ && d_.fp32 && n <= persist_ctl_max_ && gen_persist_ctl_supported(d_.H, d_.L, d_.V, n, d_.max_len);
 }
 
 Generator::~Generator() {
@@ -271,6 +277,53 @@ void Generator::record_steps_f32(int n, hipStream_t s, bool ctl) {
   HIP_LAUNCH_CHECK();
 }
 
+bool Generator::persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s) {
+  const int ML = d_.max_len;
+  GenPersistArgs a;
+  for (int l = 0; l < d_.L; ++l) {
+    const std::string k = std::to_string(l);
+    a.Whh[l] = P("weight_hh_l" + k); a.bhh[l] = P("bias_hh_l" + k);
+    if (l > 0) { a.Wih[l] = P("weight_ih_l" + k); a.bih[l] = P("bias_ih_l" + k); }
+  }
+  a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_; a.probs = probe_;
+  a.rf = rf; a.out = out;
+  if (c) { a.inv_temp = c->inv_temp; a.top_k = c->top_k; a.top_p = c->top_p; a.plen = c->plen; a.prefix = c->prefix; }
+  a.ws = pws_; a.sync = psync_; a.err = err_; a.dbg = persist_dbg_;
+  if (ppar_ < 0) {   // first launch: both sets' tagged slots -> kEmpty; later launches refill in-kernel
+    gen_persist_fill_ws(pws_, d_.H, d_.L, d_.V, ML, s);
+    ppar_ = 0;
+  }
+  a.par = ppar_;
+  ppar_ ^= 1;
+  a.N = n; a.H = d_.H; a.L = d_.L; a.V = d_.V; a.ML = ML; a.sos = d_.sos; a.eos = d_.eos;
+  if (inject_) {   // test hook: OR the spin-limit bit into the word (earlier batches' bits stay)
+    unsigned cur = 0;
+    HIP_CHECK(hipMemcpyAsync(&cur, err_, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    cur |= 32u;
+    HIP_CHECK(hipMemcpyAsync(err_, &cur, 4, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    inject_ = false;
+  }
+  gen_persist_f32(a, s);
+  // small batch, latency-bound launch: check its error word now.  A spin timeout means the
+  // workgroups were not co-resident (something else held CUs): the batch's output is garbage,
+  // so say so, stop using the persistent path and regenerate the batch on the per-char graph.
+  // (pinned host word: 138 vs 146-150 us per 1-name call against a pageable one; skipping the
+  // next call's memset after a clean call another ~2 us: profiles/r5_gen_err_readback_ab.txt)
+  HIP_CHECK(hipMemcpyAsync(err_pin_, err_, 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  const unsigned e = *reinterpret_cast<volatile unsigned*>(err_pin_);
+  if (e == 0 && last_batch) err_clean_ = true;   // the call ends here, word still 0
+  if (!(e & 32u)) return true;
+  std::fprintf(stderr, "[generator] persistent launch hit its spin limit (error word %u): "
+                       "disabling it, regenerating %d names on the per-char graph\n", e, n);
+  persist_ = false;
+  const unsigned keep = e & ~32u;   // the other bits stay (earlier batches' errors)
+  HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
+  return false;
+}
+
 void Generator::generate(const float* rf, int N, unsigned char* out, hipStream_t s) {
   GK_TRACE("gk.generate");
   const int ML = d_.max_len;
@@ -280,55 +333,11 @@ void Generator::generate(const float* rf, int N, unsigned char* out, hipStream_t
   err_clean_ = false;
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
-    bool persist_done = false;
-    if (uses_persist(n)) {   // one launch for the whole batch: no graph needed
-      GenPersistArgs a;
-      for (int l = 0; l < d_.L; ++l) {
-        const std::string k = std::to_string(l);
-        a.Whh[l] = P("weight_hh_l" + k); a.bhh[l] = P("bias_hh_l" + k);
-        if (l > 0) { a.Wih[l] = P("weight_ih_l" + k); a.bih[l] = P("bias_ih_l" + k); }
-      }
-      // the caller's uniforms and output rows directly (no staging copies: two fewer stream
-      // operations per call on the latency-bound small-batch path)
-      a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_; a.probs = probe_;
-      a.rf = rf + (size_t)start * ML; a.out = out + (size_t)start * (ML + 1);
-      a.ws = pws_; a.sync = psync_; a.err = err_; a.dbg = persist_dbg_;
-      if (ppar_ < 0) {   // first launch: both sets' tagged slots -> kEmpty; later launches refill in-kernel
-        gen_persist_fill_ws(pws_, d_.H, d_.L, d_.V, ML, s);
-        ppar_ = 0;
-      }
-      a.par = ppar_;
-      ppar_ ^= 1;
-      a.N = n; a.H = d_.H; a.L = d_.L; a.V = d_.V; a.ML = ML; a.sos = d_.sos; a.eos = d_.eos;
-      if (inject_) {   // test hook: OR the spin-limit bit into the word (earlier batches' bits stay)
-        unsigned cur = 0;
-        HIP_CHECK(hipMemcpyAsync(&cur, err_, 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        cur |= 32u;
-        HIP_CHECK(hipMemcpyAsync(err_, &cur, 4, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        inject_ = false;
-      }
-      gen_persist_f32(a, s);
-      // small batch, latency-bound launch: check its error word now.  A spin timeout means the
-      // workgroups were not co-resident (something else held CUs): the batch's output is garbage,
-      // so say so, stop using the persistent path and regenerate the batch on the per-char graph.
-      // (pinned host word: 138 vs 146-150 us per 1-name call against a pageable one; skipping the
-      // next call's memset after a clean call another ~2 us: profiles/r5_gen_err_readback_ab.txt)
-      HIP_CHECK(hipMemcpyAsync(err_pin_, err_, 4, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      const unsigned e = *reinterpret_cast<volatile unsigned*>(err_pin_);
-      if (e == 0 && start + n >= N) err_clean_ = true;   // the call ends here, word still 0
-      persist_done = !(e & 32u);
-      if (!persist_done) {
-        std::fprintf(stderr, "[generator] persistent launch hit its spin limit (error word %u): "
-                             "disabling it, regenerating %d names on the per-char graph\n", e, n);
-        persist_ = false;
-        const unsigned keep = e & ~32u;   // the other bits stay (earlier batches' errors)
-        HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
-      }
-    }
-    if (persist_done) continue;   // rows already in `out`
+    // one launch for the whole batch, no graph needed: the caller's uniforms and output rows directly
+    // (no staging copies: two fewer stream operations per call on the latency-bound small-batch path)
+    if (uses_persist(n) &&
+        persist_launch(rf + (size_t)start * ML, n, nullptr, out + (size_t)start * (ML + 1), start + n >= N, s))
+      continue;   // rows already in `out`
     HIP_CHECK(hipMemcpyAsync(rf_, rf + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     if (use_graph_) {
       auto& g = graphs_[n];
@@ -367,11 +376,17 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
     throw std::runtime_error("Generator::generate_ctl: every control array is required");
   if (N <= 0) return;
   const int ML = d_.max_len;
-  ctl_alloc();   // first call: allocates (and synchronises) before anything is captured
-  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
+  if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
+    if (uses_persist_ctl(n)) {   // one controlled launch on the caller's arrays at this batch's rows
+      Ctl b;
+      b.inv_temp = c.inv_temp + start; b.top_k = c.top_k + start; b.top_p = c.top_p + start; b.plen = c.plen + start;
+      b.prefix = c.prefix + (size_t)start * ML;
+      if (persist_launch(rf + (size_t)start * ML, n, &b, out + (size_t)start * (ML + 1), start + n >= N, s)) continue;
+    }
+    ctl_alloc();   // first batch on this path: allocates (and synchronises) before anything is captured
     HIP_CHECK(hipMemcpyAsync(rf_, rf + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     // this batch's slice of every control array: the graph reads rows 0 .. n - 1 of the buffers
     HIP_CHECK(hipMemcpyAsync(cinv_, c.inv_temp + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));

@@ -33,16 +33,23 @@ class Generator {
   // rf: device [N][max_len] uniforms of THIS rank's names; out: device [N][max_len+1]
   void generate(const float* rf, int N, unsigned char* out, hipStream_t s);
   // generate() with per-name sampling controls (docs/DESIGN.md §4b; device arrays of N entries:
-  // inv_temp = 1 / T or 0 for greedy, top_k, top_p, plen, prefix [N][max_len]).  Always the per-char
-  // fp32 / bf16x3 graph with sample_ctl_f32 as its sampler node, never the persistent launch; the
-  // bf16 mode raises.  The graph reads the controls from buffers of an arena of their own (allocated on
-  // the first call) into which each batch's slice is copied, so one recording per n serves every value.
+  // inv_temp = 1 / T or 0 for greedy, top_k, top_p, plen, prefix [N][max_len]).  The bf16 mode raises.
+  // Per batch of n names: uses_persist_ctl(n) -> ONE controlled persistent launch that reads the
+  // caller's uniforms, rows and controls in place (no staging, no arena); else the per-char fp32 /
+  // bf16x3 graph with sample_ctl_f32 as its sampler node.  That graph reads the controls from buffers
+  // of an arena of their own (allocated by the first batch that takes it) into which each batch's
+  // slice is copied, so one recording per n serves every value.
   struct Ctl {
     const float* inv_temp = nullptr; const int* top_k = nullptr; const float* top_p = nullptr;
     const int* plen = nullptr; const unsigned char* prefix = nullptr;
   };
   void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
-  size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until the first generate_ctl()
+  size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until a batch takes the per-char controlled graph
+  // generate_ctl() batches of n names run as one controlled persistent launch (exact fp32, as the plain
+  // one): up to GK_GEN_PERSIST_CTL_MAX names (default and at most 64), where a controlled variant
+  // exists (gen_persist_ctl_supported); off with GK_GEN_PERSIST=0 or set_persist(false)
+  bool uses_persist_ctl(int n) const;
+  void set_persist_ctl_max(int n) { persist_ctl_max_ = n; }
   // Teacher-forced scoring of N output rows (device [N][max_len+1], the generate() format): per token
   // log softmax(logits)[target] and the target's rank, per name their sum and the token count (all
   // device pointers: tok_logp / rank [N][max_len], name_logp / n_tok [N]).  Always the exact-fp32
@@ -86,6 +93,10 @@ class Generator {
   void reset_batch(int Bp, bool bf16, hipStream_t s);
   void score_alloc();
   void ctl_alloc();
+  // one persistent launch for n names (c: the controlled one, its arrays already at this batch's rows)
+  // and its error-word read-back.  false: the launch hit its spin limit -- the persistent path is now
+  // off, the bit is cleared and the caller regenerates the batch on its per-char graph
+  bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
   void record_score(int Bp, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
@@ -118,6 +129,7 @@ class Generator {
   bool inject_ = false;
   int global_n_ = 0;            // set_global_names
   int persist_max_ = 64;        // names per batch up to which the persistent launch is used
+  int persist_ctl_max_ = 64;    // ... with sampling controls (GK_GEN_PERSIST_CTL_MAX)
   int persist_max_bf16_ = 40;   // ... in the bf16 mode (it runs exact fp32, faster up to ~40 names:
                                 // profiles/r5_gen_persist_vs_bf16_graph_final.jsonl)
   unsigned long long* persist_dbg_ = nullptr;

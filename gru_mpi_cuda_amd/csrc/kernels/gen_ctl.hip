@@ -14,6 +14,10 @@
 //     of the non-negative q (30 steps: q <= 1), a fixed-order wave sum per probe.
 // With nothing filtered every statistic is formed by the operations of softmax_sample_wave in its
 // order, so neutral controls give the plain sampler's bytes.
+//
+// The persistent generator's controlled variants carry a second copy of this rule, ctl_sample_wave
+// (gen_sample_ctl.h), written for a kernel with no registers to spare: a change to one belongs in
+// the other (tests/test_sampling_ctl_gpu.py holds this one, tests/test_gen_persist_ctl_gpu.py that).
 #include "kernels.h"
 #include "common.h"
 #include "gen_sample.h"

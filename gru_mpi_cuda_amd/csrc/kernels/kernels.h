@@ -427,6 +427,14 @@ void gen_reset(const GenResetArgs& a, hipStream_t s);
 // layer 0 whether or not the name has ended, so the states of an ended name follow its samples.
 // With probs == nullptr the launch stops before the first char t >= 1 at which every name has ended
 // (T = t); with probs set it runs all ML chars and writes rows n < N of the last char's softmax.
+// Sampling controls (inv_temp, top_k, top_p, plen, prefix: all five or none; a mixture throws): char
+// t of name n follows docs/DESIGN.md §4b with row n of each array, as sample_ctl_f32 does on the
+// per-char graph.  A forced char (t < plen[n]) is prefix[n][t]: its uniform is ignored, and it is
+// written to the row and fed back like a sampled one (it can be the EOS byte only if the caller put
+// it there); the launch still waits for and reads that char's logits, so the workspace, `sync` and
+// the hand-offs are those of the plain launch.  A prefix byte >= V ORs 16 into err[0] (err[1] = the
+// byte, err[2] = the name) and is taken as 0.  probs is the renormalised filtered distribution, one-hot
+// for a forced or greedy last char.  Neutral controls (1, 0, 1, plen 0) give the plain launch's bytes.
 struct GenPersistArgs {
   const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
   const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
@@ -441,8 +449,18 @@ struct GenPersistArgs {
   unsigned* err = nullptr;         // bit 32: a cross-workgroup wait hit its spin limit
   unsigned long long* dbg = nullptr;   // diagnostic (nullable): [2 wgs][ML + 1][16] s_memrealtime stamps
   int N = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+  // sampling controls, row n = name n of this launch (the arrays of SampleCtlArgs): all null, or all set
+  const float* inv_temp = nullptr;         // [N]  1 / T, 0: greedy
+  const int* top_k = nullptr;              // [N]
+  const float* top_p = nullptr;            // [N]
+  const int* plen = nullptr;               // [N]  forced chars of the name, <= ML
+  const unsigned char* prefix = nullptr;   // [N][ML]
 };
 bool gen_persist_supported(int H, int L, int V, int N, int ML);
+// ... and a controlled variant exists for the shape (each has scratch 0 and two waves per SIMD:
+// gen_persist_ctl.hip); false: the per-char controlled graph is the path
+bool gen_persist_ctl_supported(int H, int L, int V, int N, int ML);
+void gen_persist_ctl_launch(const GenPersistArgs& a, hipStream_t s);   // (gen_persist_f32 dispatches here)
 long gen_persist_ws_floats(int H, int L, int V, int ML);
 void gen_persist_fill_ws(float* ws, int H, int L, int V, int ML, hipStream_t s);   // both sets -> kEmpty
 long gen_persist_sync_words(int L);

@@ -79,8 +79,9 @@ class HipGenerator:
                         prefix=None) -> torch.Tensor:
         """``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (scalars or one value per name; semantics:
         cpu_ref.make_controls, docs/DESIGN.md §4b): any that is not None -- a neutral value too -- takes
-        the controlled per-char graph (fp32 / bf16x3 only; never the persistent launch).  Bad values
-        raise ValueError before anything is launched."""
+        the controlled path (fp32 / bf16x3 only): per batch one controlled persistent launch where
+        ``g.uses_persist_ctl(batch)`` says so (small batches), else the controlled per-char graph.  Bad
+        values raise ValueError before anything is launched."""
         ML = self.cfg.max_len
         ctl = None
         if any(v is not None for v in (temperature, top_k, top_p, prefix)):
