@@ -4,6 +4,7 @@
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --seed 1
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --prefix Mar --temperature 0.8 --top-k 40 --top-p 0.95
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt
+    python -m gru_mpi_cuda_amd.cli beam     --ckpt out/model.bin --width 5 --prefix Mar
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
 
@@ -297,6 +298,41 @@ def cmd_score(args) -> int:
     return 0
 
 
+def cmd_beam(args) -> int:
+    """The `width` most probable names per prefix: one `prefix<TAB>rank<TAB>name<TAB>logp` line per beam
+    (rank from 0, dead slots left out)."""
+    import torch
+    from .engine import generator as G
+    from .models import cpu_ref
+    from .utils import ckpt
+    fmt = args.fmt
+    if fmt == "auto":
+        fmt = "gen" if os.path.exists(args.ckpt + ".json") else "ref"
+    cfg, params = ckpt.load(args.ckpt, _cfg_from(args) if fmt == "ref" else None, fmt)
+    over = {k: getattr(args, k) for k in ("max_len", "sos", "eos") if getattr(args, k) is not None}
+    cfg = cfg.replace(**over)
+    if args.prefix_file:
+        prefixes = [b.decode("latin-1") for b in _read_names(args.prefix_file)]
+    else:
+        prefixes = [args.prefix or ""]
+    if args.cpu or not torch.cuda.is_available():
+        res = cpu_ref.beam_search({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width)
+    else:
+        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)))
+        res = gen.beam_search(prefixes, args.width)
+    lines = []
+    for pre, names, lps in zip(prefixes, res.names(), res.logp):
+        for k, nm in enumerate(names):
+            lines.append(f"{_escape(pre)}\t{k}\t{_escape(nm)}\t{float(lps[k]):.6f}")
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    else:
+        sys.stdout.write(text)
+    return 0
+
+
 class _Evaluator:
     """Held-out evaluation for `train --eval-data`: the file is read once; every call scores the
     trainer's current weights on all of it (each rank the whole file: no collective of its own)."""
@@ -387,6 +423,16 @@ def main(argv=None) -> int:
     g.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(g)
     g.set_defaults(seed=0)
+    bm = sub.add_parser("beam", help="beam search: the most probable names per prefix")
+    bm.add_argument("--ckpt", required=True)
+    bm.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")
+    bm.add_argument("--width", type=int, default=4, help="beams per prefix, 1 .. min(32, vocab)")
+    bm.add_argument("--prefix", default=None, help="the names start with these chars (default: the empty prefix)")
+    bm.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
+    bm.add_argument("--out", default=None, help="prefix, rank, name and log-prob per line, tab-separated")
+    bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
+    bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
+    _add_model_args(bm)
     sub.add_parser("info", help="device / build info")
     b = sub.add_parser("bench", help="run bench.py", add_help=False)
     args, rest = ap.parse_known_args(argv)
@@ -397,7 +443,7 @@ def main(argv=None) -> int:
         return bench.main()
     if rest:
         ap.error(f"unrecognized arguments: {rest}")
-    return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "info": cmd_info}[args.cmd](args)
+    return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "beam": cmd_beam, "info": cmd_info}[args.cmd](args)
 
 
 if __name__ == "__main__":

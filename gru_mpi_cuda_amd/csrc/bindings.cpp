@@ -222,6 +222,13 @@ PYBIND11_MODULE(_C, m) {
                 Pp<int>(n_tok), S(s));
       })
       .def("score_workspace_bytes", &Generator::score_workspace_bytes)
+      .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
+                      uintptr_t n_tok, uintptr_t n_beams, uintptr_t s) {
+        g.beam(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, Pp<unsigned char>(rows), Pp<float>(logp),
+               Pp<int>(n_tok), Pp<int>(n_beams), S(s));
+      })
+      .def("beam_workspace_bytes", &Generator::beam_workspace_bytes)
+      .def("beam_graphs", &Generator::beam_graphs)
       .def("set_use_graph", &Generator::set_use_graph)
       .def("read_error", &Generator::read_error)
       .def("set_probe", [](Generator& g, uintptr_t p) { g.set_probe(Pp<float>(p)); })
@@ -840,6 +847,47 @@ PYBIND11_MODULE(_C, m) {
     if (!a.logits || !a.tgt || !a.ntok || !a.tok_logp || !a.rank || !a.name_logp || !a.ntok_out)
       throw std::runtime_error("score_logprob: logits, tgt, ntok, tok_logp, rank, name_logp, ntok_out required");
     score_logprob_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the beam search's kernels on caller-owned buffers (tests/test_beam_gpu.py)
+  m.def("beam_select", [](py::dict d, uintptr_t s) {
+    BeamSelectArgs a;
+    a.logits = GP(const float, d, "logits"); a.splits = get<int>(d, "splits", 1); a.slab = get<long>(d, "slab", 0);
+    a.bias = GP(const float, d, "bias"); a.score_in = GP(const float, d, "score_in"); a.state_in = GP(const int, d, "state_in");
+    a.plen = GP(const int, d, "plen"); a.prefix = GP(const unsigned char, d, "prefix");
+    a.score_out = GP(float, d, "score_out"); a.parent = GP(int, d, "parent"); a.chr = GP(int, d, "chr");
+    a.state_out = GP(int, d, "state_out"); a.next_id = GP(int, d, "next_id");
+    a.lp = GP(float, d, "lp"); a.sel = GP(int, d, "sel"); a.err = GP(unsigned, d, "err");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0);
+    a.max_len = get<int>(d, "max_len", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    beam_select_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("beam_reorder", [](py::dict d, uintptr_t s) {
+    BeamReorderArgs a;
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.L = get<int>(d, "L", 0); a.H = get<int>(d, "H", 0);
+    a.max_len = get<int>(d, "max_len", 0);
+    const auto hs = get<std::vector<uintptr_t>>(d, "h_src", {}), hd = get<std::vector<uintptr_t>>(d, "h_dst", {});
+    if (a.L < 1 || a.L > 4 || (int)hs.size() != a.L || (int)hd.size() != a.L)
+      throw std::runtime_error("beam_reorder: 1 <= L <= 4, L h_src and L h_dst pointers");
+    for (int l = 0; l < a.L; ++l) { a.h_src[l] = Pp<const float>(hs[l]); a.h_dst[l] = Pp<float>(hd[l]); }
+    a.parent = GP(const int, d, "parent"); a.chr = GP(const int, d, "chr"); a.next_id = GP(const int, d, "next_id");
+    a.rows_src = GP(const unsigned char, d, "rows_src"); a.rows_dst = GP(unsigned char, d, "rows_dst");
+    a.len_src = GP(const int, d, "len_src"); a.len_dst = GP(int, d, "len_dst");
+    a.ids = GP(int, d, "ids"); a.n_beams = GP(int, d, "n_beams");
+    beam_reorder(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("beam_reset", [](py::dict d, uintptr_t s) {
+    BeamResetArgs a;
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.L = get<int>(d, "L", 0); a.Bp = get<int>(d, "Bp", 0);
+    a.H = get<int>(d, "H", 0); a.max_len = get<int>(d, "max_len", 0); a.sos = get<int>(d, "sos", 0);
+    const auto h = get<std::vector<uintptr_t>>(d, "h", {});
+    if (a.L < 1 || a.L > 4 || (int)h.size() != a.L) throw std::runtime_error("beam_reset: 1 <= L <= 4 and L h pointers");
+    for (int l = 0; l < a.L; ++l) a.h[l] = Pp<float>(h[l]);
+    a.ids = GP(int, d, "ids"); a.score = GP(float, d, "score"); a.state = GP(int, d, "state"); a.len = GP(int, d, "len");
+    a.rows = GP(unsigned char, d, "rows");
+    beam_reset(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("reduce_slabs", [](uintptr_t src, int splits, long n, uintptr_t dst, uintptr_t s) {

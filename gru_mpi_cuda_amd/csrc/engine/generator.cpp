@@ -84,6 +84,7 @@ Generator::~Generator() {
   graphs_.clear();
   sgraphs_.clear();
   cgraphs_.clear();
+  bgraphs_.clear();
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
 }
@@ -516,6 +517,133 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
     HIP_CHECK(hipMemcpyAsync(rank + (size_t)start * ML, srank_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(name_logp + start, sname_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + start, sntok_out_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ------------------------------------------------------------------------------ beam search
+// Buffers of the beam loop, sized for Bmax_ rows: a generator that never searches never allocates them.
+void Generator::beam_alloc() {
+  if (bready_) return;
+  const size_t V = d_.V, H = d_.H, ML = d_.max_len, B = Bmax_;
+  const size_t slab_rows = std::max<size_t>(B, kF32SlabRows);
+  std::vector<size_t> oA, oB;
+  for (int l = 0; l < d_.L; ++l) { oA.push_back(barena_.reserve(B * H * 4)); oB.push_back(barena_.reserve(B * H * 4)); }
+  const size_t ogh = barena_.reserve(slab_rows * 3 * H * 4);
+  const size_t ogi = d_.L > 1 ? barena_.reserve(slab_rows * 3 * H * 4) : 0;
+  const size_t olg = barena_.reserve(slab_rows * V * 4);
+  const size_t oids = barena_.reserve(B * 4);
+  size_t osc[2], ost[2], oln[2], orw[2];
+  for (int i = 0; i < 2; ++i) {
+    osc[i] = barena_.reserve(B * 4); ost[i] = barena_.reserve(B * 4); oln[i] = barena_.reserve(B * 4);
+    orw[i] = barena_.reserve(B * (ML + 1));
+  }
+  const size_t opa = barena_.reserve(B * 4), och = barena_.reserve(B * 4), onx = barena_.reserve(B * 4);
+  const size_t onb = barena_.reserve(B * 4), opl = barena_.reserve(B * 4), opre = barena_.reserve(B * ML);
+  barena_.commit();
+  for (int l = 0; l < d_.L; ++l) { bhA_.push_back(barena_.get<float>(oA[l])); bhB_.push_back(barena_.get<float>(oB[l])); }
+  bgh_ = barena_.get<float>(ogh); bgi_ = d_.L > 1 ? barena_.get<float>(ogi) : nullptr;
+  blogits_ = barena_.get<float>(olg); bids_ = barena_.get<int>(oids);
+  for (int i = 0; i < 2; ++i) {
+    bscore_[i] = barena_.get<float>(osc[i]); bstate_[i] = barena_.get<int>(ost[i]); blen_[i] = barena_.get<int>(oln[i]);
+    brows_[i] = barena_.get<unsigned char>(orw[i]);
+  }
+  bparent_ = barena_.get<int>(opa); bchr_ = barena_.get<int>(och); bnext_ = barena_.get<int>(onx);
+  bnb_ = barena_.get<int>(onb); bplen_ = barena_.get<int>(opl); bprefix_ = barena_.get<unsigned char>(opre);
+  bready_ = true;
+}
+
+// The beam loop for n names of W beams: 1 + ML (L products + L gates (+ L - 1 input products) + the
+// logits product + select + reorder) launches, a single chain.  Every row runs record_steps_f32's
+// exact-fp32 step (the master weights, f32_splits slabs summed in order by the consumer), but on
+// fixed slots: the gates read bhA_ and write bhB_, the reorder gathers bhB_ -> bhA_.  Scores, states,
+// lengths and output rows alternate between two sets by step parity; the result is in set ML & 1.
+void Generator::record_beam(int n, int W, hipStream_t s) {
+  const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
+  const int Bp = rup(n * W, 64);
+  const int cap = std::max(Bmax_, kF32SlabRows);
+  BeamResetArgs r;
+  for (int l = 0; l < L; ++l) r.h[l] = bhA_[l];
+  r.ids = bids_; r.score = bscore_[0]; r.state = bstate_[0]; r.len = blen_[0]; r.rows = brows_[0];
+  r.N = n; r.W = W; r.L = L; r.Bp = Bp; r.H = H; r.max_len = ML; r.sos = d_.sos;
+  beam_reset(r, s);
+  auto product = [&](const float* A, const float* Wt, const float* bias, int N, float* C) {
+    GemmF32Args g;
+    g.A = A; g.lda = H; g.B = Wt; g.ldb = H; g.C = C; g.ldc = N;
+    g.bias = bias; g.M = Bp; g.N = N; g.K = H;
+    g.splits = f32_splits(Bp, N, H, cap); g.slab = (long)Bp * N;
+    gemm_f32_nt(g, s);
+    return g.splits;
+  };
+  for (int st = 0; st < ML; ++st) {
+    const int cur = st & 1, nxt = cur ^ 1;
+    for (int l = 0; l < L; ++l) {
+      const std::string k = std::to_string(l);
+      const int sh = product(bhA_[l], P("weight_hh_l" + k), P("bias_hh_l" + k), 3 * H, bgh_);
+      GruGatesF32Args a;
+      if (l == 0) {
+        a.P = Ptab32_; a.ids = bids_;
+      } else {
+        a.gi_splits = product(bhB_[l - 1], P("weight_ih_l" + k), P("bias_ih_l" + k), 3 * H, bgi_);
+        a.Gi = bgi_; a.gi_slab = (long)Bp * 3 * H;
+      }
+      a.Gh = bgh_; a.gh_splits = sh; a.gh_slab = (long)Bp * 3 * H; a.hprev = bhA_[l]; a.hout = bhB_[l];
+      a.Bp = Bp; a.H = H; a.V = V; a.err = err_;
+      gru_gates_f32(a, s);
+    }
+    BeamSelectArgs q;
+    q.splits = product(bhB_[L - 1], P("fc.weight"), P("fc.bias"), V, blogits_);
+    q.logits = blogits_; q.slab = (long)Bp * V;
+    q.score_in = bscore_[cur]; q.state_in = bstate_[cur]; q.plen = bplen_; q.prefix = bprefix_;
+    q.score_out = bscore_[nxt]; q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_; q.next_id = bnext_;
+    q.err = err_; q.N = n; q.W = W; q.V = V; q.step = st; q.max_len = ML; q.sos = d_.sos; q.eos = d_.eos;
+    beam_select_f32(q, s);
+    BeamReorderArgs o;
+    for (int l = 0; l < L; ++l) { o.h_src[l] = bhB_[l]; o.h_dst[l] = bhA_[l]; }
+    o.parent = bparent_; o.chr = bchr_; o.next_id = bnext_;
+    o.rows_src = brows_[cur]; o.rows_dst = brows_[nxt]; o.len_src = blen_[cur]; o.len_dst = blen_[nxt];
+    o.ids = bids_; o.n_beams = bnb_;
+    o.N = n; o.W = W; o.L = L; o.H = H; o.max_len = ML;
+    beam_reorder(o, s);
+    HIP_LAUNCH_CHECK();
+  }
+}
+
+void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
+                     int* n_tok, int* n_beams, hipStream_t s) {
+  GK_TRACE("gk.beam");
+  const int ML = d_.max_len;
+  if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::beam needs 1 <= width <= min(32, vocab)");
+  if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::beam needs max_len <= 64 and vocab <= 512");
+  if (d_.max_batch < W) throw std::runtime_error("Generator::beam needs max_batch >= width");
+  if (d_.L > 4) throw std::runtime_error("Generator::beam needs at most 4 layers");
+  if (!plen || !prefix || !rows || !logp || !n_tok || !n_beams)
+    throw std::runtime_error("Generator::beam: plen, prefix, rows, logp, n_tok and n_beams are required");
+  if (N <= 0) return;
+  beam_alloc();   // first call: allocates (and synchronises) before anything is captured
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
+  err_clean_ = false;
+  const int nb = d_.max_batch / W, fin = ML & 1;
+  for (int start = 0; start < N; start += nb) {
+    const int n = std::min(nb, N - start);
+    HIP_CHECK(hipMemcpyAsync(bplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      auto& g = bgraphs_[std::make_pair(n, W)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_beam(n, W, cap_);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_beam(n, W, s);
+    }
+    const size_t r0 = (size_t)start * W, nr = (size_t)n * W;
+    HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), brows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(logp + r0, bscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + r0, blen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_beams + start, bnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../runtime/runtime.h"
 #include "../kernels/kernels.h"
@@ -58,6 +59,19 @@ class Generator {
   // log-prob launch.  Buffers are allocated on the first call.
   void score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok, hipStream_t s);
   size_t score_workspace_bytes() const { return sarena_.bytes(); }   // 0 until the first score()
+  // Beam search (docs/DESIGN.md §4d; the rule: cpu_ref.beam_search): for each of N prefixes (device
+  // plen [N], prefix [N][max_len], as generate_ctl's) the W most probable output rows in order:
+  // rows [N][W][max_len+1], logp [N][W] (-inf for a dead slot), n_tok [N][W], n_beams [N], all device
+  // pointers.  Always the exact-fp32 arithmetic, whatever GenDims::fp32 says.  A name is W rows of the
+  // per-char fp32 step; a batch is floor(max_batch / W) names (throws when max_batch < W).  One
+  // single-chain graph per (names, W): reset, then per char the step's products and gates on fixed
+  // slots (read A, write B), beam_select_f32 and beam_reorder (gather B -> A).  Its buffers live in an
+  // arena of their own, committed by the first call; plen / prefix are copied there per batch, so a
+  // recording bakes no prefix in.
+  void beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp, int* n_tok,
+            int* n_beams, hipStream_t s);
+  size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
+  int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W)
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
   void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); }
@@ -98,6 +112,8 @@ class Generator {
   // off, the bit is cleared and the caller regenerates the batch on its per-char graph
   bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
   void record_score(int Bp, hipStream_t s);
+  void beam_alloc();
+  void record_beam(int n, int W, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
   GenDims d_;
@@ -154,6 +170,20 @@ class Generator {
   float *cinv_ = nullptr, *ctopp_ = nullptr;    // [Bmax] each: the current batch's controls
   int *ctopk_ = nullptr, *cplen_ = nullptr;
   unsigned char* cprefix_ = nullptr;            // [Bmax][ML]
+  // beam search (fourth arena, committed by the first beam() call)
+  Arena barena_;
+  bool bready_ = false;
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> bgraphs_;   // keyed by (names, W)
+  std::vector<float*> bhA_, bhB_;               // per layer [Bmax][H]: a step's input / output states
+  float *bgh_ = nullptr, *bgi_ = nullptr, *blogits_ = nullptr;   // product slabs, as gh_ / gi_ / logits_
+  int* bids_ = nullptr;                         // [Bmax]
+  float* bscore_[2] = {nullptr, nullptr};       // [Bmax] x2, by step parity, like the three below
+  int* bstate_[2] = {nullptr, nullptr};
+  int* blen_[2] = {nullptr, nullptr};
+  unsigned char* brows_[2] = {nullptr, nullptr};   // [Bmax][ML + 1] x2
+  int *bparent_ = nullptr, *bchr_ = nullptr, *bnext_ = nullptr, *bnb_ = nullptr;   // [Bmax] each
+  int* bplen_ = nullptr;                        // [Bmax] the current batch's prefixes
+  unsigned char* bprefix_ = nullptr;            // [Bmax][ML]
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

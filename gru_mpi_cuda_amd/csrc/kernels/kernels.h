@@ -495,6 +495,58 @@ struct ScoreLogprobArgs {          // per token: log softmax(logits)[target] and
 };
 void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ beam search (beam.hip, docs/DESIGN.md §4d)
+// A name owns W ordered beams = rows n W .. n W + W - 1 of the batch.  Beam states: 0 dead (score
+// -inf, empty row), 1 live, 2 finished (it wrote EOS; score and row frozen).
+// beam_select_f32, one workgroup per name: lp = log-softmax of each of the W logits rows
+// (score_logprob_f32's operations and order), candidates j = b V + c -- a live beam offers every c
+// with score s_b + lp[c] (only c = prefix[step] while step < plen), a finished beam the carry j = b V
+// with score s_b, a dead beam nothing -- and the first W candidates in the total order "score
+// descending, then j ascending" become the new beams, stored in that order; missing ones are dead.
+// Per new beam: score; parent (-1: dead); chr (the appended char, -1 for a carry or a dead beam);
+// state (finished when chr == eos or carried); next_id (chr of a live beam, else sos).
+// A prefix byte >= V is taken as 0 and ORs 16 into err[0] (err[1] = the byte, err[2] = the name's row).
+struct BeamSelectArgs {
+  const float* logits = nullptr;   // [>= N W][V], row n W + b
+  int splits = 1; long slab = 0;   // split-K slabs of the logits, summed in fixed order
+  const float* bias = nullptr;     // nullable: added after the slab sum
+  const float* score_in = nullptr; const int* state_in = nullptr;   // [N W]
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][max_len]
+  float* score_out = nullptr; int* parent = nullptr; int* chr = nullptr; int* state_out = nullptr;   // [N W],
+  int* next_id = nullptr;                                                                        // never the inputs
+  float* lp = nullptr;             // nullable [N W][V]: every row's log-softmax (tests)
+  int* sel = nullptr;              // nullable [N W]: the winners' flat indices j, -1 for a dead beam (tests)
+  unsigned* err = nullptr;         // nullable
+  int N = 0, W = 0, V = 0, step = 0, max_len = 0, sos = 0, eos = 0;   // V % 64 == 0, V <= 512, W <= min(32, V)
+};
+void beam_select_f32(const BeamSelectArgs& a, hipStream_t s);
+// The winners' state moved into the next step's slots: per layer h_dst[n W + k] = h_src[n W + parent[k]]
+// (zeros for a dead beam), rows_dst likewise with chr appended at the parent's length (len_src ->
+// len_dst), ids = next_id, n_beams[n] = the beams that are not dead.  A gather is never in place: source
+// and destination are different buffers.  Rows >= N W of every buffer are not touched.
+struct BeamReorderArgs {
+  const float* h_src[4] = {nullptr, nullptr, nullptr, nullptr};   // [.][H] post-step states
+  float* h_dst[4] = {nullptr, nullptr, nullptr, nullptr};         // [.][H] the next step's input states
+  const int* parent = nullptr; const int* chr = nullptr; const int* next_id = nullptr;   // [N W]
+  const unsigned char* rows_src = nullptr; unsigned char* rows_dst = nullptr;             // [.][max_len + 1]
+  const int* len_src = nullptr; int* len_dst = nullptr;                                   // [N W]
+  int* ids = nullptr;              // [N W] the next step's input ids
+  int* n_beams = nullptr;          // [N]
+  int N = 0, W = 0, L = 0, H = 0, max_len = 0;
+};
+void beam_reorder(const BeamReorderArgs& a, hipStream_t s);
+// The state before step 0 as ONE kernel node (no memset nodes, for the reason recorded at
+// Generator::reset_batch): all Bp rows h = 0, ids = sos, len = 0, NUL rows; beam 0 of each of the N
+// names live with score 0, every other row dead with score -inf.
+struct BeamResetArgs {
+  float* h[4] = {nullptr, nullptr, nullptr, nullptr};   // [Bp][H]
+  int* ids = nullptr; float* score = nullptr; int* state = nullptr; int* len = nullptr;   // [Bp]
+  unsigned char* rows = nullptr;   // [Bp][max_len + 1]
+  int N = 0, W = 0, L = 0, Bp = 0, H = 0, max_len = 0, sos = 0;
+};
+void beam_reset(const BeamResetArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ generic GEMM
 // C[M][N] (+)= A[M][K] · B[N][K]^T  (bf16 in, fp32 accumulate), both operands K-contiguous.
 struct GemmArgs {

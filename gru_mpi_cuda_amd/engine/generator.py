@@ -144,6 +144,32 @@ class HipGenerator:
             raise RuntimeError("HipGenerator.score: device token counts differ from the host's")
         return res
 
+    def beam_search(self, prefix=None, width: int = 4, count: Optional[int] = None) -> "BeamResult":
+        """The ``width`` most probable output rows per prefix, in order (the rule: cpu_ref.beam_search,
+        docs/DESIGN.md §4d).  ``prefix``: a string, a list of strings, or None for ``count`` (default 1)
+        empty prefixes.  Always exact fp32 arithmetic, whatever ``precision`` this generator samples
+        with.  A width outside [1, min(32, vocab)], a bad prefix and max_len > 64 raise ValueError
+        before anything is launched."""
+        pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
+        N, W, ML = pre.shape[0], int(width), self.cfg.max_len
+        if N == 0:
+            return BeamResult(np.zeros((0, W, ML + 1), np.uint8), np.zeros((0, W), np.float32),
+                              np.zeros((0, W), np.int32), np.zeros(0, np.int32), self.cfg.eos)
+        p, l = torch.from_numpy(pre).to(self.dev), torch.from_numpy(plen).to(self.dev)
+        rows = torch.empty(N, W, ML + 1, dtype=torch.uint8, device=self.dev)
+        logp = torch.empty(N, W, dtype=torch.float32, device=self.dev)
+        nt = torch.empty(N, W, dtype=torch.int32, device=self.dev)
+        nb = torch.empty(N, dtype=torch.int32, device=self.dev)
+        self.g.beam(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(), nb.data_ptr(),
+                    self._s())
+        err = self.g.read_error()   # synchronises: the prefix tensors stay alive until the call is done
+        if err:
+            raise RuntimeError(f"HipGenerator.beam_search: device error word {err}")
+        return BeamResult(rows.cpu().numpy(), logp.cpu().numpy(), nt.cpu().numpy(), nb.cpu().numpy(), self.cfg.eos)
+
+
+BeamResult = cpu_ref.BeamResult
+
 
 @dataclass
 class ScoreResult:

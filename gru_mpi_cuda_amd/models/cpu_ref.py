@@ -481,3 +481,149 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
         if not alive.any():
             break
     return out
+
+
+# --------------------------------------------------------------------------- beam search
+# The W most probable output rows per prefix (docs/DESIGN.md §4d).  A name holds W ordered beams, each
+# live (score, hidden states, row so far, last char), finished (it wrote EOS: score and row frozen) or
+# dead (score -inf, empty row).  Before step 0 beam 0 is live with score 0, h = 0 and input SOS; the
+# others are dead.  Every step l = 0 .. max_len - 1:
+#   1. every beam row takes the model's step (finished and dead rows with input SOS, ignored);
+#   2. lp = log softmax(logits) per live beam;
+#   3. candidates j = b V + c: a live beam offers every c with score s_b + lp[c] -- only c = prefix[l]
+#      while l < plen -- a finished beam the carry j = b V with score s_b, a dead beam nothing;
+#   4. the new beams are the first W candidates in the total order "score descending, then j
+#      ascending", stored in that order; with fewer than W candidates the rest are dead;
+#   5. (b, c) copies b's row and appends c; it is finished when c == eos (the byte is written, then
+#      the beam stops: the generator's rule), else live with b's post-step states and input c.
+# Forced chars add their log-prob: logp is the row's full log-probability, what ``score`` returns.
+BEAM_DEAD, BEAM_LIVE, BEAM_FIN = 0, 1, 2
+BEAM_MAX_WIDTH = 32
+
+
+class BeamResult:
+    """``HipGenerator.beam_search`` / ``cpu_ref.beam_search`` output for N prefixes of W beams, in order:
+    rows [N, W, MAX_LEN+1] uint8 (the ``generate`` format), logp [N, W] (-inf for a dead slot), n_tok
+    [N, W] int32, n_beams [N] int32 (the slots that are not dead, always the first ones)."""
+
+    def __init__(self, rows, logp, n_tok, n_beams, eos: int = 0):
+        self.rows, self.logp, self.n_tok, self.n_beams, self.eos = rows, logp, n_tok, n_beams, eos
+
+    def names(self) -> List[List[str]]:
+        """Per prefix the beams' names in order (the EOS byte dropped, dead slots left out)."""
+        out = []
+        for n in range(self.rows.shape[0]):
+            cur = []
+            for k in range(int(self.n_beams[n])):
+                b = bytes(self.rows[n, k, :int(self.n_tok[n, k])])
+                if b and b[-1] == self.eos:
+                    b = b[:-1]
+                cur.append(b.decode("latin-1"))
+            out.append(cur)
+        return out
+
+
+def beam_inputs(cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None):
+    """Validated (prefix rows [N, MAX_LEN] uint8, plen [N] int32) of a beam search.  ``prefix``: a str /
+    bytes, ``encode_prefixes`` input, or None for ``count`` (default 1) empty prefixes.  ValueError for
+    a width outside [1, min(32, vocab)], max_len > 64 and bad prefixes."""
+    if isinstance(width, bool) or int(width) != width or not 1 <= width <= min(BEAM_MAX_WIDTH, cfg.vocab):
+        raise ValueError(f"width must be an integer in [1, {min(BEAM_MAX_WIDTH, cfg.vocab)}], got {width!r}")
+    if cfg.max_len > 64:
+        raise ValueError(f"beam search needs max_len <= 64 (got {cfg.max_len})")
+    if not 0 <= cfg.sos < cfg.vocab:
+        raise ValueError(f"sos {cfg.sos} outside the vocabulary of {cfg.vocab}")
+    if prefix is None:
+        n = 1 if count is None else int(count)
+        if n < 0:
+            raise ValueError("count must be >= 0")
+        return np.zeros((n, cfg.max_len), np.uint8), np.zeros(n, np.int32)
+    if isinstance(prefix, (str, bytes)):
+        prefix = [prefix]
+    rows, plen = encode_prefixes(prefix, cfg)
+    if count is not None and count != rows.shape[0]:
+        raise ValueError(f"count = {count} but {rows.shape[0]} prefixes given")
+    return rows, plen
+
+
+def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_char: int = -1):
+    """Steps 3-4 for one name: lp [W, V], score [W], state [W] -> the W new beams in order as (parent,
+    chr, score, j), parent -1 for a dead slot, chr -1 for a carry or a dead slot."""
+    W, V = lp.shape
+    cand = np.full((W, V), -np.inf, dtype=lp.dtype)
+    offered = np.zeros((W, V), dtype=bool)
+    for b in range(W):
+        if state[b] == BEAM_LIVE:
+            if forced_char >= 0:
+                cand[b, forced_char] = score[b] + lp[b, forced_char]
+                offered[b, forced_char] = True
+            else:
+                cand[b] = score[b] + lp[b]
+                offered[b] = True
+        elif state[b] == BEAM_FIN:
+            cand[b, 0] = score[b]
+            offered[b, 0] = True
+    js = np.flatnonzero(offered.reshape(-1))
+    sc = cand.reshape(-1)[js]
+    order = js[np.lexsort((js, -sc))][:W]      # score descending, then j ascending
+    out = []
+    for j in order:
+        b, c = divmod(int(j), V)
+        out.append((b, -1 if state[b] == BEAM_FIN else c, cand[b, c], int(j)))
+    while len(out) < W:
+        out.append((-1, -1, lp.dtype.type(-np.inf), -1))
+    return out
+
+
+def beam_search(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None) -> BeamResult:
+    """The rule above in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli beam``)."""
+    pre, plen = beam_inputs(cfg, prefix, width, count)
+    N, W, ML, V, H = pre.shape[0], int(width), cfg.max_len, cfg.vocab, cfg.hidden
+    dt = params["fc.weight"].dtype
+    npdt = np.float64 if dt == torch.float64 else np.float32
+    rows = np.zeros((N, W, ML + 1), np.uint8)
+    score = np.full((N, W), -np.inf, npdt)
+    state = np.full((N, W), BEAM_DEAD, np.int64)
+    ntok = np.zeros((N, W), np.int32)
+    if N == 0:
+        return BeamResult(rows, score, ntok, np.zeros(0, np.int32), cfg.eos)
+    score[:, 0] = 0
+    state[:, 0] = BEAM_LIVE
+    hs = [torch.zeros(N * W, H, dtype=dt) for _ in range(cfg.layers)]
+    cur = torch.full((N * W,), cfg.sos, dtype=torch.int64)
+    for l in range(ML):
+        inp = params["embedding"][cur]
+        for k in range(cfg.layers):
+            gi = inp @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
+            gh = hs[k] @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
+            hs[k], _ = _gates(gi, gh, hs[k])
+            inp = hs[k]
+        logits = inp @ params["fc.weight"].T + params["fc.bias"]
+        if dt != torch.float64:
+            logits = logits.to(torch.float32)
+        lp = torch.log_softmax(logits, -1).numpy().reshape(N, W, V)
+        gather = np.zeros(N * W, np.int64)
+        nrows, nscore, nstate, nntok = np.zeros_like(rows), np.full_like(score, -np.inf), np.zeros_like(state), np.zeros_like(ntok)
+        nxt = np.full(N * W, cfg.sos, np.int64)
+        for n in range(N):
+            sel = beam_select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1)
+            for k, (b, c, s, _) in enumerate(sel):
+                if b < 0:
+                    continue
+                gather[n * W + k] = n * W + b
+                nrows[n, k] = rows[n, b]
+                nntok[n, k] = ntok[n, b]
+                nscore[n, k] = s
+                if c < 0:
+                    nstate[n, k] = BEAM_FIN
+                    continue
+                nrows[n, k, l] = c
+                nntok[n, k] = l + 1
+                nstate[n, k] = BEAM_FIN if c == cfg.eos else BEAM_LIVE
+                if c != cfg.eos:
+                    nxt[n * W + k] = c
+        g = torch.from_numpy(gather)
+        hs = [h[g] for h in hs]
+        rows, score, state, ntok = nrows, nscore, nstate, nntok
+        cur = torch.from_numpy(nxt)
+    return BeamResult(rows, score, ntok, (state != BEAM_DEAD).sum(1).astype(np.int32), cfg.eos)
