@@ -188,6 +188,22 @@ def cmd_train(args) -> int:
     return 0
 
 
+def _constraint_args(p) -> None:
+    p.add_argument("--pattern", default=None,
+                   help="one item per position: a char, \\char, . (any char of --charset), [abc], [a-z], [^...]")
+    p.add_argument("--charset", default=None, help="the chars a name may use (default: all)")
+    p.add_argument("--min-len", dest="min_len", type=int, default=None, help="no name shorter than this")
+    p.add_argument("--max-name-len", dest="max_name_len", type=int, default=None,
+                   help="no name longer than this (<= the model's max_len)")
+
+
+def _constraints_from(args):
+    """The make_constraints keywords of --pattern / --charset / --min-len / --max-name-len (None: none given)."""
+    kw = {k: v for k, v in (("pattern", args.pattern), ("charset", args.charset), ("min_len", args.min_len),
+                            ("max_len", args.max_name_len)) if v is not None}
+    return kw or None
+
+
 def cmd_generate(args) -> int:
     from .engine import generator as G
     from .utils.data import random_floats
@@ -213,6 +229,8 @@ def cmd_generate(args) -> int:
         if not pres:
             raise SystemExit(f"{args.prefix_file}: no prefixes")
         ctl["prefix"] = [pres[i % len(pres)] for i in range(N)]   # cycled over the names
+    if _constraints_from(args) is not None:
+        ctl["constraints"] = _constraints_from(args)
     ctx = None
     if args.cpu:
         from .parallel.dist import DistCtx
@@ -316,10 +334,11 @@ def cmd_beam(args) -> int:
     else:
         prefixes = [args.prefix or ""]
     if args.cpu or not torch.cuda.is_available():
-        res = cpu_ref.beam_search({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width)
+        res = cpu_ref.beam_search({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width,
+                                  constraints=_constraints_from(args))
     else:
         gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)))
-        res = gen.beam_search(prefixes, args.width)
+        res = gen.beam_search(prefixes, args.width, constraints=_constraints_from(args))
     lines = []
     for pre, names, lps in zip(prefixes, res.names(), res.logp):
         for k, nm in enumerate(names):
@@ -419,6 +438,7 @@ def main(argv=None) -> int:
     g.add_argument("--prefix", default=None, help="every name starts with these chars")
     g.add_argument("--prefix-file", dest="prefix_file", default=None,
                    help="one prefix per line, cycled over the names")
+    _constraint_args(g)
     g.add_argument("--cpu", action="store_true", help="force the CPU reference path (single process)")
     g.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(g)
@@ -429,6 +449,7 @@ def main(argv=None) -> int:
     bm.add_argument("--width", type=int, default=4, help="beams per prefix, 1 .. min(32, vocab)")
     bm.add_argument("--prefix", default=None, help="the names start with these chars (default: the empty prefix)")
     bm.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
+    _constraint_args(bm)
     bm.add_argument("--out", default=None, help="prefix, rank, name and log-prob per line, tab-separated")
     bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
     bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")

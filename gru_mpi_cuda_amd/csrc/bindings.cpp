@@ -209,13 +209,18 @@ PYBIND11_MODULE(_C, m) {
         g.generate(Pp<const float>(rf), N, Pp<unsigned char>(out), S(s));
       })
       .def("generate_ctl", [](Generator& g, uintptr_t rf, int N, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p,
-                              uintptr_t plen, uintptr_t prefix, uintptr_t out, uintptr_t s) {
+                              uintptr_t plen, uintptr_t prefix, uintptr_t out, uintptr_t s, uintptr_t allow_tab,
+                              uintptr_t allow_idx, int allow_rows) {
         Generator::Ctl c;
         c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
         c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
+        c.allow_tab = Pp<const unsigned>(allow_tab); c.allow_idx = Pp<const int>(allow_idx); c.allow_rows = allow_rows;
         g.generate_ctl(Pp<const float>(rf), N, c, Pp<unsigned char>(out), S(s));
-      })
+      }, py::arg("rf"), py::arg("N"), py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"), py::arg("plen"),
+         py::arg("prefix"), py::arg("out"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
+         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0)
       .def("ctl_workspace_bytes", &Generator::ctl_workspace_bytes)
+      .def("ctl_graphs", &Generator::ctl_graphs)
       .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
                        uintptr_t n_tok, uintptr_t s) {
         g.score(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
@@ -223,10 +228,13 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("score_workspace_bytes", &Generator::score_workspace_bytes)
       .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
-                      uintptr_t n_tok, uintptr_t n_beams, uintptr_t s) {
+                      uintptr_t n_tok, uintptr_t n_beams, uintptr_t s, uintptr_t allow_tab, uintptr_t allow_idx,
+                      int allow_rows) {
         g.beam(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, Pp<unsigned char>(rows), Pp<float>(logp),
-               Pp<int>(n_tok), Pp<int>(n_beams), S(s));
-      })
+               Pp<int>(n_tok), Pp<int>(n_beams), S(s), Pp<const unsigned>(allow_tab), Pp<const int>(allow_idx), allow_rows);
+      }, py::arg("plen"), py::arg("prefix"), py::arg("N"), py::arg("W"), py::arg("rows"), py::arg("logp"),
+         py::arg("n_tok"), py::arg("n_beams"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
+         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0)
       .def("beam_workspace_bytes", &Generator::beam_workspace_bytes)
       .def("beam_graphs", &Generator::beam_graphs)
       .def("set_use_graph", &Generator::set_use_graph)
@@ -748,6 +756,8 @@ PYBIND11_MODULE(_C, m) {
     c.inv_temp = GP(const float, d, "inv_temp"); c.top_k = GP(const int, d, "top_k");
     c.top_p = GP(const float, d, "top_p"); c.plen = GP(const int, d, "plen");
     c.prefix = GP(const unsigned char, d, "prefix"); c.row0 = get<int>(d, "row0", 0); c.err = GP(unsigned, d, "err");
+    c.allow_tab = GP(const unsigned, d, "allow_tab"); c.allow_idx = GP(const int, d, "allow_idx");
+    c.allow_rows = get<int>(d, "allow_rows", 0);
     sample_ctl_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
@@ -860,6 +870,8 @@ PYBIND11_MODULE(_C, m) {
     a.lp = GP(float, d, "lp"); a.sel = GP(int, d, "sel"); a.err = GP(unsigned, d, "err");
     a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0);
     a.max_len = get<int>(d, "max_len", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
+    a.allow_rows = get<int>(d, "allow_rows", 0);
     beam_select_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });

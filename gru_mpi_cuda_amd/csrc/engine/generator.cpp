@@ -232,7 +232,7 @@ int Generator::product_f32(const float* A32, const u16* A3, const float* W32, co
   return g.splits;
 }
 
-void Generator::record_steps_f32(int n, hipStream_t s, bool ctl) {
+void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n, 64);
   const bool x3 = split3();
@@ -270,6 +270,7 @@ void Generator::record_steps_f32(int n, hipStream_t s, bool ctl) {
       SampleCtlArgs c;
       c.s = q; c.inv_temp = cinv_; c.top_k = ctopk_; c.top_p = ctopp_; c.plen = cplen_; c.prefix = cprefix_;
       c.row0 = 0; c.err = err_;
+      if (allow_rows > 0) { c.allow_tab = ctab_; c.allow_idx = cidx_; c.allow_rows = allow_rows; }
       sample_ctl_f32(c, s);
     } else {
       sample_f32(q, s);
@@ -364,9 +365,11 @@ void Generator::ctl_alloc() {
   const size_t B = Bmax_, ML = d_.max_len;
   const size_t oi = carena_.reserve(B * 4), ok = carena_.reserve(B * 4), op = carena_.reserve(B * 4);
   const size_t ol = carena_.reserve(B * 4), opre = carena_.reserve(B * ML);
+  const size_t otab = carena_.reserve((size_t)kAllowRows * (d_.V / 32) * 4), oidx = carena_.reserve(B * ML * 4);
   carena_.commit();
   cinv_ = carena_.get<float>(oi); ctopk_ = carena_.get<int>(ok); ctopp_ = carena_.get<float>(op);
   cplen_ = carena_.get<int>(ol); cprefix_ = carena_.get<unsigned char>(opre);
+  ctab_ = carena_.get<unsigned>(otab); cidx_ = carena_.get<int>(oidx);
   cready_ = true;
 }
 
@@ -375,13 +378,18 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
   if (!d_.fp32) throw std::runtime_error("Generator::generate_ctl: sampling controls need precision fp32 or bf16x3");
   if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix)
     throw std::runtime_error("Generator::generate_ctl: every control array is required");
+  const bool masked = c.allow_tab != nullptr;
+  if (masked != (c.allow_idx != nullptr) || (masked && (c.allow_rows < 1 || c.allow_rows > kAllowRows)))
+    throw std::runtime_error("Generator::generate_ctl: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   const int ML = d_.max_len;
   if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
+  bool tab_staged = false;
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
-    if (uses_persist_ctl(n)) {   // one controlled launch on the caller's arrays at this batch's rows
+    // (a constrained batch never: the persistent variants have no mask, docs/DESIGN.md §4e)
+    if (!masked && uses_persist_ctl(n)) {   // one controlled launch on the caller's arrays at this batch's rows
       Ctl b;
       b.inv_temp = c.inv_temp + start; b.top_k = c.top_k + start; b.top_p = c.top_p + start; b.plen = c.plen + start;
       b.prefix = c.prefix + (size_t)start * ML;
@@ -395,17 +403,27 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
     HIP_CHECK(hipMemcpyAsync(ctopp_, c.top_p + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cplen_, c.plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cprefix_, c.prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    const int ar = masked ? c.allow_rows : 0;
+    if (masked) {   // the table once per call, this batch's lines
+      if (!tab_staged) {
+        HIP_CHECK(hipMemcpyAsync(ctab_, c.allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+        tab_staged = true;
+      }
+      HIP_CHECK(hipMemcpyAsync(cidx_, c.allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    }
     if (use_graph_) {
-      auto& g = cgraphs_[n];
+      // the recording bakes the table's line count in (the sampler checks every entry against it),
+      // so it is part of the key; 0 = the unconstrained graph, the only one an unconstrained call sees
+      auto& g = cgraphs_[std::make_pair(n, ar)];
       if (!g) {
         g.reset(new Graph());
         g->begin(cap_);
-        record_steps_f32(n, cap_, true);
+        record_steps_f32(n, cap_, true, ar);
         g->end(cap_);
       }
       g->launch(s);
     } else {
-      record_steps_f32(n, s, true);
+      record_steps_f32(n, s, true, ar);
     }
     HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
   }
@@ -539,6 +557,7 @@ void Generator::beam_alloc() {
   }
   const size_t opa = barena_.reserve(B * 4), och = barena_.reserve(B * 4), onx = barena_.reserve(B * 4);
   const size_t onb = barena_.reserve(B * 4), opl = barena_.reserve(B * 4), opre = barena_.reserve(B * ML);
+  const size_t otab = barena_.reserve((size_t)kAllowRows * (d_.V / 32) * 4), oidx = barena_.reserve(B * ML * 4);
   barena_.commit();
   for (int l = 0; l < d_.L; ++l) { bhA_.push_back(barena_.get<float>(oA[l])); bhB_.push_back(barena_.get<float>(oB[l])); }
   bgh_ = barena_.get<float>(ogh); bgi_ = d_.L > 1 ? barena_.get<float>(ogi) : nullptr;
@@ -549,6 +568,7 @@ void Generator::beam_alloc() {
   }
   bparent_ = barena_.get<int>(opa); bchr_ = barena_.get<int>(och); bnext_ = barena_.get<int>(onx);
   bnb_ = barena_.get<int>(onb); bplen_ = barena_.get<int>(opl); bprefix_ = barena_.get<unsigned char>(opre);
+  btab_ = barena_.get<unsigned>(otab); bidx_ = barena_.get<int>(oidx);
   bready_ = true;
 }
 
@@ -557,7 +577,7 @@ void Generator::beam_alloc() {
 // exact-fp32 step (the master weights, f32_splits slabs summed in order by the consumer), but on
 // fixed slots: the gates read bhA_ and write bhB_, the reorder gathers bhB_ -> bhA_.  Scores, states,
 // lengths and output rows alternate between two sets by step parity; the result is in set ML & 1.
-void Generator::record_beam(int n, int W, hipStream_t s) {
+void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n * W, 64);
   const int cap = std::max(Bmax_, kF32SlabRows);
@@ -596,6 +616,7 @@ void Generator::record_beam(int n, int W, hipStream_t s) {
     q.score_in = bscore_[cur]; q.state_in = bstate_[cur]; q.plen = bplen_; q.prefix = bprefix_;
     q.score_out = bscore_[nxt]; q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_; q.next_id = bnext_;
     q.err = err_; q.N = n; q.W = W; q.V = V; q.step = st; q.max_len = ML; q.sos = d_.sos; q.eos = d_.eos;
+    if (allow_rows > 0) { q.allow_tab = btab_; q.allow_idx = bidx_; q.allow_rows = allow_rows; }
     beam_select_f32(q, s);
     BeamReorderArgs o;
     for (int l = 0; l < L; ++l) { o.h_src[l] = bhB_[l]; o.h_dst[l] = bhA_[l]; }
@@ -609,7 +630,8 @@ void Generator::record_beam(int n, int W, hipStream_t s) {
 }
 
 void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
-                     int* n_tok, int* n_beams, hipStream_t s) {
+                     int* n_tok, int* n_beams, hipStream_t s, const unsigned* allow_tab, const int* allow_idx,
+                     int allow_rows) {
   GK_TRACE("gk.beam");
   const int ML = d_.max_len;
   if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::beam needs 1 <= width <= min(32, vocab)");
@@ -618,26 +640,34 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
   if (d_.L > 4) throw std::runtime_error("Generator::beam needs at most 4 layers");
   if (!plen || !prefix || !rows || !logp || !n_tok || !n_beams)
     throw std::runtime_error("Generator::beam: plen, prefix, rows, logp, n_tok and n_beams are required");
+  const bool masked = allow_tab != nullptr;
+  if (masked != (allow_idx != nullptr) || (masked && (allow_rows < 1 || allow_rows > kAllowRows)))
+    throw std::runtime_error("Generator::beam: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   beam_alloc();   // first call: allocates (and synchronises) before anything is captured
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   const int nb = d_.max_batch / W, fin = ML & 1;
+  const int ar = masked ? allow_rows : 0;
+  if (masked)   // the table once per call
+    HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
   for (int start = 0; start < N; start += nb) {
     const int n = std::min(nb, N - start);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    if (masked)
+      HIP_CHECK(hipMemcpyAsync(bidx_, allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     if (use_graph_) {
-      auto& g = bgraphs_[std::make_pair(n, W)];
+      auto& g = bgraphs_[std::make_tuple(n, W, ar)];   // ar: baked into the recording, as in generate_ctl
       if (!g) {
         g.reset(new Graph());
         g->begin(cap_);
-        record_beam(n, W, cap_);
+        record_beam(n, W, cap_, ar);
         g->end(cap_);
       }
       g->launch(s);
     } else {
-      record_beam(n, W, s);
+      record_beam(n, W, s, ar);
     }
     const size_t r0 = (size_t)start * W, nr = (size_t)n * W;
     HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), brows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));

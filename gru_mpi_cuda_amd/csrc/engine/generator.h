@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 #include "../runtime/runtime.h"
@@ -40,10 +41,16 @@ class Generator {
   // bf16x3 graph with sample_ctl_f32 as its sampler node.  That graph reads the controls from buffers
   // of an arena of their own (allocated by the first batch that takes it) into which each batch's
   // slice is copied, so one recording per n serves every value.
+  // Constraints (docs/DESIGN.md §4e; allow_tab [allow_rows][V / 32] and allow_idx [N][max_len], device
+  // pointers, both or neither, allow_rows <= kAllowRows): every batch of a constrained call takes the
+  // per-char graph -- the persistent variants have no mask -- in a recording of its own per n, whose
+  // sampler reads the table and the batch's idx slice from two more buffers of that arena.
   struct Ctl {
     const float* inv_temp = nullptr; const int* top_k = nullptr; const float* top_p = nullptr;
     const int* plen = nullptr; const unsigned char* prefix = nullptr;
+    const unsigned* allow_tab = nullptr; const int* allow_idx = nullptr; int allow_rows = 0;
   };
+  static constexpr int kAllowRows = 1024;   // lines of a constraint table
   void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
   size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until a batch takes the per-char controlled graph
   // generate_ctl() batches of n names run as one controlled persistent launch (exact fp32, as the plain
@@ -67,11 +74,14 @@ class Generator {
   // single-chain graph per (names, W): reset, then per char the step's products and gates on fixed
   // slots (read A, write B), beam_select_f32 and beam_reorder (gather B -> A).  Its buffers live in an
   // arena of their own, committed by the first call; plen / prefix are copied there per batch, so a
-  // recording bakes no prefix in.
+  // recording bakes no prefix in.  allow_tab / allow_idx ([N][max_len]) / allow_rows: the names'
+  // constraints as in Ctl (null: none); a constrained call has its own graph per (names, W).
   void beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp, int* n_tok,
-            int* n_beams, hipStream_t s);
+            int* n_beams, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
+            int allow_rows = 0);
   size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
-  int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W)
+  int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
+  int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
   void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); }
@@ -98,7 +108,8 @@ class Generator {
 
  private:
   void record_steps(int n_active, hipStream_t s);
-  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false);   // ctl: sample_ctl_f32 as the sampler node
+  // ctl: sample_ctl_f32 as the sampler node; allow_rows > 0: with the constraint buffers
+  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false, int allow_rows = 0);
   // one product of the fp32 / bf16x3 path: C = h W^T (+ bias) -> splits (slabs of M x N at C).  fp32
   // reads A32 / W32; bf16x3 the split copies A3 ([hi|hi|lo] rows) / W3 ([hi|lo|hi] rows)
   int product_f32(const float* A32, const u16* A3, const float* W32, const u16* W3, const float* bias, int M, int N,
@@ -113,7 +124,7 @@ class Generator {
   bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
   void record_score(int Bp, hipStream_t s);
   void beam_alloc();
-  void record_beam(int n, int W, hipStream_t s);
+  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
   GenDims d_;
@@ -166,14 +177,17 @@ class Generator {
   // sampling controls (third arena, committed by the first generate_ctl() call)
   Arena carena_;
   bool cready_ = false;
-  std::map<int, std::unique_ptr<Graph>> cgraphs_;   // controlled per-char graphs, keyed by active-name count
+  // controlled per-char graphs, keyed by (active-name count, constraint table lines or 0)
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> cgraphs_;
   float *cinv_ = nullptr, *ctopp_ = nullptr;    // [Bmax] each: the current batch's controls
   int *ctopk_ = nullptr, *cplen_ = nullptr;
   unsigned char* cprefix_ = nullptr;            // [Bmax][ML]
+  unsigned* ctab_ = nullptr;                    // [kAllowRows][V / 32] the call's constraint table
+  int* cidx_ = nullptr;                         // [Bmax][ML] the current batch's lines
   // beam search (fourth arena, committed by the first beam() call)
   Arena barena_;
   bool bready_ = false;
-  std::map<std::pair<int, int>, std::unique_ptr<Graph>> bgraphs_;   // keyed by (names, W)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> bgraphs_;   // keyed by (names, W, table lines or 0)
   std::vector<float*> bhA_, bhB_;               // per layer [Bmax][H]: a step's input / output states
   float *bgh_ = nullptr, *bgi_ = nullptr, *blogits_ = nullptr;   // product slabs, as gh_ / gi_ / logits_
   int* bids_ = nullptr;                         // [Bmax]
@@ -184,6 +198,8 @@ class Generator {
   int *bparent_ = nullptr, *bchr_ = nullptr, *bnext_ = nullptr, *bnb_ = nullptr;   // [Bmax] each
   int* bplen_ = nullptr;                        // [Bmax] the current batch's prefixes
   unsigned char* bprefix_ = nullptr;            // [Bmax][ML]
+  unsigned* btab_ = nullptr;                    // [kAllowRows][V / 32] the call's constraint table
+  int* bidx_ = nullptr;                         // [Bmax][ML] the current batch's lines
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

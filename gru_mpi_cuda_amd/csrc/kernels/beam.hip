@@ -16,6 +16,11 @@
 // winner rescans its registers.  One barrier per round and no global memory inside the rounds, no
 // atomics on results, no cross-workgroup communication; every cross-lane statistic is one of the
 // fixed-order DPP helpers of gen_sample.h, in score_logprob_f32's order of operations.
+//
+// Constraints (docs/DESIGN.md §4e, the MASK instantiations): the name's allowed chars at this step are
+// one line of a bit table; a lane loads the one word that covers its V/64 chars once, before the rows,
+// and a live beam's masked candidate keeps key 0.  Carries are not masked.  MASK = false is the kernel
+// as it was.
 #include <cmath>
 #include <stdexcept>
 #include "kernels.h"
@@ -41,7 +46,7 @@ DEV unsigned wave_umax(unsigned u) {   // identical in every lane
 }  // namespace
 
 // R: beam rows per wave (wave w owns beams w and w + nw), MAXPER: logits per lane and row
-template <int R, int MAXPER>
+template <int R, int MAXPER, bool MASK>
 __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a) {
 #pragma clang fp contract(off)
   __shared__ unsigned s_key[2][kMaxWaves];
@@ -63,6 +68,19 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
       }
       fc = 0;
     }
+  }
+  unsigned ok = 0u;   // MASK: bit e = this lane's char e is allowed
+  if constexpr (MASK) {
+    int ar = a.allow_idx[(size_t)n * a.max_len + a.step];
+    if (ar < 0 || ar >= a.allow_rows) {   // never expected (the host builds both): flag it, no constraint
+      if (a.err && threadIdx.x == 0) {
+        atomicOr(a.err, 16u);
+        a.err[1] = (unsigned)ar;
+        a.err[2] = (unsigned)(n * W);
+      }
+      ar = 0;
+    }
+    ok = a.allow_tab[(size_t)ar * (V >> 5) + ((lane * per) >> 5)] >> ((lane * per) & 31);
   }
   // candidates of this wave's rows: key 0 = not offered
   unsigned key[R][MAXPER];
@@ -104,7 +122,7 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
       const float lp = (xv[e] - mx) - lse;
       if (a.lp) a.lp[row * V + c] = lp;
       if (st == kLive) {
-        if (!forced || c == fc) key[r][e] = beam_key(sb + lp);
+        if ((!forced || c == fc) && (!MASK || ((ok >> e) & 1u))) key[r][e] = beam_key(sb + lp);
       } else if (st == kFin && c == 0) {
         key[r][e] = beam_key(sb);   // the carry, j = b V
       }
@@ -193,15 +211,28 @@ void beam_select_f32(const BeamSelectArgs& a, hipStream_t s) {
     throw std::runtime_error("beam_select_f32: needs 0 <= step < max_len, eos >= 0 and 0 <= sos < V");
   if (a.splits < 1 || (a.splits > 1 && a.slab < (long)a.N * a.W * a.V))
     throw std::runtime_error("beam_select_f32: split-K slabs overlap");
+  if ((a.allow_tab != nullptr) != (a.allow_idx != nullptr))
+    throw std::runtime_error("beam_select_f32: allow_tab and allow_idx are set together or not at all");
+  const bool mask = a.allow_tab != nullptr;
+  if (mask && (a.allow_rows < 1 || 32 % (a.V / 64)))
+    throw std::runtime_error("beam_select_f32: constraints need allow_rows >= 1 and V / 64 in {1, 2, 4, 8}");
   if (a.N <= 0) return;
   const int nw = a.W <= kMaxWaves ? a.W : kMaxWaves;
   const dim3 grid(a.N), block(64 * nw);
-  if (a.W <= kMaxWaves) {
-    if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<1, 4>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((beam_select_f32_kernel<1, 8>), grid, block, 0, s, a);
+  if (mask) {
+    if (a.W <= kMaxWaves) {
+      if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<1, 4, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((beam_select_f32_kernel<1, 8, true>), grid, block, 0, s, a);
+    } else {
+      if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<2, 4, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((beam_select_f32_kernel<2, 8, true>), grid, block, 0, s, a);
+    }
+  } else if (a.W <= kMaxWaves) {
+    if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<1, 4, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((beam_select_f32_kernel<1, 8, false>), grid, block, 0, s, a);
   } else {
-    if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<2, 4>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((beam_select_f32_kernel<2, 8>), grid, block, 0, s, a);
+    if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<2, 4, false>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((beam_select_f32_kernel<2, 8, false>), grid, block, 0, s, a);
   }
 }
 

@@ -18,6 +18,11 @@
 // The persistent generator's controlled variants carry a second copy of this rule, ctl_sample_wave
 // (gen_sample_ctl.h), written for a kernel with no registers to spare: a change to one belongs in
 // the other (tests/test_sampling_ctl_gpu.py holds this one, tests/test_gen_persist_ctl_gpu.py that).
+//
+// Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy has none): a row's
+// allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one
+// 32-bit word of that line -- one load per lane and row -- and a masked char takes y = -inf after the
+// temperature scale and is in no kept set.  MASK = false is the kernel as it was.
 #include "kernels.h"
 #include "common.h"
 #include "gen_sample.h"
@@ -31,7 +36,7 @@ DEV unsigned order_key(float f) {
   return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
-template <int MAXPER>
+template <int MAXPER, bool MASK>
 __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
 #pragma clang fp contract(off)
   const SampleF32Args& a = c.s;
@@ -60,6 +65,19 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
     const int k = c.top_k[cb];
     const float tp = c.top_p[cb];
     const float scale = it == 0.f ? 1.f : it;
+    unsigned ok = 0u;   // MASK: bit e = this lane's char e is allowed
+    if constexpr (MASK) {
+      int ar = c.allow_idx[(size_t)cb * a.max_len + a.step];
+      if (ar < 0 || ar >= c.allow_rows) {   // never expected (the host builds both): flag it, no constraint
+        if (c.err && lane == 0) {
+          atomicOr(c.err, 16u);
+          c.err[1] = (unsigned)ar;
+          c.err[2] = (unsigned)b;
+        }
+        ar = 0;
+      }
+      ok = c.allow_tab[(size_t)ar * (V >> 5) + ((lane * per) >> 5)] >> ((lane * per) & 31);
+    }
     float y[MAXPER];
     float mx = -INFINITY;
 #pragma unroll
@@ -69,6 +87,8 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
         for (int s2 = 1; s2 < a.splits; ++s2) v += x[s2 * a.slab + e];   // split-K slabs, fixed order
         if (a.bias) v += a.bias[lane * per + e];
         y[e] = v * scale;
+        if constexpr (MASK)
+          if (!((ok >> e) & 1u)) y[e] = -INFINITY;
       } else {
         y[e] = -INFINITY;
       }
@@ -79,7 +99,7 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
       int first = V;
 #pragma unroll
       for (int e = MAXPER - 1; e >= 0; --e)
-        if (e < per && y[e] == mx) first = lane * per + e;
+        if (e < per && y[e] == mx && (!MASK || ((ok >> e) & 1u))) first = lane * per + e;
       sel = wave_min_dpp(first);
       if (sel >= V) sel = V - 1;   // (only a row of NaNs gets here)
       if (prow)
@@ -89,7 +109,7 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
     } else {
       bool keep[MAXPER];
 #pragma unroll
-      for (int e = 0; e < MAXPER; ++e) keep[e] = e < per;
+      for (int e = 0; e < MAXPER; ++e) keep[e] = e < per && (!MASK || ((ok >> e) & 1u));
       if (k > 0 && k < V) {   // t = key of the k-th largest value: the largest t with #{key >= t} >= k
         unsigned key[MAXPER];
 #pragma unroll
@@ -99,11 +119,11 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
           const unsigned cand = t | (1u << bit);
           int cnt = 0;
 #pragma unroll
-          for (int e = 0; e < MAXPER; ++e) cnt += __popcll(__ballot(e < per && key[e] >= cand));
+          for (int e = 0; e < MAXPER; ++e) cnt += __popcll(__ballot((MASK ? keep[e] : e < per) && key[e] >= cand));
           if (cnt >= k) t = cand;
         }
 #pragma unroll
-        for (int e = 0; e < MAXPER; ++e) keep[e] = e < per && key[e] >= t;
+        for (int e = 0; e < MAXPER; ++e) keep[e] = (MASK ? keep[e] : e < per) && key[e] >= t;
       }
       float ex[MAXPER];
       float se = 0.f;
@@ -161,7 +181,10 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
 #pragma unroll
       for (int e = 0; e < MAXPER; ++e) {
         psum += p[e];
-        if (e < per && hit == V && psum > rnd) hit = lane * per + e;
+        // MASK: only a kept char is a hit.  The scan's lanes associate their sums differently, so a lane
+        // past the last kept char can hold a total one ulp above an earlier lane's and exceed an r that
+        // no kept char's running sum exceeded; unmasked, any index it picks is at least a legal char
+        if (e < per && hit == V && psum > rnd && (!MASK || keep[e])) hit = lane * per + e;
       }
       hit = wave_min_dpp(hit);
       last = -wave_min_dpp(-last);   // the highest kept index (V - 1 with nothing filtered)
@@ -182,9 +205,20 @@ void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s) {
   if (a.V % 64 || a.V > 512 || a.V <= 0) throw std::runtime_error("sample_ctl_f32: needs V % 64 == 0 and V <= 512");
   if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix || c.row0 < 0)
     throw std::runtime_error("sample_ctl_f32: inv_temp, top_k, top_p, plen and prefix are required");
+  if ((c.allow_tab != nullptr) != (c.allow_idx != nullptr))
+    throw std::runtime_error("sample_ctl_f32: allow_tab and allow_idx are set together or not at all");
+  const bool mask = c.allow_tab != nullptr;
+  if (mask && (c.allow_rows < 1 || 32 % (a.V / 64)))
+    throw std::runtime_error("sample_ctl_f32: constraints need allow_rows >= 1 and V / 64 in {1, 2, 4, 8}");
   if (a.N <= 0) return;
-  if (a.V == 256) hipLaunchKernelGGL(sample_ctl_f32_kernel<4>, dim3(a.N), dim3(64), 0, s, c);
-  else hipLaunchKernelGGL(sample_ctl_f32_kernel<8>, dim3(a.N), dim3(64), 0, s, c);
+  const dim3 grid(a.N), block(64);
+  if (a.V == 256) {
+    if (mask) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true>), grid, block, 0, s, c);
+    else hipLaunchKernelGGL((sample_ctl_f32_kernel<4, false>), grid, block, 0, s, c);
+  } else {
+    if (mask) hipLaunchKernelGGL((sample_ctl_f32_kernel<8, true>), grid, block, 0, s, c);
+    else hipLaunchKernelGGL((sample_ctl_f32_kernel<8, false>), grid, block, 0, s, c);
+  }
 }
 
 }  // namespace gk

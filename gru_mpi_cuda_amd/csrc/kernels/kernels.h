@@ -375,6 +375,12 @@ void sample_f32(const SampleF32Args& a, hipStream_t s);
 // the maximum logit); else y = x * inv_temp, top-k (0 or >= V: off), softmax, top-p (>= 1: off),
 // renormalise, `psum > r`, falling back to the highest kept index.  probs (s.probs, nullable) gets
 // the renormalised filtered row.
+// Constraints (docs/DESIGN.md §4e; allow_tab and allow_idx both set, or both null): the chars a row may
+// emit at this step are the bits of table line allow_idx[(b + row0) * max_len + step] -- bit c % 32 of
+// word c / 32 -- and a masked char has y = -inf after the temperature scale: never the greedy choice,
+// never counted or kept by top-k, probability exactly 0.  A forced step does not read them.  An entry
+// outside [0, allow_rows) ORs 16 into err[0] (err[1] = the entry, err[2] = the row) and takes line 0.
+// Needs 32 % (V / 64) == 0, so that a lane's chars lie in one word.
 struct SampleCtlArgs {
   SampleF32Args s;
   const float* inv_temp = nullptr;         // [..]  1 / T, 0 for T == 0
@@ -384,6 +390,9 @@ struct SampleCtlArgs {
   const unsigned char* prefix = nullptr;   // [..][max_len]
   int row0 = 0;
   unsigned* err = nullptr;                 // nullable: bit 4 set (and the char clamped) on a prefix byte >= V
+  const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]: the allowed sets as bit masks
+  const int* allow_idx = nullptr;          // nullable [..][max_len]: the table line of a row's step
+  int allow_rows = 0;
 };
 void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s);
 // bf16x3 operands: an fp32 value x = hi + lo with hi = bf16(x), lo = bf16(x - hi).  Weights become
@@ -506,6 +515,9 @@ void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
 // Per new beam: score; parent (-1: dead); chr (the appended char, -1 for a carry or a dead beam);
 // state (finished when chr == eos or carried); next_id (chr of a live beam, else sos).
 // A prefix byte >= V is taken as 0 and ORs 16 into err[0] (err[1] = the byte, err[2] = the name's row).
+// Constraints (docs/DESIGN.md §4e; allow_tab and allow_idx both set, or both null): a live beam offers c
+// only if bit c of table line allow_idx[n * max_len + step] is set (SampleCtlArgs' layout, and its
+// rule for an entry outside [0, allow_rows)), also on a forced step; a finished beam's carry is not masked.
 struct BeamSelectArgs {
   const float* logits = nullptr;   // [>= N W][V], row n W + b
   int splits = 1; long slab = 0;   // split-K slabs of the logits, summed in fixed order
@@ -519,6 +531,9 @@ struct BeamSelectArgs {
   int* sel = nullptr;              // nullable [N W]: the winners' flat indices j, -1 for a dead beam (tests)
   unsigned* err = nullptr;         // nullable
   int N = 0, W = 0, V = 0, step = 0, max_len = 0, sos = 0, eos = 0;   // V % 64 == 0, V <= 512, W <= min(32, V)
+  const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]
+  const int* allow_idx = nullptr;          // nullable [N][max_len]
+  int allow_rows = 0;
 };
 void beam_select_f32(const BeamSelectArgs& a, hipStream_t s);
 // The winners' state moved into the next step's slots: per layer h_dst[n W + k] = h_src[n W + parent[k]]

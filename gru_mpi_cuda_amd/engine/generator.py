@@ -75,41 +75,57 @@ class HipGenerator:
     def _s(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
 
+    def _constraint_tensors(self, cons):
+        """A Constraints object's arrays on the device: (tab, idx, lines)."""
+        if self.cfg.vocab // 64 not in (1, 2, 4, 8):
+            raise ValueError(f"constraints need vocab in (64, 128, 256, 512), got {self.cfg.vocab}")
+        tab = torch.from_numpy(cons.tab.view(np.int32)).to(self.dev)
+        idx = torch.from_numpy(np.ascontiguousarray(cons.idx, dtype=np.int32)).to(self.dev)
+        return tab, idx, cons.rows
+
     def generate_device(self, rf_dev: torch.Tensor, n: int, *, temperature=None, top_k=None, top_p=None,
-                        prefix=None) -> torch.Tensor:
+                        prefix=None, constraints=None) -> torch.Tensor:
         """``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (scalars or one value per name; semantics:
         cpu_ref.make_controls, docs/DESIGN.md §4b): any that is not None -- a neutral value too -- takes
         the controlled path (fp32 / bf16x3 only): per batch one controlled persistent launch where
-        ``g.uses_persist_ctl(batch)`` says so (small batches), else the controlled per-char graph.  Bad
-        values raise ValueError before anything is launched."""
+        ``g.uses_persist_ctl(batch)`` says so (small batches), else the controlled per-char graph.
+        ``constraints`` (a cpu_ref.Constraints for the ``n`` names, or a dict of cpu_ref.make_constraints
+        keywords; docs/DESIGN.md §4e): every name samples inside its per-position allowed sets, always on
+        the controlled per-char graph.  Bad values raise ValueError before anything is launched."""
         ML = self.cfg.max_len
         ctl = None
-        if any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        cons = cpu_ref.as_constraints(self.cfg, max(n, 0), constraints)
+        if cons is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
             if self.precision == "bf16":
-                raise ValueError('sampling controls need precision "fp32" or "bf16x3" (the bf16 mode samples '
-                                 "inside its fused FC kernel)")
+                raise ValueError('sampling controls and constraints need precision "fp32" or "bf16x3" (the bf16 '
+                                 "mode samples inside its fused FC kernel)")
             ctl = cpu_ref.make_controls(self.cfg, max(n, 0), temperature, top_k, top_p, prefix)
+            cpu_ref.check_prefix_allowed(cons, ctl.prefix, ctl.plen)
         out = torch.empty(max(n, 1), ML + 1, dtype=torch.uint8, device=self.dev)   # every row written
         if n > 0 and ctl is None:
             self.g.generate(rf_dev.data_ptr(), n, out.data_ptr(), self._s())
         elif n > 0:
             dev = [torch.from_numpy(a).to(self.dev) for a in (ctl.inv_temp, ctl.top_k, ctl.top_p, ctl.plen, ctl.prefix)]
-            self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s())
+            extra = ()
+            if cons is not None:
+                tab, idx, rows = self._constraint_tensors(cons)
+                extra = (tab.data_ptr(), idx.data_ptr(), rows)
+            self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s(), *extra)
             err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
             if err:
                 raise RuntimeError(f"HipGenerator.generate: device error word {err}")
         return out[:n]
 
     def generate(self, rfloats: np.ndarray, start: int = 0, count: Optional[int] = None, *, temperature=None,
-                 top_k=None, top_p=None, prefix=None) -> np.ndarray:
-        """Names ``start .. start+count-1`` of the job.  The controls are generate_device's; per-name values
-        are indexed by the generated names (``count`` entries)."""
+                 top_k=None, top_p=None, prefix=None, constraints=None) -> np.ndarray:
+        """Names ``start .. start+count-1`` of the job.  The controls and constraints are generate_device's;
+        per-name values are indexed by the generated names (``count`` entries)."""
         ML = self.cfg.max_len
         N = (rfloats.size // ML - start) if count is None else count
         rf = torch.from_numpy(np.ascontiguousarray(rfloats[start * ML:(start + N) * ML], dtype=np.float32))
         rf = rf.to(self.dev)
         return self.generate_device(rf, N, temperature=temperature, top_k=top_k, top_p=top_p,
-                                    prefix=prefix).cpu().numpy()
+                                    prefix=prefix, constraints=constraints).cpu().numpy()
 
     def load_state(self, params: Dict[str, torch.Tensor]) -> None:
         """New weights (cfg-shaped tensors) into the flat buffer; every derived copy and table follows."""
@@ -144,14 +160,18 @@ class HipGenerator:
             raise RuntimeError("HipGenerator.score: device token counts differ from the host's")
         return res
 
-    def beam_search(self, prefix=None, width: int = 4, count: Optional[int] = None) -> "BeamResult":
+    def beam_search(self, prefix=None, width: int = 4, count: Optional[int] = None, constraints=None) -> "BeamResult":
         """The ``width`` most probable output rows per prefix, in order (the rule: cpu_ref.beam_search,
         docs/DESIGN.md §4d).  ``prefix``: a string, a list of strings, or None for ``count`` (default 1)
         empty prefixes.  Always exact fp32 arithmetic, whatever ``precision`` this generator samples
-        with.  A width outside [1, min(32, vocab)], a bad prefix and max_len > 64 raise ValueError
-        before anything is launched."""
+        with.  ``constraints`` (a cpu_ref.Constraints for the prefixes, or a dict of
+        cpu_ref.make_constraints keywords; docs/DESIGN.md §4e): the ``width`` most probable rows that
+        satisfy them.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
+        raise ValueError before anything is launched."""
         pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
         N, W, ML = pre.shape[0], int(width), self.cfg.max_len
+        cons = cpu_ref.as_constraints(self.cfg, N, constraints)
+        cpu_ref.check_prefix_allowed(cons, pre, plen)
         if N == 0:
             return BeamResult(np.zeros((0, W, ML + 1), np.uint8), np.zeros((0, W), np.float32),
                               np.zeros((0, W), np.int32), np.zeros(0, np.int32), self.cfg.eos)
@@ -160,8 +180,12 @@ class HipGenerator:
         logp = torch.empty(N, W, dtype=torch.float32, device=self.dev)
         nt = torch.empty(N, W, dtype=torch.int32, device=self.dev)
         nb = torch.empty(N, dtype=torch.int32, device=self.dev)
+        extra = ()
+        if cons is not None:
+            tab, idx, lines = self._constraint_tensors(cons)
+            extra = (tab.data_ptr(), idx.data_ptr(), lines)
         self.g.beam(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(), nb.data_ptr(),
-                    self._s())
+                    self._s(), *extra)
         err = self.g.read_error()   # synchronises: the prefix tensors stay alive until the call is done
         if err:
             raise RuntimeError(f"HipGenerator.beam_search: device error word {err}")
@@ -294,11 +318,25 @@ def _slice_control(v, N: int, start: int, count: int):
     return v[start:start + count]
 
 
+def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: int):
+    """This rank's part of the job's constraints: a Constraints object's idx rows by global name index
+    (the table is shared), a keyword dict's per-name values like any control."""
+    if constraints is None:
+        return None
+    if isinstance(constraints, cpu_ref.Constraints):
+        if constraints.idx.shape[0] != N:
+            raise ValueError(f"constraints for {N} names expected, got {constraints.idx.shape[0]}")
+        return constraints.slice(start, count)
+    return {k: _slice_control(v, N, start, count) for k, v in dict(constraints).items()}
+
+
 def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
-            prefix=None) -> None:
+            prefix=None, constraints=None) -> None:
     """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
-    scalars or one value per name of the job; every rank takes its names' slice."""
+    scalars or one value per name of the job; every rank takes its names' slice.  ``constraints``: a
+    cpu_ref.Constraints for the N names or a dict of make_constraints keywords (docs/DESIGN.md §4e),
+    sliced by global name index like the prefixes."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len
@@ -306,6 +344,8 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
     per = -(-N // ctx.world)          # ceil: fixed slab size for the all-gather
     ctl = {k: _slice_control(v, N, start, count) for k, v in
            (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("prefix", prefix)) if v is not None}
+    if constraints is not None:
+        ctl["constraints"] = _slice_constraints(cfg, constraints, N, start, count)
     if _S.gen is not None:
         _S.gen.g.set_global_names(N)   # bf16 mode: the same arithmetic path at every world size
         mine = _S.gen.generate(random_floats, start, count, **ctl)

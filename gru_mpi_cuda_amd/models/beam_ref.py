@@ -153,12 +153,14 @@ def log_softmax(x: np.ndarray, f64: bool) -> np.ndarray:
 
 
 def select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced: int, eos: int, sos: int,
-           mut: Optional[str] = None) -> Out:
+           mut: Optional[str] = None, allowed: Optional[np.ndarray] = None) -> Out:
     """Steps 3-5 of the rule for one name in the dtype of ``lp``: the W new beams (parent, chr, state,
     score, next_id, sel = the flat index j) and ``gaps``: the neighbour gaps of the first W + 1
-    candidates in order."""
+    candidates in order.  ``allowed``: bool [V], the name's constraint set at this step (docs/DESIGN.md
+    §4e; None: everything): a live beam offers only chars in it, a carry is not masked."""
     W, V = lp.shape
     dt = lp.dtype
+    ok = np.ones(V, bool) if allowed is None else np.asarray(allowed, bool)
     cand = np.full((W, V), -np.inf, dt)
     off = np.zeros((W, V), bool)
     for b in range(W):
@@ -169,12 +171,13 @@ def select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced: int, eo
             st = LIVE
         if st == LIVE:
             if forced >= 0 and mut != "forced_unrestricted":
-                add = dt.type(0) if mut == "forced_lp_not_added" else lp[b, forced]
-                cand[b, forced] = score[b] + add
-                off[b, forced] = True
+                if ok[forced]:
+                    add = dt.type(0) if mut == "forced_lp_not_added" else lp[b, forced]
+                    cand[b, forced] = score[b] + add
+                    off[b, forced] = True
             else:
-                cand[b] = score[b] + lp[b]
-                off[b] = True
+                cand[b] = np.where(ok, score[b] + lp[b], dt.type(-np.inf))
+                off[b] = ok
         elif st == FIN and mut != "carry_dropped":
             cand[b, 0] = score[b]
             off[b, 0] = True
@@ -223,7 +226,8 @@ def _select_all(d: Out, f64: bool, mut: Optional[str] = None) -> Out:
             forced = int(d["prefix"][n, d["step"]])
             if forced >= V:
                 forced = 0
-        s = select(lp[n], d["score"][n * W:(n + 1) * W].astype(dt), d["state"][n * W:(n + 1) * W], forced, d["eos"], d["sos"], mut)
+        s = select(lp[n], d["score"][n * W:(n + 1) * W].astype(dt), d["state"][n * W:(n + 1) * W], forced, d["eos"], d["sos"], mut,
+                   None if d.get("allowed") is None else d["allowed"][n])      # "allowed": bool [N][V], optional
         for k in res:
             res[k].append(s[k])
         clear[n] = _clear(s["gaps"])
@@ -363,7 +367,8 @@ def case_model(c: TrajCase):
     return _models[key]
 
 
-def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64: bool, mut: Optional[str] = None) -> Out:
+def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64: bool, mut: Optional[str] = None,
+         cons: Optional[cpu_ref.Constraints] = None) -> Out:
     N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
     dt = torch.float64 if f64 else torch.float32
     npdt = np.float64 if f64 else np.float32
@@ -394,8 +399,10 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
         nstate, nntok = np.zeros_like(state), np.zeros_like(ntok)
         nxt = np.full(N * W, cfg.sos, np.int64)
         step_top = []
+        ok_l = None if cons is None else cons.allowed(l)
         for n in range(N):
-            s = select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1, cfg.eos, cfg.sos, mut)
+            s = select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1, cfg.eos, cfg.sos, mut,
+                       None if cons is None else ok_l[n])
             clear[n, l] = _clear(s["gaps"])
             step_top.append((s["sel"].copy(), s["score"].copy()))
             for k in range(W):
@@ -419,11 +426,13 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
     return dict(rows=rows, logp=score, n_tok=ntok, n_beams=(state != DEAD).sum(1).astype(np.int32), clear=clear, tops=tops)
 
 
-def oracle(params, cfg: GRUConfig, prefixes, W: int) -> Out:
+def oracle(params, cfg: GRUConfig, prefixes, W: int, constraints=None) -> Out:
     """The float64 trajectory: rows, logp, n_tok, n_beams, ``clear`` [N][ML] and ``settled`` [N] (every
-    step's clearance at least GUARD)."""
+    step's clearance at least GUARD).  ``constraints``: as cpu_ref.beam_search's."""
     pre, plen = cpu_ref.beam_inputs(cfg, list(prefixes), W)
-    out = _run(params, cfg, pre, plen, W, True)
+    cons = cpu_ref.as_constraints(cfg, pre.shape[0], constraints)
+    cpu_ref.check_prefix_allowed(cons, pre, plen)
+    out = _run(params, cfg, pre, plen, W, True, cons=cons)
     out["settled"] = out["clear"].min(1) >= GUARD
     return out
 

@@ -375,19 +375,262 @@ def make_controls(cfg: GRUConfig, count: int, temperature=None, top_k=None, top_
     return Controls(inv, k, p32, plen, rows)
 
 
-def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray):
-    """Steps 2-7 on logits x [N, V] with Controls arrays of N entries -> (probs [N, V], keep [N, V])."""
+# Constraints (docs/DESIGN.md §4e): one more set definition in both rules.  Name n at step l has an
+# allowed set A = line idx[n, l] of a table of bit masks (bit c % 32 of word c / 32 = char c); line 0 is
+# "everything", so constrained and free names mix in one batch.
+#   sampling (steps 2-7 above): y_i = -inf outside A, applied after the temperature scale.  Greedy is
+#     the lowest index of the maximum over A; top-k keeps i iff i in A and #{j in A : y_j > y_i} < k (a
+#     set smaller than k is kept whole, nothing outside A ever); softmax and top-p run over the kept
+#     set; a masked char has probability exactly 0; the fallback is the highest kept index, inside A.
+#     A forced step is unchanged.  With A = everything every operation and its order is the one above.
+#   beam (step 3 below): a live beam offers c only if c is in A (and, while l < plen, only prefix[l]);
+#     carries are not masked; scores stay the model's un-renormalised log-probabilities.
+# The forced prefix is the special case of singleton sets.
+CONSTRAINT_MAX_ROWS = 1024
+
+
+class Constraints:
+    """Per-position allowed sets of ``count`` names: tab uint32 [M, V/32] (line 0 all ones, lines
+    distinct, M <= 1024), idx int32 [count, max_len].  (A vocabulary that is no multiple of 32 -- CPU
+    only -- rounds the words up; the spare bits are 0.)"""
+
+    def __init__(self, tab: np.ndarray, idx: np.ndarray, vocab: Optional[int] = None):
+        self.tab, self.idx = tab, idx
+        self.vocab = int(tab.shape[1]) * 32 if vocab is None else int(vocab)
+
+    @property
+    def rows(self) -> int:
+        return int(self.tab.shape[0])
+
+    def lines(self) -> np.ndarray:
+        """The table as bool [M, V]."""
+        bits = (self.tab[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+        return bits.reshape(self.tab.shape[0], -1).astype(bool)[:, :self.vocab]
+
+    def allowed(self, step: Optional[int] = None) -> np.ndarray:
+        """bool [count, V] of a step, or [count, max_len, V] of all."""
+        ln = self.lines()
+        return ln[self.idx] if step is None else ln[self.idx[:, step]]
+
+    def slice(self, start: int, count: int) -> "Constraints":
+        """Names start .. start + count - 1 (the table is shared)."""
+        return Constraints(self.tab, np.ascontiguousarray(self.idx[start:start + count]), self.vocab)
+
+
+def _as_bytes(v, what: str) -> bytes:
+    try:
+        return v.encode("latin-1") if isinstance(v, str) else bytes(v)
+    except UnicodeEncodeError as e:
+        raise ValueError(f"{what} {v!r} is not latin-1") from e
+
+
+def _parse_pattern(pat: bytes, cfg: GRUConfig, cs: np.ndarray) -> List[np.ndarray]:
+    """One bool [V] set per pattern item.  cs: the charset as bool [V]."""
+    V = cfg.vocab
+    items = []
+
+    def one(c: int) -> np.ndarray:
+        if c >= V:
+            raise ValueError(f"pattern {pat!r} names byte {c} >= vocab ({V})")
+        if c == cfg.eos:
+            raise ValueError(f"pattern {pat!r} names the EOS byte {cfg.eos} (lengths are set by min_len / max_len)")
+        s = np.zeros(V, bool)
+        s[c] = True
+        return s
+
+    i, n = 0, len(pat)
+    while i < n:
+        c = pat[i]
+        if c == 0x5C:                                   # backslash: the next char, literally
+            if i + 1 >= n:
+                raise ValueError(f"pattern {pat!r} ends in a backslash")
+            items.append(one(pat[i + 1]))
+            i += 2
+        elif c == 0x2E:                                 # .
+            items.append(cs.copy())
+            i += 1
+        elif c == 0x5B:                                 # [ ... ]
+            i += 1
+            neg = i < n and pat[i] == 0x5E
+            if neg:
+                i += 1
+            s = np.zeros(V, bool)
+            members = 0
+            while True:
+                if i >= n:
+                    raise ValueError(f"pattern {pat!r}: a class without its ']'")
+                if pat[i] == 0x5D:
+                    i += 1
+                    break
+                if pat[i] == 0x5C:
+                    if i + 1 >= n:
+                        raise ValueError(f"pattern {pat!r} ends in a backslash")
+                    i += 1
+                lo = pat[i]
+                i += 1
+                hi = lo
+                if i + 1 < n and pat[i] == 0x2D and pat[i + 1] != 0x5D:   # a-z
+                    i += 1
+                    if pat[i] == 0x5C:
+                        if i + 1 >= n:
+                            raise ValueError(f"pattern {pat!r} ends in a backslash")
+                        i += 1
+                    hi = pat[i]
+                    i += 1
+                    if hi < lo:
+                        raise ValueError(f"pattern {pat!r}: range {chr(lo)}-{chr(hi)} runs backwards")
+                for ch in range(lo, hi + 1):
+                    s |= one(ch)
+                members += 1
+            if not members:
+                raise ValueError(f"pattern {pat!r}: an empty class")
+            items.append(cs & ~s if neg else s)
+        elif c == 0x5D:
+            raise ValueError(f"pattern {pat!r}: a ']' without its class (write \\])")
+        else:
+            items.append(one(c))
+            i += 1
+    return items
+
+
+def _name_sets(cfg: GRUConfig, pattern, charset, min_len, max_len) -> np.ndarray:
+    """bool [max_len, V]: the allowed set of every step of one name (all ones = no constraint)."""
+    ML, V, eos = cfg.max_len, cfg.vocab, cfg.eos
+    if not 0 <= eos < V:
+        raise ValueError(f"eos {eos} outside the vocabulary of {V}")
+    cs = np.ones(V, bool)
+    if charset is not None:
+        b = np.frombuffer(_as_bytes(charset, "charset"), dtype=np.uint8)
+        if (b >= V).any():
+            raise ValueError(f"charset names a byte >= vocab ({V})")
+        if (b == eos).any():
+            raise ValueError(f"charset names the EOS byte {eos} (lengths are set by min_len / max_len)")
+        cs[:] = False
+        cs[b] = True
+    cs[eos] = False
+    items = [] if pattern is None else _parse_pattern(_as_bytes(pattern, "pattern"), cfg, cs)
+    if len(items) > ML:
+        raise ValueError(f"pattern {pattern!r} has {len(items)} items, more than max_len = {ML}")
+    lo = max(0 if min_len is None else int(min_len), len(items))
+    hi = ML if max_len is None else int(max_len)
+    if (min_len is not None and int(min_len) < 0) or hi < 0 or hi > ML:
+        raise ValueError(f"min_len >= 0 and 0 <= max_len <= {ML} expected, got {min_len!r} and {max_len!r}")
+    free = pattern is None and charset is None and lo == 0 and hi == ML
+    sets = np.ones((ML, V), bool)
+    for l in range(ML):
+        if free or l > hi:       # past the forced EOS no step is reached: no constraint
+            continue
+        if l == hi:              # (hi < ML) only EOS: the name has at most hi chars
+            s = np.zeros(V, bool)
+        else:
+            s = items[l].copy() if l < len(items) else cs.copy()
+        s[eos] = l >= lo
+        if not s.any():
+            raise ValueError(f"no char is allowed at step {l} (pattern {pattern!r}, charset {charset!r}, "
+                             f"min_len {lo}, max_len {hi})")
+        sets[l] = s
+    return sets
+
+
+def _per_name_obj(v, n: int, what: str) -> list:
+    if v is None or isinstance(v, (str, bytes)) or np.ndim(v) == 0:
+        return [v] * n
+    if len(v) != n:
+        raise ValueError(f"{what}: one value or {n} values expected, got {len(v)}")
+    return list(v)
+
+
+def make_constraints(cfg: GRUConfig, count: int, pattern=None, charset=None, min_len=None, max_len=None) -> Constraints:
+    """Each argument: one value for all ``count`` names or one per name (None: no such constraint).
+    ``charset``: the non-EOS chars a name may use (str / bytes; default every char but EOS).  ``pattern``:
+    one item per position, no quantifiers -- a literal char, ``\\`` + a literal char, ``.`` (any char of
+    charset), ``[abc]`` / ``[a-z]`` / ``[^...]`` classes (a negated class is taken inside charset); P items
+    imply min_len >= P and positions past the pattern follow charset.  ``min_len`` = m: no EOS at steps
+    < m.  ``max_len`` = M <= cfg.max_len: only EOS at step M (when M < cfg.max_len).  ValueError for an
+    empty allowed set at any step, a byte >= vocab, a malformed or too long pattern, and more than 1024
+    distinct sets."""
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    ML, V = cfg.max_len, cfg.vocab
+    cols = [_per_name_obj(v, count, w) for v, w in ((pattern, "pattern"), (charset, "charset"),
+                                                    (min_len, "min_len"), (max_len, "max_len"))]
+    if count == 0:   # still validate single values
+        _name_sets(cfg, *[None if v is not None and not isinstance(v, (str, bytes)) and np.ndim(v) else v
+                          for v in (pattern, charset, min_len, max_len)])
+    lines: Dict[bytes, int] = {np.ones(V, bool).tobytes(): 0}
+    per_name: Dict[tuple, np.ndarray] = {}
+    idx = np.zeros((count, ML), np.int32)
+    for n in range(count):
+        key = tuple(None if v is None else (_as_bytes(v, "pattern / charset") if isinstance(v, (str, bytes)) else int(v))
+                    for v in (cols[0][n], cols[1][n], cols[2][n], cols[3][n]))
+        row = per_name.get(key)
+        if row is None:
+            sets = _name_sets(cfg, *key)
+            row = np.zeros(ML, np.int32)
+            for l in range(ML):
+                row[l] = lines.setdefault(sets[l].tobytes(), len(lines))
+            per_name[key] = row
+        idx[n] = row
+    if len(lines) > CONSTRAINT_MAX_ROWS:
+        raise ValueError(f"{len(lines)} distinct allowed sets, more than {CONSTRAINT_MAX_ROWS}")
+    bits = np.stack([np.frombuffer(k, dtype=bool) for k in lines])            # insertion order = line number
+    words = -(-V // 32)
+    bits = np.concatenate([bits, np.zeros((len(lines), words * 32 - V), bool)], 1)
+    w = (bits.reshape(len(lines), words, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)
+    return Constraints(np.ascontiguousarray(w.astype(np.uint32)), idx, V)
+
+
+def as_constraints(cfg: GRUConfig, count: int, constraints) -> Optional[Constraints]:
+    """None, a Constraints object for ``count`` names, or a dict of make_constraints keywords."""
+    if constraints is None or isinstance(constraints, Constraints):
+        c = constraints
+    elif isinstance(constraints, dict):
+        c = make_constraints(cfg, count, **constraints)
+    else:
+        raise ValueError("constraints: a Constraints object or a dict of make_constraints keywords expected")
+    if c is not None:
+        if (c.idx.shape != (count, cfg.max_len) or c.tab.ndim != 2 or c.tab.shape[1] != -(-cfg.vocab // 32)
+                or c.vocab != cfg.vocab):
+            raise ValueError(f"constraints: idx [{count}, {cfg.max_len}] and tab [M, {-(-cfg.vocab // 32)}] for a vocabulary "
+                             f"of {cfg.vocab} expected, got {c.idx.shape}, {c.tab.shape} and {c.vocab}")
+        if not 1 <= c.rows <= CONSTRAINT_MAX_ROWS:
+            raise ValueError(f"constraints: 1 .. {CONSTRAINT_MAX_ROWS} table lines expected, got {c.rows}")
+        if c.idx.size and (c.idx.min() < 0 or c.idx.max() >= c.rows):
+            raise ValueError("constraints: an idx entry outside the table")
+    return c
+
+
+def check_prefix_allowed(cons: Optional[Constraints], prefix: np.ndarray, plen: np.ndarray) -> None:
+    """ValueError when a forced char is not in its step's set."""
+    if cons is None or not len(plen) or not plen.any():
+        return
+    ML = prefix.shape[1]
+    ok = np.take_along_axis(cons.allowed(), prefix.astype(np.int64)[:, :, None], 2)[:, :, 0]
+    bad = (np.arange(ML)[None, :] < plen[:, None]) & ~ok
+    if bad.any():
+        n, l = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f"prefix {n}: char {int(prefix[n, l])} at position {l} is not allowed by the constraint")
+
+
+def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray,
+            allowed: Optional[np.ndarray] = None):
+    """Steps 2-7 on logits x [N, V] with Controls arrays of N entries (and the rows' allowed sets, bool
+    [N, V], None: everything) -> (probs [N, V], keep [N, V])."""
     N, V = x.shape
     dt = x.dtype
     inv_t = torch.from_numpy(inv)
     greedy = inv_t == 0
     y = x * torch.where(greedy, torch.ones_like(inv_t), inv_t).to(dt).unsqueeze(-1)
     keep = torch.ones(N, V, dtype=torch.bool)
+    if allowed is not None:
+        keep = torch.from_numpy(np.array(allowed, dtype=bool)).reshape(N, V)
+        y = torch.where(keep, y, torch.full_like(y, -math.inf))
     k = torch.from_numpy(top_k.astype(np.int64))
     kact = (k > 0) & (k < V)
     if kact.any():   # y_i >= the k-th largest value  <=>  fewer than k values above y_i
         kth = torch.sort(y, -1, descending=True).values.gather(-1, (k.clamp(1, V) - 1).unsqueeze(-1))
-        keep = torch.where(kact.unsqueeze(-1), y >= kth, keep)
+        keep = torch.where(kact.unsqueeze(-1), (y >= kth) & keep, keep)   # (& keep: a set smaller than k)
     ninf = torch.full_like(y, -math.inf)
     p = torch.from_numpy(top_p).to(dt)
     pact = p < 1
@@ -405,20 +648,34 @@ def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarr
     return torch.softmax(torch.where(keep, y, ninf), -1), keep
 
 
-def filter_probs(logits: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0) -> torch.Tensor:
+def filter_probs(logits: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0, allowed=None) -> torch.Tensor:
     """The distribution step 7 samples from: logits [N, V] (or [V]) in fp32 or fp64 (fp64: the oracle),
-    the controls scalars or N values.  T == 0 gives the one-hot row of the lowest arg-max."""
+    the controls scalars or N values.  T == 0 gives the one-hot row of the lowest arg-max.  ``allowed``:
+    bool [N, V] (or [V]), the rows' allowed sets (None: everything)."""
     x = logits.unsqueeze(0) if logits.dim() == 1 else logits
     c = make_controls(GRUConfig(vocab=x.shape[-1]), x.shape[0], temperature, top_k, top_p)
-    probs, _ = _filter(x, c.inv_temp, c.top_k, c.top_p)
+    probs, _ = _filter(x, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, x.shape))
     return probs[0] if logits.dim() == 1 else probs
 
 
+def _allowed_rows(allowed, shape) -> Optional[np.ndarray]:
+    if allowed is None:
+        return None
+    a = np.asarray(allowed, dtype=bool)
+    a = np.broadcast_to(a, shape) if a.ndim == 1 else a
+    if a.shape != tuple(shape):
+        raise ValueError(f"allowed: bool {tuple(shape)} expected, got {a.shape}")
+    if not a.any(-1).all():
+        raise ValueError("allowed: a row with an empty set")
+    return a
+
+
 def sample_controlled(logits: torch.Tensor, r: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0,
-                      controls: Optional[Controls] = None) -> torch.Tensor:
-    """Steps 2-7: logits [N, V], uniforms r [N] -> chosen index [N] (int64)."""
+                      controls: Optional[Controls] = None, allowed=None) -> torch.Tensor:
+    """Steps 2-7: logits [N, V], uniforms r [N] (and the rows' allowed sets, bool [N, V]) -> chosen index
+    [N] (int64)."""
     c = controls or make_controls(GRUConfig(vocab=logits.shape[-1]), logits.shape[0], temperature, top_k, top_p)
-    probs, keep = _filter(logits, c.inv_temp, c.top_k, c.top_p)
+    probs, keep = _filter(logits, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, logits.shape))
     V = probs.shape[-1]
     cs = torch.empty_like(probs)
     acc = torch.zeros_like(probs[..., 0])
@@ -432,7 +689,8 @@ def sample_controlled(logits: torch.Tensor, r: torch.Tensor, temperature=1.0, to
 
 
 def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0,
-             count: Optional[int] = None, temperature=None, top_k=None, top_p=None, prefix=None) -> np.ndarray:
+             count: Optional[int] = None, temperature=None, top_k=None, top_p=None, prefix=None,
+             constraints=None) -> np.ndarray:
     """Batched version of the reference's per-name loop (namegensf.cu:649-884).
 
     Names ``start .. start+count-1`` of the global job; name n at step l consumes
@@ -443,13 +701,18 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
 
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (see ``make_controls``; scalars or one value per
     generated name, i.e. ``count`` entries): any that is not None takes the controlled sampler above
-    (neutral values give the plain path's bytes).  fp64 params give the oracle."""
+    (neutral values give the plain path's bytes).  ``constraints``: a Constraints object for the ``count``
+    names or a dict of ``make_constraints`` keywords; it takes the controlled sampler too, inside each
+    step's allowed set (a table of only line 0 gives the unconstrained bytes).  fp64 params give the
+    oracle."""
     ML = cfg.max_len
     N = (rfloats.size // ML - start) if count is None else count
     out = np.zeros((N, ML + 1), dtype=np.uint8)
     ctl = None
-    if any(v is not None for v in (temperature, top_k, top_p, prefix)):
+    cons = as_constraints(cfg, max(N, 0), constraints)
+    if cons is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
         ctl = make_controls(cfg, max(N, 0), temperature, top_k, top_p, prefix)
+        check_prefix_allowed(cons, ctl.prefix, ctl.plen)
     if N <= 0:
         return out
     H = cfg.hidden
@@ -472,7 +735,8 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
             prob = torch.softmax(logits, -1)
             sel = sample_inverse_cdf(prob, rf[:, l].to(prob.dtype))
         else:
-            sel = sample_controlled(logits, rf[:, l], controls=ctl)
+            sel = sample_controlled(logits, rf[:, l], controls=ctl,
+                                    allowed=None if cons is None else cons.allowed(l))
             forced = torch.from_numpy(ctl.plen > l)
             sel = torch.where(forced, torch.from_numpy(ctl.prefix[:, l].astype(np.int64)), sel)
         out[alive.numpy(), l] = sel[alive].numpy().astype(np.uint8)
@@ -546,20 +810,24 @@ def beam_inputs(cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int
     return rows, plen
 
 
-def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_char: int = -1):
+def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_char: int = -1, allowed=None):
     """Steps 3-4 for one name: lp [W, V], score [W], state [W] -> the W new beams in order as (parent,
-    chr, score, j), parent -1 for a dead slot, chr -1 for a carry or a dead slot."""
+    chr, score, j), parent -1 for a dead slot, chr -1 for a carry or a dead slot.  ``allowed``: bool [V],
+    the name's set at this step (None: everything): a live beam offers only chars in it, carries are
+    not masked."""
     W, V = lp.shape
     cand = np.full((W, V), -np.inf, dtype=lp.dtype)
     offered = np.zeros((W, V), dtype=bool)
+    ok = np.ones(V, bool) if allowed is None else np.asarray(allowed, dtype=bool)
     for b in range(W):
         if state[b] == BEAM_LIVE:
             if forced_char >= 0:
-                cand[b, forced_char] = score[b] + lp[b, forced_char]
-                offered[b, forced_char] = True
+                if ok[forced_char]:
+                    cand[b, forced_char] = score[b] + lp[b, forced_char]
+                    offered[b, forced_char] = True
             else:
-                cand[b] = score[b] + lp[b]
-                offered[b] = True
+                cand[b] = np.where(ok, score[b] + lp[b], -np.inf)
+                offered[b] = ok
         elif state[b] == BEAM_FIN:
             cand[b, 0] = score[b]
             offered[b, 0] = True
@@ -575,10 +843,23 @@ def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_cha
     return out
 
 
-def beam_search(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None) -> BeamResult:
-    """The rule above in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli beam``)."""
+def beam_search(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None,
+                constraints=None) -> BeamResult:
+    """The rule above in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli beam``).
+    ``constraints``: a Constraints object for the N prefixes or a dict of ``make_constraints`` keywords:
+    the W most probable names that satisfy it."""
     pre, plen = beam_inputs(cfg, prefix, width, count)
-    N, W, ML, V, H = pre.shape[0], int(width), cfg.max_len, cfg.vocab, cfg.hidden
+    cons = as_constraints(cfg, pre.shape[0], constraints)
+    check_prefix_allowed(cons, pre, plen)
+    return beam_search_rule(params, cfg, pre, plen, int(width), cons)
+
+
+def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int,
+                     cons: Optional[Constraints] = None) -> BeamResult:
+    """The rule itself on validated inputs (``beam_inputs`` / ``as_constraints``).  It has no width limit
+    of its own -- the limits of ``beam_inputs`` are the device's -- so a width that holds every candidate
+    makes the search exhaustive (tests/test_constraints.py)."""
+    N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
     dt = params["fc.weight"].dtype
     npdt = np.float64 if dt == torch.float64 else np.float32
     rows = np.zeros((N, W, ML + 1), np.uint8)
@@ -606,7 +887,8 @@ def beam_search(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, cou
         nrows, nscore, nstate, nntok = np.zeros_like(rows), np.full_like(score, -np.inf), np.zeros_like(state), np.zeros_like(ntok)
         nxt = np.full(N * W, cfg.sos, np.int64)
         for n in range(N):
-            sel = beam_select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1)
+            sel = beam_select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1,
+                              None if cons is None else cons.allowed(l)[n])
             for k, (b, c, s, _) in enumerate(sel):
                 if b < 0:
                     continue
