@@ -4,6 +4,7 @@
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --seed 1
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 20 --prefix Mar --temperature 0.8 --top-k 40 --top-p 0.95
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt
+    python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt --temperature 0.8 --top-k 40 --pattern '[A-Z]'
     python -m gru_mpi_cuda_amd.cli beam     --ckpt out/model.bin --width 5 --prefix Mar
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
@@ -274,7 +275,9 @@ def _read_names(path: str) -> list:
 
 def cmd_score(args) -> int:
     """Teacher-forced log-likelihood of names under a checkpoint: one `name<TAB>logp<TAB>n_tok` line
-    per name, a JSON summary on stderr."""
+    per name, a JSON summary on stderr.  With any of `generate`'s sampling flags logp is the
+    log-probability that `generate` with the same flags emits the name: `-inf` for a name it cannot
+    emit, counted as `impossible` in the summary (docs/DESIGN.md §4f)."""
     import torch
     from .engine import generator as G
     from .models import cpu_ref
@@ -293,12 +296,25 @@ def cmd_score(args) -> int:
         rows = raw.reshape(-1, ML + 1)
     else:
         rows = G.encode_names(_read_names(args.names), cfg)
+    # the sampler's settings (generate's flags): the rows are scored under the distribution it draws from
+    ctl = {key: getattr(args, key) for key in ("temperature", "top_k", "top_p") if getattr(args, key) is not None}
+    if args.prefix is not None and args.prefix_file is not None:
+        raise SystemExit("--prefix and --prefix-file exclude each other")
+    if args.prefix is not None:
+        ctl["prefix"] = args.prefix
+    elif args.prefix_file is not None:
+        pres = _read_names(args.prefix_file)
+        if not pres:
+            raise SystemExit(f"{args.prefix_file}: no prefixes")
+        ctl["prefix"] = [pres[i % len(pres)] for i in range(rows.shape[0])]   # cycled over the rows, as generate does
+    if _constraints_from(args) is not None:
+        ctl["constraints"] = _constraints_from(args)
     t0 = time.perf_counter()
     if args.cpu or not torch.cuda.is_available():
-        tok, name, n_tok, rank = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows)
-        res = G.ScoreResult(tok, rank, name, n_tok)
+        out = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows, **ctl)
+        res = G.ScoreResult(out[0], out[3], out[1], out[2], out[4] if ctl else None)
     else:
-        res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0]))).score(rows)
+        res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0]))).score(rows, **ctl)
     dt = time.perf_counter() - t0
     lines = []
     for r, lp, nt in zip(rows, res.name_logp, res.n_tok):
@@ -312,7 +328,8 @@ def cmd_score(args) -> int:
     else:
         sys.stdout.write(text)
     print(json.dumps({"names": int(rows.shape[0]), "tokens": res.tokens, "nll_per_char": res.nll_per_char,
-                      "perplexity": res.perplexity, "top1": res.top1, "seconds": round(dt, 4)}), file=sys.stderr)
+                      "perplexity": res.perplexity, "top1": res.top1, "impossible": res.impossible,
+                      "seconds": round(dt, 4)}), file=sys.stderr)
     return 0
 
 
@@ -416,6 +433,15 @@ def main(argv=None) -> int:
     src.add_argument("--raw", default=None, help="raw N x (MAX_LEN+1) bytes, as `generate --raw-out` writes")
     sc.add_argument("--out", default=None, help="name, log-prob and token count per line, tab-separated")
     sc.add_argument("--cpu", action="store_true", help="cpu_ref.score in fp32 instead of the HIP generator")
+    sc.add_argument("--temperature", type=float, default=None,
+                    help="score under the sampler: `generate`'s temperature T >= 0 (0: greedy).  With any of these "
+                         "flags logp is the log-probability that `generate` with the same flags emits the name "
+                         "(-inf: it cannot)")
+    sc.add_argument("--top-k", dest="top_k", type=int, default=None, help="`generate`'s --top-k (0: off)")
+    sc.add_argument("--top-p", dest="top_p", type=float, default=None, help="`generate`'s --top-p, in (0, 1] (1: off)")
+    sc.add_argument("--prefix", default=None, help="`generate`'s --prefix: every name is forced to start with these chars")
+    sc.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line, cycled over the names")
+    _constraint_args(sc)
     sc.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(sc)
     g = sub.add_parser("generate", help="namegen_initialize / namegen / namegen_finalize")

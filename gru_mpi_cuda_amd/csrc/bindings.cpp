@@ -222,11 +222,23 @@ PYBIND11_MODULE(_C, m) {
       .def("ctl_workspace_bytes", &Generator::ctl_workspace_bytes)
       .def("ctl_graphs", &Generator::ctl_graphs)
       .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
-                       uintptr_t n_tok, uintptr_t s) {
+                       uintptr_t n_tok, uintptr_t s, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p, uintptr_t plen,
+                       uintptr_t prefix, uintptr_t n_kept, uintptr_t allow_tab, uintptr_t allow_idx, int allow_rows) {
+        // inv_temp set: the controlled score (every control array and n_kept are then required)
+        Generator::Ctl c;
+        c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
+        c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
+        c.allow_tab = Pp<const unsigned>(allow_tab); c.allow_idx = Pp<const int>(allow_idx); c.allow_rows = allow_rows;
+        const bool ctl = inv_temp || top_k || top_p || plen || prefix || n_kept || allow_tab || allow_idx;
         g.score(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
-                Pp<int>(n_tok), S(s));
-      })
+                Pp<int>(n_tok), S(s), ctl ? &c : nullptr, Pp<int>(n_kept));
+      }, py::arg("rows"), py::arg("N"), py::arg("tok_logp"), py::arg("rank"), py::arg("name_logp"), py::arg("n_tok"),
+         py::arg("stream"), py::arg("inv_temp") = (uintptr_t)0, py::arg("top_k") = (uintptr_t)0,
+         py::arg("top_p") = (uintptr_t)0, py::arg("plen") = (uintptr_t)0, py::arg("prefix") = (uintptr_t)0,
+         py::arg("n_kept") = (uintptr_t)0, py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
+         py::arg("allow_rows") = 0)
       .def("score_workspace_bytes", &Generator::score_workspace_bytes)
+      .def("score_graphs", &Generator::score_graphs)
       .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
                       uintptr_t n_tok, uintptr_t n_beams, uintptr_t s, uintptr_t allow_tab, uintptr_t allow_idx,
                       int allow_rows) {
@@ -857,6 +869,25 @@ PYBIND11_MODULE(_C, m) {
     if (!a.logits || !a.tgt || !a.ntok || !a.tok_logp || !a.rank || !a.name_logp || !a.ntok_out)
       throw std::runtime_error("score_logprob: logits, tgt, ntok, tok_logp, rank, name_logp, ntok_out required");
     score_logprob_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // score_logprob under the sampler's controls and constraints (tests/test_score_ctl_gpu.py)
+  m.def("score_ctl_logprob", [](py::dict d, uintptr_t s) {
+    ScoreCtlArgs c;
+    ScoreLogprobArgs& a = c.s;
+    a.logits = GP(const float, d, "logits"); a.splits = get<int>(d, "splits", 1); a.slab = get<long>(d, "slab", 0);
+    a.bias = GP(const float, d, "bias"); a.tgt = GP(const int, d, "tgt"); a.ntok = GP(const int, d, "ntok");
+    a.tok_logp = GP(float, d, "tok_logp"); a.rank = GP(int, d, "rank"); a.name_logp = GP(float, d, "name_logp");
+    a.ntok_out = GP(int, d, "ntok_out");
+    a.Bp = get<int>(d, "Bp", 0); a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0);
+    if (!a.logits || !a.tgt || !a.ntok || !a.tok_logp || !a.rank || !a.name_logp || !a.ntok_out)
+      throw std::runtime_error("score_ctl_logprob: logits, tgt, ntok, tok_logp, rank, name_logp, ntok_out required");
+    c.inv_temp = GP(const float, d, "inv_temp"); c.top_k = GP(const int, d, "top_k");
+    c.top_p = GP(const float, d, "top_p"); c.plen = GP(const int, d, "plen");
+    c.prefix = GP(const unsigned char, d, "prefix"); c.row0 = get<int>(d, "row0", 0); c.err = GP(unsigned, d, "err");
+    c.allow_tab = GP(const unsigned, d, "allow_tab"); c.allow_idx = GP(const int, d, "allow_idx");
+    c.allow_rows = get<int>(d, "allow_rows", 0); c.n_kept = GP(int, d, "n_kept");
+    score_ctl_logprob_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
   // the beam search's kernels on caller-owned buffers (tests/test_beam_gpu.py)

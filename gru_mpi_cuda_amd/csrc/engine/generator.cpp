@@ -83,6 +83,7 @@ bool Generator::uses_persist_ctl(int n) const {
 Generator::~Generator() {
   graphs_.clear();
   sgraphs_.clear();
+  scgraphs_.clear();
   cgraphs_.clear();
   bgraphs_.clear();
   if (cap_) (void)hipStreamDestroy(cap_);
@@ -458,9 +459,25 @@ void Generator::score_alloc() {
   sready_ = true;
 }
 
+// The current batch's controls, its constraint lines, the call's table and the staged n_kept, sized for
+// Bmax_ names: a generator that never scores with controls never allocates them.
+void Generator::score_ctl_alloc() {
+  if (scready_) return;
+  const size_t B = Bmax_, ML = d_.max_len;
+  const size_t oi = scarena_.reserve(B * 4), ok = scarena_.reserve(B * 4), op = scarena_.reserve(B * 4);
+  const size_t ol = scarena_.reserve(B * 4), opre = scarena_.reserve(B * ML);
+  const size_t otab = scarena_.reserve((size_t)kAllowRows * (d_.V / 32) * 4), oidx = scarena_.reserve(B * ML * 4);
+  const size_t onk = scarena_.reserve(B * ML * 4);
+  scarena_.commit();
+  scinv_ = scarena_.get<float>(oi); sctopk_ = scarena_.get<int>(ok); sctopp_ = scarena_.get<float>(op);
+  scplen_ = scarena_.get<int>(ol); scprefix_ = scarena_.get<unsigned char>(opre);
+  sctab_ = scarena_.get<unsigned>(otab); scidx_ = scarena_.get<int>(oidx); snkept_ = scarena_.get<int>(onk);
+  scready_ = true;
+}
+
 // The schedule for a padded batch of Bp rows (the name count is read from sn_ by score_prep, so one
 // recording serves every count that pads to Bp): 2 L ML + L + 2 launches, a single chain.
-void Generator::record_score(int Bp, hipStream_t s) {
+void Generator::record_score(int Bp, hipStream_t s, bool ctl, int allow_rows) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int cap = std::max(Bmax_, kF32SlabRows);
   ScorePrepArgs p;
@@ -501,40 +518,73 @@ void Generator::record_score(int Bp, hipStream_t s) {
   q.logits = slogits_; q.splits = g.splits; q.slab = g.slab; q.tgt = stgt_; q.ntok = sntok_;
   q.tok_logp = stok_; q.rank = srank_; q.name_logp = sname_; q.ntok_out = sntok_out_;
   q.Bp = Bp; q.V = V; q.ML = ML;
-  score_logprob_f32(q, s);
+  if (ctl) {   // the controls of rows 0 .. Bp - 1 of the staging buffers (pad rows read none)
+    ScoreCtlArgs c;
+    c.s = q; c.inv_temp = scinv_; c.top_k = sctopk_; c.top_p = sctopp_; c.plen = scplen_; c.prefix = scprefix_;
+    c.row0 = 0; c.err = err_; c.n_kept = snkept_;
+    if (allow_rows > 0) { c.allow_tab = sctab_; c.allow_idx = scidx_; c.allow_rows = allow_rows; }
+    score_ctl_logprob_f32(c, s);
+  } else {
+    score_logprob_f32(q, s);
+  }
   HIP_LAUNCH_CHECK();
 }
 
 void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok,
-                      hipStream_t s) {
+                      hipStream_t s, const Ctl* c, int* n_kept) {
   GK_TRACE("gk.score");
+  const bool masked = c && c->allow_tab != nullptr;
+  if (c) {
+    if (!c->inv_temp || !c->top_k || !c->top_p || !c->plen || !c->prefix || !n_kept)
+      throw std::runtime_error("Generator::score: a controlled score needs every control array and n_kept");
+    if (masked != (c->allow_idx != nullptr) || (masked && (c->allow_rows < 1 || c->allow_rows > kAllowRows)))
+      throw std::runtime_error("Generator::score: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
+    if (masked && 32 % (d_.V / 64))
+      throw std::runtime_error("Generator::score: constraints need vocab / 64 in {1, 2, 4, 8}");
+  }
   if (N <= 0) return;
   const int ML = d_.max_len;
   if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::score needs max_len <= 64 and vocab <= 512");
   score_alloc();   // first call: allocates (and synchronises) before anything is captured
+  if (c) score_ctl_alloc();   // ... the first controlled one its control buffers
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
+  const int ar = masked ? c->allow_rows : 0;
+  if (masked)   // the table once per call
+    HIP_CHECK(hipMemcpyAsync(sctab_, c->allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
     const int Bp = rup(n, 64);
     score_set_count(sn_, n, s);
     HIP_CHECK(hipMemcpyAsync(srows_, rows + (size_t)start * (ML + 1), (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+    if (c) {   // this batch's slice of every control array: the recording reads rows 0 .. n - 1 of the buffers
+      HIP_CHECK(hipMemcpyAsync(scinv_, c->inv_temp + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(sctopk_, c->top_k + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(sctopp_, c->top_p + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(scplen_, c->plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(scprefix_, c->prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+      if (masked)
+        HIP_CHECK(hipMemcpyAsync(scidx_, c->allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    }
     if (use_graph_) {
-      auto& g = sgraphs_[Bp];
+      // an uncontrolled call: the graphs it had.  A controlled recording bakes the table's line count in
+      // (every entry is checked against it), so that is part of its key; 0 = unconstrained
+      auto& g = c ? scgraphs_[std::make_pair(Bp, ar)] : sgraphs_[Bp];
       if (!g) {
         g.reset(new Graph());
         g->begin(cap_);
-        record_score(Bp, cap_);
+        record_score(Bp, cap_, c != nullptr, ar);
         g->end(cap_);
       }
       g->launch(s);
     } else {
-      record_score(Bp, s);
+      record_score(Bp, s, c != nullptr, ar);
     }
     HIP_CHECK(hipMemcpyAsync(tok_logp + (size_t)start * ML, stok_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(rank + (size_t)start * ML, srank_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(name_logp + start, sname_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + start, sntok_out_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    if (c) HIP_CHECK(hipMemcpyAsync(n_kept + (size_t)start * ML, snkept_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

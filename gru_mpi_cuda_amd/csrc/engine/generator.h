@@ -64,8 +64,18 @@ class Generator {
   // arithmetic, whatever GenDims::fp32 says.  Layer-major schedule (the targets are known): per layer
   // ONE input-projection GEMM over all max_len * Bp rows, then its steps; ONE logits GEMM; one
   // log-prob launch.  Buffers are allocated on the first call.
-  void score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok, hipStream_t s);
-  size_t score_workspace_bytes() const { return sarena_.bytes(); }   // 0 until the first score()
+  // With controls (c: generate_ctl's arrays and constraints for the N names, device pointers; n_kept
+  // [N][max_len] then required; docs/DESIGN.md §4f): tok_logp is the log-probability under the sampler's
+  // distribution, score_ctl_logprob_f32 in place of the last launch -- score_prep, the products and
+  // the gates are the plain schedule's.  The controls live in an arena of their own, committed by the
+  // first controlled call; each batch's slice is copied there and the table once per call, so a
+  // recording bakes no value in: one per (Bp, table lines or 0).  c == nullptr is the call as it was,
+  // on the graphs it had.  Every precision mode scores with controls (scoring is exact fp32 always).
+  void score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok, hipStream_t s,
+             const Ctl* c = nullptr, int* n_kept = nullptr);
+  // 0 until the first score(); grows when the first controlled score() commits the control buffers
+  size_t score_workspace_bytes() const { return sarena_.bytes() + scarena_.bytes(); }
+  int score_graphs() const { return (int)(sgraphs_.size() + scgraphs_.size()); }   // recordings so far
   // Beam search (docs/DESIGN.md §4d; the rule: cpu_ref.beam_search): for each of N prefixes (device
   // plen [N], prefix [N][max_len], as generate_ctl's) the W most probable output rows in order:
   // rows [N][W][max_len+1], logp [N][W] (-inf for a dead slot), n_tok [N][W], n_beams [N], all device
@@ -122,7 +132,9 @@ class Generator {
   // and its error-word read-back.  false: the launch hit its spin limit -- the persistent path is now
   // off, the bit is cleared and the caller regenerates the batch on its per-char graph
   bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
-  void record_score(int Bp, hipStream_t s);
+  // ctl: score_ctl_logprob_f32 as the last launch; allow_rows > 0: with the constraint buffers
+  void record_score(int Bp, hipStream_t s, bool ctl = false, int allow_rows = 0);
+  void score_ctl_alloc();
   void beam_alloc();
   void record_beam(int n, int W, hipStream_t s, int allow_rows = 0);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
@@ -174,6 +186,16 @@ class Generator {
   float *sgh_ = nullptr, *sgi_ = nullptr, *slogits_ = nullptr;   // step product slabs, [ML*Bp][3H], [ML*Bp][V] slabs
   float *stok_ = nullptr, *sname_ = nullptr;    // staged outputs [Bmax][ML], [Bmax]
   int *srank_ = nullptr, *sntok_out_ = nullptr;
+  // scoring with controls (committed by the first controlled score() call)
+  Arena scarena_;
+  bool scready_ = false;
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> scgraphs_;   // keyed by (Bp, constraint table lines or 0)
+  float *scinv_ = nullptr, *sctopp_ = nullptr;  // [Bmax] each: the current batch's controls
+  int *sctopk_ = nullptr, *scplen_ = nullptr;
+  unsigned char* scprefix_ = nullptr;           // [Bmax][ML]
+  unsigned* sctab_ = nullptr;                   // [kAllowRows][V / 32] the call's constraint table
+  int* scidx_ = nullptr;                        // [Bmax][ML] the current batch's lines
+  int* snkept_ = nullptr;                       // staged output [Bmax][ML]
   // sampling controls (third arena, committed by the first generate_ctl() call)
   Arena carena_;
   bool cready_ = false;

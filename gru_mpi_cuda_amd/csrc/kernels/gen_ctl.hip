@@ -18,6 +18,8 @@
 // The persistent generator's controlled variants carry a second copy of this rule, ctl_sample_wave
 // (gen_sample_ctl.h), written for a kernel with no registers to spare: a change to one belongs in
 // the other (tests/test_sampling_ctl_gpu.py holds this one, tests/test_gen_persist_ctl_gpu.py that).
+// A third copy scores rows under this distribution: score_ctl_logprob_f32_kernel (score_ctl.hip,
+// tests/test_score_ctl_gpu.py).
 //
 // Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy has none): a row's
 // allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one

@@ -3,7 +3,8 @@
 // values per lane: the sampler of the persistent generator's controlled variants (gen_persist_ctl.hip).
 //
 // It is the rule of sample_ctl_f32_kernel (gen_ctl.hip), which stays the per-char graph's sampler: the
-// two copies sit side by side, and a change to one belongs in the other.  This one is written for a
+// two copies sit side by side, and a change to one belongs in the other (and in the scorer's copy of the
+// kept-set rule, score_ctl_logprob_f32_kernel in score_ctl.hip).  This one is written for a
 // kernel whose weights fill the register file: it keeps only y[PER] live (plus q[PER] during the top-p
 // search) where gen_ctl.hip keeps key[] / ex[] / keep[] as well.  A filtered entry is marked by
 // y = -inf, so its expf(y - mx) is exactly the 0 that gen_ctl.hip selects, and every expf / key is

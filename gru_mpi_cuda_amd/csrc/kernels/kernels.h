@@ -503,6 +503,31 @@ struct ScoreLogprobArgs {          // per token: log softmax(logits)[target] and
   int Bp = 0, V = 0, ML = 0;       // V % 64 == 0, V <= 512, ML <= 64
 };
 void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
+// score_logprob_f32 under the sampler's distribution (score_ctl.hip, docs/DESIGN.md §4f): tok_logp is
+// the log-probability that sample_ctl_f32 with the name's controls (row b + row0 of each array) and
+// allowed sets picks the target.  Step l < plen: 0 if the target is prefix[l], else -inf.  inv_temp == 0:
+// 0 if the target is the lowest index of the maximum over the allowed set, else -inf.  Else K = the kept
+// set of §4b steps 3-6 with §4e's mask, and tok_logp = (y_t - max_K y) - log sum_K exp(y_j - max_K y)
+// for a target in K, exactly -inf outside it; never NaN.  name_logp is the step-order sum (-inf
+// propagates), rank stays the model's rank on the raw logits, n_kept = |K| (1 on a forced or greedy step,
+// -1 at a masked position).  The constraint fields, their both-or-neither rule, the V / 64 in {1, 2, 4, 8}
+// restriction and the out-of-table entry (line 0, 16 into err[0], err[1] = the entry, err[2] = the row)
+// are SampleCtlArgs'.  A row with n_tok == 0 (a pad row) reads no control.
+struct ScoreCtlArgs {
+  ScoreLogprobArgs s;
+  const float* inv_temp = nullptr;         // [..]  1 / T, 0 for T == 0
+  const int* top_k = nullptr;              // [..]
+  const float* top_p = nullptr;            // [..]
+  const int* plen = nullptr;               // [..]  forced chars of the name, <= ML
+  const unsigned char* prefix = nullptr;   // [..][ML]
+  int row0 = 0;
+  unsigned* err = nullptr;                 // nullable
+  const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]
+  const int* allow_idx = nullptr;          // nullable [..][ML]
+  int allow_rows = 0;
+  int* n_kept = nullptr;                   // [Bp][ML]
+};
+void score_ctl_logprob_f32(const ScoreCtlArgs& c, hipStream_t s);
 
 // ------------------------------------------------------------------ beam search (beam.hip, docs/DESIGN.md §4d)
 // A name owns W ordered beams = rows n W .. n W + W - 1 of the batch.  Beam states: 0 dead (score

@@ -135,27 +135,55 @@ class HipGenerator:
         self.flat.copy_(to_flat(icfg, params).to(self.dev))
         self.g.refresh_weights(self._s())
 
-    def score(self, rows: np.ndarray) -> "ScoreResult":
+    def score(self, rows: np.ndarray, *, temperature=None, top_k=None, top_p=None, prefix=None,
+              constraints=None) -> "ScoreResult":
         """Teacher-forced log-likelihood of output rows ([N, MAX_LEN+1] or flat uint8, the format
         ``generate`` writes; semantics: cpu_ref.score_inputs).  Always exact fp32 arithmetic, whatever
         ``precision`` this generator samples with.  A byte >= vocab at a scored position raises
-        ValueError before anything is launched."""
+        ValueError before anything is launched.
+        ``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` / ``constraints`` (``generate``'s keywords, scalars
+        or one value per row; the rule: cpu_ref.score, docs/DESIGN.md §4f): any that is not None -- a neutral
+        value too -- scores the rows under the distribution ``generate`` samples from with these settings:
+        exp(name_logp) is the probability that it emits exactly that row, -inf marks a row it cannot emit,
+        and the result carries n_kept.  Every precision mode takes them.  Bad values raise ValueError
+        before anything is launched."""
         ML = self.cfg.max_len
+        ctl = cons = None
+        if constraints is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+            count = np.ascontiguousarray(rows, dtype=np.uint8).size // (ML + 1)
+            cons = cpu_ref.as_constraints(self.cfg, count, constraints)
+            ctl = cpu_ref.make_controls(self.cfg, count, temperature, top_k, top_p, prefix)
+            cpu_ref.check_prefix_allowed(cons, ctl.prefix, ctl.plen)
+            if cons is not None and self.cfg.vocab // 64 not in (1, 2, 4, 8):
+                raise ValueError(f"constraints need vocab in (64, 128, 256, 512), got {self.cfg.vocab}")
         rows, n_tok, _, _ = cpu_ref.score_inputs(self.cfg, rows)
         N = rows.shape[0]
         if N == 0:
             return ScoreResult(np.zeros((0, ML), np.float32), np.zeros((0, ML), np.int32),
-                               np.zeros(0, np.float32), np.zeros(0, np.int32))
+                               np.zeros(0, np.float32), np.zeros(0, np.int32),
+                               None if ctl is None else np.zeros((0, ML), np.int32))
         r = torch.from_numpy(rows).to(self.dev)
         tok = torch.empty(N, ML, dtype=torch.float32, device=self.dev)
         rank = torch.empty(N, ML, dtype=torch.int32, device=self.dev)
         name = torch.empty(N, dtype=torch.float32, device=self.dev)
         nt = torch.empty(N, dtype=torch.int32, device=self.dev)
-        self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s())
-        err = self.g.read_error()   # synchronises
+        nk = None
+        if ctl is None:
+            self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s())
+        else:
+            dev = [torch.from_numpy(a).to(self.dev) for a in (ctl.inv_temp, ctl.top_k, ctl.top_p, ctl.plen, ctl.prefix)]
+            nk = torch.empty(N, ML, dtype=torch.int32, device=self.dev)
+            extra = ()
+            if cons is not None:
+                tab, idx, lines = self._constraint_tensors(cons)
+                extra = (tab.data_ptr(), idx.data_ptr(), lines)
+            self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s(),
+                         *[t.data_ptr() for t in dev], nk.data_ptr(), *extra)
+        err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
         if err:
             raise RuntimeError(f"HipGenerator.score: device error word {err}")
-        res = ScoreResult(tok.cpu().numpy(), rank.cpu().numpy(), name.cpu().numpy(), nt.cpu().numpy())
+        res = ScoreResult(tok.cpu().numpy(), rank.cpu().numpy(), name.cpu().numpy(), nt.cpu().numpy(),
+                          None if nk is None else nk.cpu().numpy())
         if not np.array_equal(res.n_tok, n_tok):
             raise RuntimeError("HipGenerator.score: device token counts differ from the host's")
         return res
@@ -199,15 +227,23 @@ BeamResult = cpu_ref.BeamResult
 class ScoreResult:
     """``HipGenerator.score`` / ``cpu_ref.score`` output.  tok_logp [N, ML] (masked positions 0),
     rank [N, ML] int32 (masked -1), name_logp [N], n_tok [N] int32; the summaries are computed in
-    float64 from tok_logp."""
+    float64 from tok_logp.  A score with sampling controls or constraints (docs/DESIGN.md §4f) also has
+    n_kept [N, ML] int32, the size of each step's kept set (masked -1; None for a plain score), and may
+    hold -inf: ``impossible`` counts the names the sampler cannot emit, and with one of them
+    nll_per_char and perplexity are inf (top1 is the model's, unchanged)."""
     tok_logp: np.ndarray
     rank: np.ndarray
     name_logp: np.ndarray
     n_tok: np.ndarray
+    n_kept: Optional[np.ndarray] = None
 
     @property
     def tokens(self) -> int:
         return int(self.n_tok.sum())
+
+    @property
+    def impossible(self) -> int:
+        return int(np.isneginf(self.name_logp).sum())
 
     @property
     def nll_per_char(self) -> float:

@@ -224,20 +224,40 @@ def score_inputs(cfg: GRUConfig, rows: np.ndarray):
     return rows, n_tok, x, tgt
 
 
-def score(params: Params, cfg: GRUConfig, rows: np.ndarray):
+def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, top_k=None, top_p=None, prefix=None,
+          constraints=None):
     """log P of output rows under the model, teacher-forced from a zero hidden state (score_inputs).
 
     Returns numpy (tok_logp [N, ML], name_logp [N], n_tok [N] int32, rank [N, ML] int32) in the dtype
     of ``params`` (fp64 params: the oracle).  tok_logp[l] = log softmax(logits_l)[c[l]]; rank[l] = the
     number of j with logit_j > logit_target, or equal and j < target (0: the arg-max is the target);
     name_logp = the tokens' sum in step order.  Masked positions: tok_logp 0, rank -1.
-    exp(name_logp) is the probability that ``generate`` emits exactly that row."""
+    exp(name_logp) is the probability that ``generate`` emits exactly that row.
+
+    ``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` / ``constraints`` (``generate``'s keywords, scalars or
+    one value per row; docs/DESIGN.md §4f): any that is not None -- a neutral value too -- scores the row
+    under the distribution ``generate`` samples from with these settings, and a fifth array is returned,
+    n_kept [N, ML] int32 (masked -1).  At step l with target t:
+      * forced (l < plen): tok_logp 0 if t == prefix[l], else -inf; n_kept 1;
+      * greedy (T == 0): 0 if t is the lowest index of the maximum over the allowed set, else -inf; n_kept 1;
+      * else K = the kept set of steps 3-6 above ``Controls`` inside the step's allowed set, n_kept = |K|,
+        tok_logp = (y_t - max_K y) - log sum_K exp(y_j - max_K y) for t in K and exactly -inf outside.
+    Never NaN; name_logp is the step-order sum, so one -inf makes it -inf: exp(name_logp) is the
+    probability that ``generate`` with these settings emits exactly this row.  rank stays the model's
+    rank on the raw logits, n_tok is read from the row alone."""
+    ctl = cons = None
+    if constraints is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        count = np.ascontiguousarray(rows, dtype=np.uint8).size // (cfg.max_len + 1)
+        cons = as_constraints(cfg, count, constraints)
+        ctl = make_controls(cfg, count, temperature, top_k, top_p, prefix)
+        check_prefix_allowed(cons, ctl.prefix, ctl.plen)
     rows, n_tok, x, tgt = score_inputs(cfg, rows)
     N, ML = tgt.shape
     dt = params["fc.weight"].dtype
     npdt = np.float64 if dt == torch.float64 else np.float32
     if N == 0:
-        return (np.zeros((0, ML), npdt), np.zeros(0, npdt), n_tok, np.zeros((0, ML), np.int32))
+        empty = (np.zeros((0, ML), npdt), np.zeros(0, npdt), n_tok, np.zeros((0, ML), np.int32))
+        return empty if ctl is None else empty + (np.zeros((0, ML), np.int32),)
     logits = forward(params, cfg, torch.from_numpy(x))
     if dt != torch.float64:
         logits = logits.to(torch.float32)
@@ -250,10 +270,46 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray):
     j = torch.arange(cfg.vocab).view(1, 1, -1)
     rank = ((logits > xt) | ((logits == xt) & (j < tc))).sum(-1)
     rank = torch.where(mask, rank, torch.full_like(rank, -1))
+    n_kept = None
+    if ctl is not None:
+        lp, n_kept = _score_controlled(logits, tgt, mask, ctl, cons)
     name = torch.zeros(N, dtype=lp.dtype)
     for l in range(ML):   # step order, as the device sums
         name = name + lp[:, l]
-    return lp.numpy(), name.numpy(), n_tok, rank.numpy().astype(np.int32)
+    out = (lp.numpy(), name.numpy(), n_tok, rank.numpy().astype(np.int32))
+    return out if ctl is None else out + (n_kept,)
+
+
+def _score_controlled(logits: torch.Tensor, tgt: np.ndarray, mask: torch.Tensor, ctl: "Controls", cons):
+    """tok_logp [N, ML] (torch) and n_kept [N, ML] int32 of ``score``'s controlled rule: per step the kept
+    set of ``_filter`` and the log-softmax over it, formed in the log domain (no log of a rounded
+    probability)."""
+    N, ML, V = logits.shape
+    dt = logits.dtype
+    ninf = torch.tensor(-math.inf, dtype=dt)
+    lp = torch.zeros(N, ML, dtype=dt)
+    n_kept = np.full((N, ML), -1, np.int32)
+    inv_t = torch.from_numpy(ctl.inv_temp)
+    scale = torch.where(inv_t == 0, torch.ones_like(inv_t), inv_t).to(dt).unsqueeze(-1)
+    rows = torch.arange(N)
+    for l in range(ML):
+        live = mask[:, l]
+        if not live.any():
+            continue
+        t = torch.from_numpy(np.maximum(tgt[:, l], 0))
+        _, keep = _filter(logits[:, l], ctl.inv_temp, ctl.top_k, ctl.top_p, None if cons is None else cons.allowed(l))
+        y = logits[:, l] * scale                               # _filter's y: rounded once, in the logits' dtype
+        # (with everything kept and T == 1 these are the plain call's operations: its bytes)
+        ls = torch.log_softmax(torch.where(keep, y, ninf), -1)
+        step = torch.where(keep[rows, t], ls[rows, t], ninf)
+        nk = keep.sum(-1)
+        forced = torch.from_numpy(ctl.plen > l)
+        hit = torch.from_numpy(ctl.prefix[:, l].astype(np.int64)) == t
+        step = torch.where(forced, torch.where(hit, torch.zeros_like(step), ninf), step)
+        nk = torch.where(forced, torch.ones_like(nk), nk)
+        lp[:, l] = torch.where(live, step, torch.zeros_like(step))
+        n_kept[:, l] = np.where(live.numpy(), nk.numpy(), -1)
+    return lp, n_kept
 
 
 # --------------------------------------------------------------------------- generation
