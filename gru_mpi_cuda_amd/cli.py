@@ -6,6 +6,7 @@
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt --temperature 0.8 --top-k 40 --pattern '[A-Z]'
     python -m gru_mpi_cuda_amd.cli beam     --ckpt out/model.bin --width 5 --prefix Mar
+    python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 200 --regex '.*son' --exclude-file train.txt --exclude-emitted
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
 
@@ -196,12 +197,22 @@ def _constraint_args(p) -> None:
     p.add_argument("--min-len", dest="min_len", type=int, default=None, help="no name shorter than this")
     p.add_argument("--max-name-len", dest="max_name_len", type=int, default=None,
                    help="no name longer than this (<= the model's max_len)")
+    p.add_argument("--regex", default=None,
+                   help="the whole name matches this: --pattern's items, groups ( ), |, and * + ? {m} {m,} {m,n} "
+                        "(not with --pattern; docs/DESIGN.md §4g)")
+    p.add_argument("--exclude-file", dest="exclude_file", default=None,
+                   help="one name per line: none of them is generated (novel names: pass the training file)")
 
 
 def _constraints_from(args):
-    """The make_constraints keywords of --pattern / --charset / --min-len / --max-name-len (None: none given)."""
+    """The make_constraints keywords of --pattern / --charset / --min-len / --max-name-len / --regex /
+    --exclude-file (None: none given)."""
     kw = {k: v for k, v in (("pattern", args.pattern), ("charset", args.charset), ("min_len", args.min_len),
-                            ("max_len", args.max_name_len)) if v is not None}
+                            ("max_len", args.max_name_len), ("regex", args.regex)) if v is not None}
+    if args.exclude_file is not None:
+        kw["exclude"] = _read_names(args.exclude_file)
+    if "pattern" in kw and ("regex" in kw or "exclude" in kw):
+        raise SystemExit("--pattern cannot be combined with --regex / --exclude-file (write the pattern as a regex)")
     return kw or None
 
 
@@ -240,7 +251,10 @@ def cmd_generate(args) -> int:
     G.namegen_initialize(N, args.seed, args.ckpt, cfg, fmt, ctx=ctx, precision=args.precision)
     out = np.zeros(N * (ml + 1), dtype=np.uint8)
     t1 = time.perf_counter()
-    G.namegen(N, rf, out, **ctl)
+    if args.exclude_emitted:
+        _generate_distinct(G, args, N, ml, ctl, out)
+    else:
+        G.namegen(N, rf, out, **ctl)
     t2 = time.perf_counter()
     rank = int(os.environ.get("RANK", "0"))
     if rank == 0:
@@ -258,6 +272,43 @@ def cmd_generate(args) -> int:
                           "names_per_s": round(N / max(t2 - t1, 1e-9), 1)}), file=sys.stderr)
     G.namegen_finalize()
     return 0
+
+
+def _generate_distinct(G, args, N: int, ml: int, ctl: dict, out: np.ndarray) -> None:
+    """--exclude-emitted: N distinct names.  Batches of --emit-batch names; every batch's names join the
+    exclusion list (docs/DESIGN.md §4g) before the next one, and of the names that one batch holds twice
+    the later ones are dropped and drawn again.  Batch r draws the uniforms of seed + r."""
+    from .utils.data import random_floats
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--exclude-emitted runs on one rank")
+    cons = dict(ctl.get("constraints") or {})
+    if "pattern" in cons:
+        raise SystemExit("--exclude-emitted cannot be combined with --pattern (write the pattern as a regex)")
+    seen = set(cons.get("exclude") or [])
+    rows = out.reshape(N, ml + 1)
+    done = r = 0
+    while done < N:
+        n = min(args.emit_batch, N - done)
+        prefix = ctl.get("prefix")
+        if isinstance(prefix, list):
+            prefix = prefix[done:done + n]
+        kw = {k: v for k, v in ctl.items() if k not in ("constraints", "prefix")}
+        if prefix is not None:
+            kw["prefix"] = prefix
+        buf = np.zeros(n * (ml + 1), dtype=np.uint8)
+        try:
+            G.namegen(n, random_floats(n, ml, seed=args.seed + r), buf, constraints=dict(cons, exclude=sorted(seen)), **kw)
+        except ValueError as e:
+            raise SystemExit(f"--exclude-emitted: {done} of {N} names generated, then: {e}")
+        r += 1
+        eos = bytes([G._S.cfg.eos])
+        for row in buf.reshape(n, ml + 1):
+            name = bytes(row[:ml]).split(eos, 1)[0]
+            if name in seen:
+                continue
+            seen.add(name)
+            rows[done] = row
+            done += 1
 
 
 def _escape(name: str) -> str:
@@ -465,6 +516,10 @@ def main(argv=None) -> int:
     g.add_argument("--prefix-file", dest="prefix_file", default=None,
                    help="one prefix per line, cycled over the names")
     _constraint_args(g)
+    g.add_argument("--exclude-emitted", dest="exclude_emitted", action="store_true",
+                   help="distinct names: every batch's names are excluded from the later batches")
+    g.add_argument("--emit-batch", dest="emit_batch", type=int, default=256,
+                   help="names per batch of --exclude-emitted")
     g.add_argument("--cpu", action="store_true", help="force the CPU reference path (single process)")
     g.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(g)

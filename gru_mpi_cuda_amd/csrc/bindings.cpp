@@ -210,15 +210,18 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("generate_ctl", [](Generator& g, uintptr_t rf, int N, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p,
                               uintptr_t plen, uintptr_t prefix, uintptr_t out, uintptr_t s, uintptr_t allow_tab,
-                              uintptr_t allow_idx, int allow_rows) {
+                              uintptr_t allow_idx, int allow_rows, uintptr_t allow_next, uintptr_t allow_start) {
         Generator::Ctl c;
+        c.allow_next = Pp<const unsigned short>(allow_next); c.allow_start = Pp<const int>(allow_start);
         c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
         c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
         c.allow_tab = Pp<const unsigned>(allow_tab); c.allow_idx = Pp<const int>(allow_idx); c.allow_rows = allow_rows;
         g.generate_ctl(Pp<const float>(rf), N, c, Pp<unsigned char>(out), S(s));
       }, py::arg("rf"), py::arg("N"), py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"), py::arg("plen"),
          py::arg("prefix"), py::arg("out"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
-         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0)
+         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0,
+         py::arg("allow_start") = (uintptr_t)0)
+      .def("automaton_graphs", &Generator::automaton_graphs)
       .def("ctl_workspace_bytes", &Generator::ctl_workspace_bytes)
       .def("ctl_graphs", &Generator::ctl_graphs)
       .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
@@ -241,12 +244,14 @@ PYBIND11_MODULE(_C, m) {
       .def("score_graphs", &Generator::score_graphs)
       .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
                       uintptr_t n_tok, uintptr_t n_beams, uintptr_t s, uintptr_t allow_tab, uintptr_t allow_idx,
-                      int allow_rows) {
+                      int allow_rows, uintptr_t allow_next, uintptr_t allow_start) {
         g.beam(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, Pp<unsigned char>(rows), Pp<float>(logp),
-               Pp<int>(n_tok), Pp<int>(n_beams), S(s), Pp<const unsigned>(allow_tab), Pp<const int>(allow_idx), allow_rows);
+               Pp<int>(n_tok), Pp<int>(n_beams), S(s), Pp<const unsigned>(allow_tab), Pp<const int>(allow_idx), allow_rows,
+               Pp<const unsigned short>(allow_next), Pp<const int>(allow_start));
       }, py::arg("plen"), py::arg("prefix"), py::arg("N"), py::arg("W"), py::arg("rows"), py::arg("logp"),
          py::arg("n_tok"), py::arg("n_beams"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
-         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0)
+         py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0,
+         py::arg("allow_start") = (uintptr_t)0)
       .def("beam_workspace_bytes", &Generator::beam_workspace_bytes)
       .def("beam_graphs", &Generator::beam_graphs)
       .def("set_use_graph", &Generator::set_use_graph)
@@ -770,6 +775,7 @@ PYBIND11_MODULE(_C, m) {
     c.prefix = GP(const unsigned char, d, "prefix"); c.row0 = get<int>(d, "row0", 0); c.err = GP(unsigned, d, "err");
     c.allow_tab = GP(const unsigned, d, "allow_tab"); c.allow_idx = GP(const int, d, "allow_idx");
     c.allow_rows = get<int>(d, "allow_rows", 0);
+    c.allow_state = GP(int, d, "allow_state"); c.allow_next = GP(const unsigned short, d, "allow_next");
     sample_ctl_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
@@ -903,6 +909,8 @@ PYBIND11_MODULE(_C, m) {
     a.max_len = get<int>(d, "max_len", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
     a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
     a.allow_rows = get<int>(d, "allow_rows", 0);
+    a.allow_state_in = GP(const int, d, "allow_state_in"); a.allow_state_out = GP(int, d, "allow_state_out");
+    a.allow_next = GP(const unsigned short, d, "allow_next");
     beam_select_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });
@@ -930,6 +938,7 @@ PYBIND11_MODULE(_C, m) {
     for (int l = 0; l < a.L; ++l) a.h[l] = Pp<float>(h[l]);
     a.ids = GP(int, d, "ids"); a.score = GP(float, d, "score"); a.state = GP(int, d, "state"); a.len = GP(int, d, "len");
     a.rows = GP(unsigned char, d, "rows");
+    a.allow_state = GP(int, d, "allow_state"); a.allow_start = GP(const int, d, "allow_start");
     beam_reset(a, S(s));
     HIP_LAUNCH_CHECK();
   });

@@ -86,6 +86,11 @@ Generator::~Generator() {
   scgraphs_.clear();
   cgraphs_.clear();
   bgraphs_.clear();
+  agraphs_.clear();
+  abgraphs_.clear();
+  for (void* p : {(void*)atab_, (void*)anxt_, (void*)astart_, (void*)astate_, (void*)abstart_, (void*)abstate_[0],
+                  (void*)abstate_[1]})
+    if (p) (void)hipFree(p);
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
 }
@@ -233,11 +238,12 @@ int Generator::product_f32(const float* A32, const u16* A3, const float* W32, co
   return g.splits;
 }
 
-void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows) {
+void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows, bool automaton) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n, 64);
   const bool x3 = split3();
   reset_batch(Bp, false, s);
+  if (automaton) automaton_reset(astate_, astart_, n, n, s);   // every name back to its start state
   for (int st = 0; st < ML; ++st) {
     const int cur = st & 1, nxt = cur ^ 1;
     for (int l = 0; l < L; ++l) {
@@ -271,7 +277,8 @@ void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows)
       SampleCtlArgs c;
       c.s = q; c.inv_temp = cinv_; c.top_k = ctopk_; c.top_p = ctopp_; c.plen = cplen_; c.prefix = cprefix_;
       c.row0 = 0; c.err = err_;
-      if (allow_rows > 0) { c.allow_tab = ctab_; c.allow_idx = cidx_; c.allow_rows = allow_rows; }
+      if (automaton) { c.allow_tab = atab_; c.allow_next = anxt_; c.allow_state = astate_; c.allow_rows = allow_rows; }
+      else if (allow_rows > 0) { c.allow_tab = ctab_; c.allow_idx = cidx_; c.allow_rows = allow_rows; }
       sample_ctl_f32(c, s);
     } else {
       sample_f32(q, s);
@@ -374,16 +381,50 @@ void Generator::ctl_alloc() {
   cready_ = true;
 }
 
+void Generator::automaton_stage(const unsigned* tab, const unsigned short* next, int states, hipStream_t s) {
+  const size_t B = Bmax_, V = d_.V;
+  if (!astate_) {
+    for (int** p : {&astart_, &astate_, &abstart_, &abstate_[0], &abstate_[1]}) {
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), B * 4));
+      HIP_CHECK(hipMemset(*p, 0, B * 4));
+    }
+  }
+  if (states > acap_) {   // grow: the recordings hold the old addresses
+    HIP_CHECK(hipDeviceSynchronize());
+    agraphs_.clear();
+    abgraphs_.clear();
+    if (atab_) HIP_CHECK(hipFree(atab_));
+    if (anxt_) HIP_CHECK(hipFree(anxt_));
+    atab_ = nullptr; anxt_ = nullptr; acap_ = 0;
+    int cap = 1024;
+    while (cap < states) cap *= 2;
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&atab_), (size_t)cap * (V / 32) * 4));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&anxt_), (size_t)cap * V * 2));
+    acap_ = cap;
+  }
+  HIP_CHECK(hipMemcpyAsync(atab_, tab, (size_t)states * (V / 32) * 4, hipMemcpyDeviceToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(anxt_, next, (size_t)states * V * 2, hipMemcpyDeviceToDevice, s));
+}
+
 void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s) {
   GK_TRACE("gk.generate_ctl");
   if (!d_.fp32) throw std::runtime_error("Generator::generate_ctl: sampling controls need precision fp32 or bf16x3");
   if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix)
     throw std::runtime_error("Generator::generate_ctl: every control array is required");
+  const bool aut = c.allow_next != nullptr || c.allow_start != nullptr;
+  if (aut && (!c.allow_next || !c.allow_start || !c.allow_tab || c.allow_idx || c.allow_rows < 1 ||
+              c.allow_rows > kAutoStates || (d_.V != 256 && d_.V != 512)))
+    throw std::runtime_error("Generator::generate_ctl: an automaton needs allow_tab, allow_next and allow_start, no "
+                             "allow_idx, 1 <= allow_rows <= 65535 and a vocabulary of 256 or 512");
   const bool masked = c.allow_tab != nullptr;
-  if (masked != (c.allow_idx != nullptr) || (masked && (c.allow_rows < 1 || c.allow_rows > kAllowRows)))
+  if (!aut && (masked != (c.allow_idx != nullptr) || (masked && (c.allow_rows < 1 || c.allow_rows > kAllowRows))))
     throw std::runtime_error("Generator::generate_ctl: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   const int ML = d_.max_len;
+  if (aut) {   // before the error word is cleared: growing the buffers synchronises
+    ctl_alloc();
+    automaton_stage(c.allow_tab, c.allow_next, c.allow_rows, s);
+  }
   if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   bool tab_staged = false;
@@ -405,6 +446,29 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
     HIP_CHECK(hipMemcpyAsync(cplen_, c.plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cprefix_, c.prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
     const int ar = masked ? c.allow_rows : 0;
+    if (aut) {   // the tables are staged: this batch's start states, then its graph
+      HIP_CHECK(hipMemcpyAsync(astart_, c.allow_start + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      if (use_graph_) {
+        // every state count has a recording of its own, and a caller that grows an exclusion list call by
+        // call never comes back to one: keep the latest few
+        if (agraphs_.size() >= kAutoGraphs && !agraphs_.count(std::make_pair(n, ar))) {
+          HIP_CHECK(hipStreamSynchronize(s));
+          agraphs_.clear();
+        }
+        auto& g = agraphs_[std::make_pair(n, ar)];
+        if (!g) {
+          g.reset(new Graph());
+          g->begin(cap_);
+          record_steps_f32(n, cap_, true, ar, true);
+          g->end(cap_);
+        }
+        g->launch(s);
+      } else {
+        record_steps_f32(n, s, true, ar, true);
+      }
+      HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+      continue;
+    }
     if (masked) {   // the table once per call, this batch's lines
       if (!tab_staged) {
         HIP_CHECK(hipMemcpyAsync(ctab_, c.allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
@@ -627,7 +691,7 @@ void Generator::beam_alloc() {
 // exact-fp32 step (the master weights, f32_splits slabs summed in order by the consumer), but on
 // fixed slots: the gates read bhA_ and write bhB_, the reorder gathers bhB_ -> bhA_.  Scores, states,
 // lengths and output rows alternate between two sets by step parity; the result is in set ML & 1.
-void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows) {
+void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows, bool automaton) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n * W, 64);
   const int cap = std::max(Bmax_, kF32SlabRows);
@@ -635,6 +699,7 @@ void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows) {
   for (int l = 0; l < L; ++l) r.h[l] = bhA_[l];
   r.ids = bids_; r.score = bscore_[0]; r.state = bstate_[0]; r.len = blen_[0]; r.rows = brows_[0];
   r.N = n; r.W = W; r.L = L; r.Bp = Bp; r.H = H; r.max_len = ML; r.sos = d_.sos;
+  if (automaton) { r.allow_state = abstate_[0]; r.allow_start = abstart_; }
   beam_reset(r, s);
   auto product = [&](const float* A, const float* Wt, const float* bias, int N, float* C) {
     GemmF32Args g;
@@ -666,7 +731,12 @@ void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows) {
     q.score_in = bscore_[cur]; q.state_in = bstate_[cur]; q.plen = bplen_; q.prefix = bprefix_;
     q.score_out = bscore_[nxt]; q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_; q.next_id = bnext_;
     q.err = err_; q.N = n; q.W = W; q.V = V; q.step = st; q.max_len = ML; q.sos = d_.sos; q.eos = d_.eos;
-    if (allow_rows > 0) { q.allow_tab = btab_; q.allow_idx = bidx_; q.allow_rows = allow_rows; }
+    if (automaton) {
+      q.allow_tab = atab_; q.allow_next = anxt_; q.allow_rows = allow_rows;
+      q.allow_state_in = abstate_[cur]; q.allow_state_out = abstate_[nxt];
+    } else if (allow_rows > 0) {
+      q.allow_tab = btab_; q.allow_idx = bidx_; q.allow_rows = allow_rows;
+    }
     beam_select_f32(q, s);
     BeamReorderArgs o;
     for (int l = 0; l < L; ++l) { o.h_src[l] = bhB_[l]; o.h_dst[l] = bhA_[l]; }
@@ -681,7 +751,7 @@ void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows) {
 
 void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
                      int* n_tok, int* n_beams, hipStream_t s, const unsigned* allow_tab, const int* allow_idx,
-                     int allow_rows) {
+                     int allow_rows, const unsigned short* allow_next, const int* allow_start) {
   GK_TRACE("gk.beam");
   const int ML = d_.max_len;
   if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::beam needs 1 <= width <= min(32, vocab)");
@@ -690,34 +760,47 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
   if (d_.L > 4) throw std::runtime_error("Generator::beam needs at most 4 layers");
   if (!plen || !prefix || !rows || !logp || !n_tok || !n_beams)
     throw std::runtime_error("Generator::beam: plen, prefix, rows, logp, n_tok and n_beams are required");
+  const bool aut = allow_next != nullptr || allow_start != nullptr;
+  if (aut && (!allow_next || !allow_start || !allow_tab || allow_idx || allow_rows < 1 || allow_rows > kAutoStates ||
+              (d_.V != 256 && d_.V != 512)))
+    throw std::runtime_error("Generator::beam: an automaton needs allow_tab, allow_next and allow_start, no allow_idx, "
+                             "1 <= allow_rows <= 65535 and a vocabulary of 256 or 512");
   const bool masked = allow_tab != nullptr;
-  if (masked != (allow_idx != nullptr) || (masked && (allow_rows < 1 || allow_rows > kAllowRows)))
+  if (!aut && (masked != (allow_idx != nullptr) || (masked && (allow_rows < 1 || allow_rows > kAllowRows))))
     throw std::runtime_error("Generator::beam: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   beam_alloc();   // first call: allocates (and synchronises) before anything is captured
+  if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);   // the tables once per call
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   const int nb = d_.max_batch / W, fin = ML & 1;
   const int ar = masked ? allow_rows : 0;
-  if (masked)   // the table once per call
+  if (masked && !aut)   // the table once per call
     HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
   for (int start = 0; start < N; start += nb) {
     const int n = std::min(nb, N - start);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
-    if (masked)
+    if (aut)
+      HIP_CHECK(hipMemcpyAsync(abstart_, allow_start + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    else if (masked)
       HIP_CHECK(hipMemcpyAsync(bidx_, allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     if (use_graph_) {
-      auto& g = bgraphs_[std::make_tuple(n, W, ar)];   // ar: baked into the recording, as in generate_ctl
+      // ar: baked into the recording, as in generate_ctl; the automaton recordings have a map of their own
+      if (aut && abgraphs_.size() >= kAutoGraphs && !abgraphs_.count(std::make_tuple(n, W, ar))) {   // as in generate_ctl
+        HIP_CHECK(hipStreamSynchronize(s));
+        abgraphs_.clear();
+      }
+      auto& g = aut ? abgraphs_[std::make_tuple(n, W, ar)] : bgraphs_[std::make_tuple(n, W, ar)];
       if (!g) {
         g.reset(new Graph());
         g->begin(cap_);
-        record_beam(n, W, cap_, ar);
+        record_beam(n, W, cap_, ar, aut);
         g->end(cap_);
       }
       g->launch(s);
     } else {
-      record_beam(n, W, s, ar);
+      record_beam(n, W, s, ar, aut);
     }
     const size_t r0 = (size_t)start * W, nr = (size_t)n * W;
     HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), brows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));

@@ -49,8 +49,19 @@ class Generator {
     const float* inv_temp = nullptr; const int* top_k = nullptr; const float* top_p = nullptr;
     const int* plen = nullptr; const unsigned char* prefix = nullptr;
     const unsigned* allow_tab = nullptr; const int* allow_idx = nullptr; int allow_rows = 0;
+    // Automaton (docs/DESIGN.md §4g; both set with allow_tab, never with allow_idx; allow_rows = the
+    // states, <= kAutoStates): allow_next [allow_rows][V], allow_start [N] the names' start states
+    const unsigned short* allow_next = nullptr; const int* allow_start = nullptr;
   };
   static constexpr int kAllowRows = 1024;   // lines of a constraint table
+  static constexpr int kAutoStates = 65535; // states of an automaton
+  static constexpr size_t kAutoGraphs = 16; // automaton recordings kept per map (a full map is dropped before the next one)
+  // An automaton-constrained generate_ctl() / beam() (score() never sees one: the host walks its known
+  // rows into an allow_idx) uploads tab and next once per call into buffers that
+  // grow on demand -- a table can be 32 MiB, too much to reserve for every generator -- and every
+  // batch takes the controlled per-char graph (beam: its graph) in a recording of its own per (n,
+  // states), whose head resets the per-row state buffer from the batch's start states and whose
+  // sampler (select) advances it.  Growing the buffers drops those recordings.
   void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
   size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until a batch takes the per-char controlled graph
   // generate_ctl() batches of n names run as one controlled persistent launch (exact fp32, as the plain
@@ -88,13 +99,14 @@ class Generator {
   // constraints as in Ctl (null: none); a constrained call has its own graph per (names, W).
   void beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp, int* n_tok,
             int* n_beams, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
-            int allow_rows = 0);
+            int allow_rows = 0, const unsigned short* allow_next = nullptr, const int* allow_start = nullptr);
   size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
+  int automaton_graphs() const { return (int)(agraphs_.size() + abgraphs_.size()); }   // ... with an automaton
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
-  void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); }
+  void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); agraphs_.clear(); }
   // Small batches (fp32 modes: <= GK_GEN_PERSIST_MAX names, default and at most 64; bf16 mode: <= 24):
   // one persistent launch per batch (gen_persist.hip, exact fp32) instead of the per-char graph.
   // On by default; GK_GEN_PERSIST=0 or set_persist(false) turns it off.
@@ -119,7 +131,8 @@ class Generator {
  private:
   void record_steps(int n_active, hipStream_t s);
   // ctl: sample_ctl_f32 as the sampler node; allow_rows > 0: with the constraint buffers
-  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false, int allow_rows = 0);
+  // automaton: allow_rows states, the sampler reads atab_ / anxt_ / astate_ and the head resets astate_
+  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false, int allow_rows = 0, bool automaton = false);
   // one product of the fp32 / bf16x3 path: C = h W^T (+ bias) -> splits (slabs of M x N at C).  fp32
   // reads A32 / W32; bf16x3 the split copies A3 ([hi|hi|lo] rows) / W3 ([hi|lo|hi] rows)
   int product_f32(const float* A32, const u16* A3, const float* W32, const u16* W3, const float* bias, int M, int N,
@@ -136,7 +149,9 @@ class Generator {
   void record_score(int Bp, hipStream_t s, bool ctl = false, int allow_rows = 0);
   void score_ctl_alloc();
   void beam_alloc();
-  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0);
+  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false);
+  // the automaton buffers for `states` states (grown, never shrunk) and the call's tables into them
+  void automaton_stage(const unsigned* tab, const unsigned short* next, int states, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
 
   GenDims d_;
@@ -222,6 +237,15 @@ class Generator {
   unsigned char* bprefix_ = nullptr;            // [Bmax][ML]
   unsigned* btab_ = nullptr;                    // [kAllowRows][V / 32] the call's constraint table
   int* bidx_ = nullptr;                         // [Bmax][ML] the current batch's lines
+  // automaton constraints (plain allocations, made by the first automaton call and grown on demand)
+  unsigned* atab_ = nullptr;                    // [acap_][V / 32] the call's state sets
+  unsigned short* anxt_ = nullptr;              // [acap_][V] the call's successor table
+  int acap_ = 0;                                // states the two hold
+  int *astart_ = nullptr, *astate_ = nullptr;   // [Bmax] the sampler's batch: start states, current states
+  int* abstart_ = nullptr;                      // [Bmax] the beam batch's start states
+  int* abstate_[2] = {nullptr, nullptr};        // [Bmax] x2 the beam rows' states, by step parity
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> agraphs_;          // keyed by (n, states)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> abgraphs_;   // keyed by (names, W, states)
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

@@ -21,6 +21,11 @@
 // one line of a bit table; a lane loads the one word that covers its V/64 chars once, before the rows,
 // and a live beam's masked candidate keeps key 0.  Carries are not masked.  MASK = false is the kernel
 // as it was.
+//
+// Automaton (docs/DESIGN.md §4g, the AUTO instantiations, always with MASK): every beam row has a state
+// of its own, so the word is loaded per row, from the line its state names; the winners' threads write
+// the children's states -- allow_next[parent's line][chr], 0 for a carry or a dead slot -- into the
+// other state buffer, as the reorder gathers h.  AUTO = false is the kernel as it was.
 #include <cmath>
 #include <stdexcept>
 #include "kernels.h"
@@ -46,7 +51,7 @@ DEV unsigned wave_umax(unsigned u) {   // identical in every lane
 }  // namespace
 
 // R: beam rows per wave (wave w owns beams w and w + nw), MAXPER: logits per lane and row
-template <int R, int MAXPER, bool MASK>
+template <int R, int MAXPER, bool MASK, bool AUTO = false>
 __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a) {
 #pragma clang fp contract(off)
   __shared__ unsigned s_key[2][kMaxWaves];
@@ -70,7 +75,7 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
     }
   }
   unsigned ok = 0u;   // MASK: bit e = this lane's char e is allowed
-  if constexpr (MASK) {
+  if constexpr (MASK && !AUTO) {
     int ar = a.allow_idx[(size_t)n * a.max_len + a.step];
     if (ar < 0 || ar >= a.allow_rows) {   // never expected (the host builds both): flag it, no constraint
       if (a.err && threadIdx.x == 0) {
@@ -115,6 +120,18 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
     const float lse = logf(se);
     const float sb = a.score_in[row];
     const int st = a.state_in[row];
+    if constexpr (AUTO) {   // this row's line
+      int q = a.allow_state_in[row];
+      if (q < 0 || q >= a.allow_rows) {   // never expected (the host builds start and next): flag it, the free state
+        if (a.err && lane == 0) {
+          atomicOr(a.err, 16u);
+          a.err[1] = (unsigned)q;
+          a.err[2] = (unsigned)row;
+        }
+        q = 0;
+      }
+      ok = a.allow_tab[(size_t)q * (V >> 5) + ((lane * per) >> 5)] >> ((lane * per) & 31);
+    }
 #pragma unroll
     for (int e = 0; e < MAXPER; ++e) {
       if (e >= per) continue;
@@ -181,12 +198,18 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
     const size_t o = (size_t)n * W + k;
     float sc = -INFINITY;
     int parent = -1, ch = -1, st = kDead, nxt = a.sos;
+    int qn = 0;   // AUTO: the child's automaton state
     if (any) {
       const size_t prow = (size_t)n * W + pb;
       parent = pb;
       if (a.state_in[prow] == kFin) {
         sc = a.score_in[prow]; st = kFin;
       } else {
+        if constexpr (AUTO) {
+          int q = a.allow_state_in[prow];
+          if (q < 0 || q >= a.allow_rows) q = 0;   // (flagged above)
+          qn = a.allow_next[(size_t)q * V + pc];
+        }
         // the candidate's score back from its key (the key keeps every bit but the sign of zero)
         sc = __uint_as_float((wk & 0x80000000u) ? (wk & 0x7fffffffu) : ~wk);
         ch = pc;
@@ -196,6 +219,7 @@ __global__ void __launch_bounds__(1024) beam_select_f32_kernel(BeamSelectArgs a)
     }
     a.score_out[o] = sc; a.parent[o] = parent; a.chr[o] = ch; a.state_out[o] = st; a.next_id[o] = nxt;
     if (a.sel) a.sel[o] = any ? wj : -1;
+    if constexpr (AUTO) a.allow_state_out[o] = qn;
   }
 }
 
@@ -211,7 +235,12 @@ void beam_select_f32(const BeamSelectArgs& a, hipStream_t s) {
     throw std::runtime_error("beam_select_f32: needs 0 <= step < max_len, eos >= 0 and 0 <= sos < V");
   if (a.splits < 1 || (a.splits > 1 && a.slab < (long)a.N * a.W * a.V))
     throw std::runtime_error("beam_select_f32: split-K slabs overlap");
-  if ((a.allow_tab != nullptr) != (a.allow_idx != nullptr))
+  const bool aut = a.allow_state_in || a.allow_state_out || a.allow_next;
+  if (aut && (!a.allow_state_in || !a.allow_state_out || !a.allow_next || !a.allow_tab || a.allow_idx ||
+              a.allow_state_in == a.allow_state_out || a.allow_rows > 65535 || (a.V != 256 && a.V != 512)))
+    throw std::runtime_error("beam_select_f32: an automaton needs allow_state_in, allow_state_out (another buffer), "
+                             "allow_next and allow_tab, no allow_idx, at most 65535 states and V = 256 or 512");
+  if (!aut && (a.allow_tab != nullptr) != (a.allow_idx != nullptr))
     throw std::runtime_error("beam_select_f32: allow_tab and allow_idx are set together or not at all");
   const bool mask = a.allow_tab != nullptr;
   if (mask && (a.allow_rows < 1 || 32 % (a.V / 64)))
@@ -219,7 +248,15 @@ void beam_select_f32(const BeamSelectArgs& a, hipStream_t s) {
   if (a.N <= 0) return;
   const int nw = a.W <= kMaxWaves ? a.W : kMaxWaves;
   const dim3 grid(a.N), block(64 * nw);
-  if (mask) {
+  if (aut) {
+    if (a.W <= kMaxWaves) {
+      if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<1, 4, true, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((beam_select_f32_kernel<1, 8, true, true>), grid, block, 0, s, a);
+    } else {
+      if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<2, 4, true, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((beam_select_f32_kernel<2, 8, true, true>), grid, block, 0, s, a);
+    }
+  } else if (mask) {
     if (a.W <= kMaxWaves) {
       if (a.V <= 256) hipLaunchKernelGGL((beam_select_f32_kernel<1, 4, true>), grid, block, 0, s, a);
       else hipLaunchKernelGGL((beam_select_f32_kernel<1, 8, true>), grid, block, 0, s, a);
@@ -297,6 +334,7 @@ void beam_reorder(const BeamReorderArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(beam_reorder_kernel, dim3(a.N, a.L + 1), dim3(256), 0, s, a);
 }
 
+template <bool AUTO>
 __global__ void __launch_bounds__(256) beam_reset_kernel(BeamResetArgs a) {
   const long n = (long)a.Bp * a.H, stride = (long)gridDim.x * blockDim.x;
   const long nrow = (long)a.Bp * (a.max_len + 1);
@@ -310,6 +348,7 @@ __global__ void __launch_bounds__(256) beam_reset_kernel(BeamResetArgs a) {
       a.score[i] = first ? 0.f : -INFINITY;
       a.state[i] = first ? kLive : kDead;
       a.len[i] = 0;
+      if constexpr (AUTO) a.allow_state[i] = first ? a.allow_start[i / a.W] : 0;
     }
   }
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nrow; i += stride) a.rows[i] = 0;
@@ -322,7 +361,10 @@ void beam_reset(const BeamResetArgs& a, hipStream_t s) {
     if (!a.h[l]) throw std::runtime_error("beam_reset: null h");
   if (!a.ids || !a.score || !a.state || !a.len || !a.rows)
     throw std::runtime_error("beam_reset: ids, score, state, len and rows are required");
-  hipLaunchKernelGGL(beam_reset_kernel, dim3(256), dim3(256), 0, s, a);
+  if ((a.allow_state != nullptr) != (a.allow_start != nullptr))
+    throw std::runtime_error("beam_reset: allow_state and allow_start are set together or not at all");
+  if (a.allow_state) hipLaunchKernelGGL(beam_reset_kernel<true>, dim3(256), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(beam_reset_kernel<false>, dim3(256), dim3(256), 0, s, a);
 }
 
 }  // namespace gk

@@ -25,6 +25,11 @@
 // allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one
 // 32-bit word of that line -- one load per lane and row -- and a masked char takes y = -inf after the
 // temperature scale and is in no kept set.  MASK = false is the kernel as it was.
+//
+// Automaton (docs/DESIGN.md §4g, the AUTO instantiations, always with MASK): the line index is not a
+// function of the step but a per-row state in device memory.  Every lane reads it (one uniform 4-byte
+// load), and once the char is known lane 0 stores the successor, a 2-byte load from allow_next -- on a
+// forced step too, which reads no mask but still advances.  AUTO = false is the kernel as it was.
 #include "kernels.h"
 #include "common.h"
 #include "gen_sample.h"
@@ -38,7 +43,7 @@ DEV unsigned order_key(float f) {
   return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
-template <int MAXPER, bool MASK>
+template <int MAXPER, bool MASK, bool AUTO = false>
 __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
 #pragma clang fp contract(off)
   const SampleF32Args& a = c.s;
@@ -47,6 +52,18 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
   const int cb = b + c.row0;   // this row's controls
   float* prow = a.probs ? a.probs + (size_t)b * V : nullptr;
   int sel;
+  int q = 0;   // AUTO: this row's automaton state = its table line
+  if constexpr (AUTO) {
+    q = c.allow_state[cb];
+    if (q < 0 || q >= c.allow_rows) {   // never expected (the host builds start and next): flag it, the free state
+      if (c.err && lane == 0) {
+        atomicOr(c.err, 16u);
+        c.err[1] = (unsigned)q;
+        c.err[2] = (unsigned)b;
+      }
+      q = 0;
+    }
+  }
   if (a.step < c.plen[cb]) {   // forced: the uniform of this step is ignored
     sel = c.prefix[(size_t)cb * a.max_len + a.step];
     if (sel >= V) {   // never expected (the host checks first): flag it instead of feeding it on
@@ -68,7 +85,9 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
     const float tp = c.top_p[cb];
     const float scale = it == 0.f ? 1.f : it;
     unsigned ok = 0u;   // MASK: bit e = this lane's char e is allowed
-    if constexpr (MASK) {
+    if constexpr (AUTO) {
+      ok = c.allow_tab[(size_t)q * (V >> 5) + ((lane * per) >> 5)] >> ((lane * per) & 31);
+    } else if constexpr (MASK) {
       int ar = c.allow_idx[(size_t)cb * a.max_len + a.step];
       if (ar < 0 || ar >= c.allow_rows) {   // never expected (the host builds both): flag it, no constraint
         if (c.err && lane == 0) {
@@ -199,7 +218,19 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
       if (sel == a.eos) a.alive[b] = 0;
     }
     a.ids[b] = sel;
+    if constexpr (AUTO) c.allow_state[cb] = c.allow_next[(size_t)q * V + sel];   // 0 <= sel < V on every branch
   }
+}
+
+__global__ void __launch_bounds__(256) automaton_reset_kernel(int* state, const int* start, int n, int Bp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Bp) state[i] = i < n ? start[i] : 0;
+}
+
+void automaton_reset(int* state, const int* start, int n, int Bp, hipStream_t s) {
+  if (!state || !start || n < 0 || n > Bp) throw std::runtime_error("automaton_reset: state, start and 0 <= n <= Bp required");
+  if (Bp <= 0) return;
+  hipLaunchKernelGGL(automaton_reset_kernel, dim3((Bp + 255) / 256), dim3(256), 0, s, state, start, n, Bp);
 }
 
 void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s) {
@@ -207,13 +238,23 @@ void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s) {
   if (a.V % 64 || a.V > 512 || a.V <= 0) throw std::runtime_error("sample_ctl_f32: needs V % 64 == 0 and V <= 512");
   if (!c.inv_temp || !c.top_k || !c.top_p || !c.plen || !c.prefix || c.row0 < 0)
     throw std::runtime_error("sample_ctl_f32: inv_temp, top_k, top_p, plen and prefix are required");
-  if ((c.allow_tab != nullptr) != (c.allow_idx != nullptr))
+  if (!c.allow_state && !c.allow_next && (c.allow_tab != nullptr) != (c.allow_idx != nullptr))
     throw std::runtime_error("sample_ctl_f32: allow_tab and allow_idx are set together or not at all");
   const bool mask = c.allow_tab != nullptr;
   if (mask && (c.allow_rows < 1 || 32 % (a.V / 64)))
     throw std::runtime_error("sample_ctl_f32: constraints need allow_rows >= 1 and V / 64 in {1, 2, 4, 8}");
+  if ((c.allow_state != nullptr) != (c.allow_next != nullptr) || (c.allow_state && (!c.allow_tab || c.allow_idx)))
+    throw std::runtime_error("sample_ctl_f32: allow_state and allow_next are set together, with allow_tab and without allow_idx");
+  if (c.allow_state && c.allow_rows > 65535)
+    throw std::runtime_error("sample_ctl_f32: an automaton has at most 65535 states");
   if (a.N <= 0) return;
   const dim3 grid(a.N), block(64);
+  if (c.allow_state) {
+    if (a.V == 256) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true, true>), grid, block, 0, s, c);
+    else if (a.V == 512) hipLaunchKernelGGL((sample_ctl_f32_kernel<8, true, true>), grid, block, 0, s, c);
+    else throw std::runtime_error("sample_ctl_f32: the automaton instantiations need V = 256 or 512");
+    return;
+  }
   if (a.V == 256) {
     if (mask) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true>), grid, block, 0, s, c);
     else hipLaunchKernelGGL((sample_ctl_f32_kernel<4, false>), grid, block, 0, s, c);

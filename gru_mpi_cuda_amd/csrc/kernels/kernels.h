@@ -393,8 +393,17 @@ struct SampleCtlArgs {
   const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]: the allowed sets as bit masks
   const int* allow_idx = nullptr;          // nullable [..][max_len]: the table line of a row's step
   int allow_rows = 0;
+  // Automaton (docs/DESIGN.md §4g; both set together with allow_tab, never with allow_idx): the row's
+  // line is allow_state[b + row0] -- the allow_idx rule for a value outside [0, allow_rows) -- and once
+  // the char is known lane 0 stores allow_next[line][char] there, on a forced step too (which reads no
+  // mask but still advances).  The host builds allow_next with every entry < allow_rows.
+  int* allow_state = nullptr;                    // nullable [..]: read and written
+  const unsigned short* allow_next = nullptr;    // nullable [allow_rows][V]
 };
 void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s);
+// state[i] = start[i] for i < n, 0 (the free state) for n <= i < Bp: the head of an automaton batch as
+// a kernel node of its own (docs/DESIGN.md §4g)
+void automaton_reset(int* state, const int* start, int n, int Bp, hipStream_t s);
 // bf16x3 operands: an fp32 value x = hi + lo with hi = bf16(x), lo = bf16(x - hi).  Weights become
 // [R][3K] = [hi | lo | hi] rows and activations [hi | hi | lo] rows, so ONE bf16 MFMA GEMM over 3K
 // accumulates hi*hi + hi*lo + lo*hi in fp32 (the lo*lo term, ~2^-16 relative, is dropped).
@@ -559,6 +568,13 @@ struct BeamSelectArgs {
   const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]
   const int* allow_idx = nullptr;          // nullable [N][max_len]
   int allow_rows = 0;
+  // Automaton (docs/DESIGN.md §4g; all three set together with allow_tab, never with allow_idx): beam
+  // row n W + b reads its line from allow_state_in (a value outside [0, allow_rows): err 16, line 0);
+  // new beam k gets allow_state_out = allow_next[line of its parent][chr] when its parent was live,
+  // else 0 (a carry, a dead slot).  Never in place: the two state buffers differ.
+  const int* allow_state_in = nullptr;           // nullable [N W]
+  int* allow_state_out = nullptr;                // nullable [N W]
+  const unsigned short* allow_next = nullptr;    // nullable [allow_rows][V]
 };
 void beam_select_f32(const BeamSelectArgs& a, hipStream_t s);
 // The winners' state moved into the next step's slots: per layer h_dst[n W + k] = h_src[n W + parent[k]]
@@ -584,6 +600,10 @@ struct BeamResetArgs {
   int* ids = nullptr; float* score = nullptr; int* state = nullptr; int* len = nullptr;   // [Bp]
   unsigned char* rows = nullptr;   // [Bp][max_len + 1]
   int N = 0, W = 0, L = 0, Bp = 0, H = 0, max_len = 0, sos = 0;
+  // Automaton (docs/DESIGN.md §4g; both or neither): beam 0 of name n starts in allow_start[n], every
+  // other row in state 0
+  int* allow_state = nullptr;          // nullable [Bp]
+  const int* allow_start = nullptr;    // nullable [N]
 };
 void beam_reset(const BeamResetArgs& a, hipStream_t s);
 

@@ -76,12 +76,25 @@ class HipGenerator:
         return torch.cuda.current_stream(self.dev).cuda_stream
 
     def _constraint_tensors(self, cons):
-        """A Constraints object's arrays on the device: (tab, idx, lines)."""
+        """A Constraints object's arrays on the device: (tab, idx, lines); an Automaton's (docs/DESIGN.md
+        §4g): (tab, None, states, nxt, start).  The tuple holds the tensors alive; ``_constraint_args``
+        turns it into the native call's trailing arguments."""
+        if isinstance(cons, cpu_ref.Automaton):
+            if self.cfg.vocab not in (256, 512):
+                raise ValueError(f"regex / exclude constraints need vocab 256 or 512 on the device, got {self.cfg.vocab}")
+            tab = torch.from_numpy(cons.tab.view(np.int32)).to(self.dev)
+            nxt = torch.from_numpy(np.ascontiguousarray(cons.nxt, dtype=np.uint16).view(np.int16)).to(self.dev)
+            start = torch.from_numpy(np.ascontiguousarray(cons.start, dtype=np.int32)).to(self.dev)
+            return tab, None, cons.states, nxt, start
         if self.cfg.vocab // 64 not in (1, 2, 4, 8):
             raise ValueError(f"constraints need vocab in (64, 128, 256, 512), got {self.cfg.vocab}")
         tab = torch.from_numpy(cons.tab.view(np.int32)).to(self.dev)
         idx = torch.from_numpy(np.ascontiguousarray(cons.idx, dtype=np.int32)).to(self.dev)
         return tab, idx, cons.rows
+
+    @staticmethod
+    def _constraint_args(t) -> tuple:
+        return tuple(0 if v is None else (v if isinstance(v, int) else v.data_ptr()) for v in t)
 
     def generate_device(self, rf_dev: torch.Tensor, n: int, *, temperature=None, top_k=None, top_p=None,
                         prefix=None, constraints=None) -> torch.Tensor:
@@ -91,7 +104,10 @@ class HipGenerator:
         ``g.uses_persist_ctl(batch)`` says so (small batches), else the controlled per-char graph.
         ``constraints`` (a cpu_ref.Constraints for the ``n`` names, or a dict of cpu_ref.make_constraints
         keywords; docs/DESIGN.md §4e): every name samples inside its per-position allowed sets, always on
-        the controlled per-char graph.  Bad values raise ValueError before anything is launched."""
+        the controlled per-char graph.  With ``regex`` / ``exclude`` among the keywords, or a
+        cpu_ref.Automaton (docs/DESIGN.md §4g), the sets follow what the name has emitted so far: the same
+        graph with a per-row state that the sampler advances.  Bad values raise ValueError before anything
+        is launched."""
         ML = self.cfg.max_len
         ctl = None
         cons = cpu_ref.as_constraints(self.cfg, max(n, 0), constraints)
@@ -108,8 +124,8 @@ class HipGenerator:
             dev = [torch.from_numpy(a).to(self.dev) for a in (ctl.inv_temp, ctl.top_k, ctl.top_p, ctl.plen, ctl.prefix)]
             extra = ()
             if cons is not None:
-                tab, idx, rows = self._constraint_tensors(cons)
-                extra = (tab.data_ptr(), idx.data_ptr(), rows)
+                held = self._constraint_tensors(cons)
+                extra = self._constraint_args(held)
             self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s(), *extra)
             err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
             if err:
@@ -154,6 +170,8 @@ class HipGenerator:
             cons = cpu_ref.as_constraints(self.cfg, count, constraints)
             ctl = cpu_ref.make_controls(self.cfg, count, temperature, top_k, top_p, prefix)
             cpu_ref.check_prefix_allowed(cons, ctl.prefix, ctl.plen)
+            if isinstance(cons, cpu_ref.Automaton):   # the rows are known: the host walks them into per-step lines
+                cons = cons.for_rows(self.cfg, rows)
             if cons is not None and self.cfg.vocab // 64 not in (1, 2, 4, 8):
                 raise ValueError(f"constraints need vocab in (64, 128, 256, 512), got {self.cfg.vocab}")
         rows, n_tok, _, _ = cpu_ref.score_inputs(self.cfg, rows)
@@ -175,8 +193,8 @@ class HipGenerator:
             nk = torch.empty(N, ML, dtype=torch.int32, device=self.dev)
             extra = ()
             if cons is not None:
-                tab, idx, lines = self._constraint_tensors(cons)
-                extra = (tab.data_ptr(), idx.data_ptr(), lines)
+                held = self._constraint_tensors(cons)
+                extra = self._constraint_args(held)
             self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s(),
                          *[t.data_ptr() for t in dev], nk.data_ptr(), *extra)
         err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
@@ -193,8 +211,8 @@ class HipGenerator:
         docs/DESIGN.md §4d).  ``prefix``: a string, a list of strings, or None for ``count`` (default 1)
         empty prefixes.  Always exact fp32 arithmetic, whatever ``precision`` this generator samples
         with.  ``constraints`` (a cpu_ref.Constraints for the prefixes, or a dict of
-        cpu_ref.make_constraints keywords; docs/DESIGN.md §4e): the ``width`` most probable rows that
-        satisfy them.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
+        cpu_ref.make_constraints keywords; docs/DESIGN.md §4e; ``regex`` / ``exclude`` or a cpu_ref.Automaton:
+        §4g, a state per beam): the ``width`` most probable rows that satisfy them.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
         raise ValueError before anything is launched."""
         pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
         N, W, ML = pre.shape[0], int(width), self.cfg.max_len
@@ -210,8 +228,8 @@ class HipGenerator:
         nb = torch.empty(N, dtype=torch.int32, device=self.dev)
         extra = ()
         if cons is not None:
-            tab, idx, lines = self._constraint_tensors(cons)
-            extra = (tab.data_ptr(), idx.data_ptr(), lines)
+            held = self._constraint_tensors(cons)
+            extra = self._constraint_args(held)
         self.g.beam(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(), nb.data_ptr(),
                     self._s(), *extra)
         err = self.g.read_error()   # synchronises: the prefix tensors stay alive until the call is done
@@ -363,7 +381,13 @@ def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: i
         if constraints.idx.shape[0] != N:
             raise ValueError(f"constraints for {N} names expected, got {constraints.idx.shape[0]}")
         return constraints.slice(start, count)
-    return {k: _slice_control(v, N, start, count) for k, v in dict(constraints).items()}
+    if isinstance(constraints, cpu_ref.Automaton):
+        if constraints.start.shape[0] != N:
+            raise ValueError(f"constraints for {N} names expected, got {constraints.start.shape[0]}")
+        return constraints.slice(start, count)
+    def one_list(k, v):   # exclude = one list of names for every name of the job, not a per-name value
+        return k == "exclude" and v is not None and all(isinstance(x, (str, bytes)) for x in v)
+    return {k: v if one_list(k, v) else _slice_control(v, N, start, count) for k, v in dict(constraints).items()}
 
 
 def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
@@ -371,8 +395,8 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
     """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
     scalars or one value per name of the job; every rank takes its names' slice.  ``constraints``: a
-    cpu_ref.Constraints for the N names or a dict of make_constraints keywords (docs/DESIGN.md §4e),
-    sliced by global name index like the prefixes."""
+    cpu_ref.Constraints / cpu_ref.Automaton for the N names or a dict of make_constraints keywords
+    (docs/DESIGN.md §4e, §4g: ``regex`` / ``exclude``), sliced by global name index like the prefixes."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len

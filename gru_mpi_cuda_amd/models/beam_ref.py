@@ -157,13 +157,15 @@ def select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced: int, eo
     """Steps 3-5 of the rule for one name in the dtype of ``lp``: the W new beams (parent, chr, state,
     score, next_id, sel = the flat index j) and ``gaps``: the neighbour gaps of the first W + 1
     candidates in order.  ``allowed``: bool [V], the name's constraint set at this step (docs/DESIGN.md
-    §4e; None: everything): a live beam offers only chars in it, a carry is not masked."""
+    §4e; None: everything), or bool [W, V], a set per beam (an automaton's states, §4g): a live beam offers
+    only chars in it, a carry is not masked."""
     W, V = lp.shape
     dt = lp.dtype
-    ok = np.ones(V, bool) if allowed is None else np.asarray(allowed, bool)
+    oks = np.ones(V, bool) if allowed is None else np.asarray(allowed, bool)
     cand = np.full((W, V), -np.inf, dt)
     off = np.zeros((W, V), bool)
     for b in range(W):
+        ok = oks[b] if oks.ndim == 2 else oks
         st = state[b]
         if st == DEAD and mut == "dead_offered":
             st = LIVE
@@ -227,7 +229,7 @@ def _select_all(d: Out, f64: bool, mut: Optional[str] = None) -> Out:
             if forced >= V:
                 forced = 0
         s = select(lp[n], d["score"][n * W:(n + 1) * W].astype(dt), d["state"][n * W:(n + 1) * W], forced, d["eos"], d["sos"], mut,
-                   None if d.get("allowed") is None else d["allowed"][n])      # "allowed": bool [N][V], optional
+                   None if d.get("allowed") is None else d["allowed"][n])      # "allowed": bool [N][V] or [N][W][V], optional
         for k in res:
             res[k].append(s[k])
         clear[n] = _clear(s["gaps"])
@@ -382,6 +384,10 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
     cur = torch.full((N * W,), cfg.sos, dtype=torch.int64)
     clear = np.full((N, ML), np.inf)
     tops = []
+    aut = cons if isinstance(cons, cpu_ref.Automaton) else None
+    if aut is not None:   # §4g: a state per beam, beam 0 in the name's start state
+        alines, astate = aut.lines(), np.zeros((N, W), np.int64)
+        astate[:, 0] = aut.start
     for l in range(ML):
         pre_h = hs
         inp = p["embedding"][cur]
@@ -399,7 +405,8 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
         nstate, nntok = np.zeros_like(state), np.zeros_like(ntok)
         nxt = np.full(N * W, cfg.sos, np.int64)
         step_top = []
-        ok_l = None if cons is None else cons.allowed(l)
+        ok_l = None if cons is None else (alines[astate] if aut is not None else cons.allowed(l))
+        nastate = None if aut is None else np.zeros_like(astate)
         for n in range(N):
             s = select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1, cfg.eos, cfg.sos, mut,
                        None if cons is None else ok_l[n])
@@ -417,10 +424,14 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
                 if c >= 0:
                     nrows[n, k, l] = c
                     nntok[n, k] = l + 1
+                    if aut is not None:   # (a carried or dead beam keeps state 0)
+                        nastate[n, k] = aut.nxt[astate[n, b], c]
                 nxt[n * W + k] = s["next_id"][k]
         g = torch.from_numpy(gather)
         hs = [h[g] for h in (pre_h if mut == "pre_step_h" else new)]
         rows, score, state, ntok = nrows, nscore, nstate, nntok
+        if aut is not None:
+            astate = nastate
         cur = torch.from_numpy(nxt)
         tops.append(step_top)
     return dict(rows=rows, logp=score, n_tok=ntok, n_beams=(state != DEAD).sum(1).astype(np.int32), clear=clear, tops=tops)

@@ -251,6 +251,8 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, to
         cons = as_constraints(cfg, count, constraints)
         ctl = make_controls(cfg, count, temperature, top_k, top_p, prefix)
         check_prefix_allowed(cons, ctl.prefix, ctl.plen)
+        if isinstance(cons, Automaton):   # the rows are known: walk them into per-(row, step) lines (§4g)
+            cons = cons.for_rows(cfg, rows)
     rows, n_tok, x, tgt = score_inputs(cfg, rows)
     N, ML = tgt.shape
     dt = params["fc.weight"].dtype
@@ -596,8 +598,11 @@ def _per_name_obj(v, n: int, what: str) -> list:
     return list(v)
 
 
-def make_constraints(cfg: GRUConfig, count: int, pattern=None, charset=None, min_len=None, max_len=None) -> Constraints:
+def make_constraints(cfg: GRUConfig, count: int, pattern=None, charset=None, min_len=None, max_len=None,
+                     regex=None, exclude=None):
     """Each argument: one value for all ``count`` names or one per name (None: no such constraint).
+    ``regex`` / ``exclude`` (never with ``pattern``): the result is an ``Automaton`` (``make_automaton``
+    below, docs/DESIGN.md §4g) instead of a Constraints object; without them nothing changes.
     ``charset``: the non-EOS chars a name may use (str / bytes; default every char but EOS).  ``pattern``:
     one item per position, no quantifiers -- a literal char, ``\\`` + a literal char, ``.`` (any char of
     charset), ``[abc]`` / ``[a-z]`` / ``[^...]`` classes (a negated class is taken inside charset); P items
@@ -608,6 +613,10 @@ def make_constraints(cfg: GRUConfig, count: int, pattern=None, charset=None, min
     count = int(count)
     if count < 0:
         raise ValueError("count must be >= 0")
+    if regex is not None or exclude is not None:
+        if pattern is not None:
+            raise ValueError("pattern cannot be combined with regex / exclude (write the pattern as a regex)")
+        return make_automaton(cfg, count, regex, exclude, charset, min_len, max_len)
     ML, V = cfg.max_len, cfg.vocab
     cols = [_per_name_obj(v, count, w) for v, w in ((pattern, "pattern"), (charset, "charset"),
                                                     (min_len, "min_len"), (max_len, "max_len"))]
@@ -637,14 +646,19 @@ def make_constraints(cfg: GRUConfig, count: int, pattern=None, charset=None, min
     return Constraints(np.ascontiguousarray(w.astype(np.uint32)), idx, V)
 
 
-def as_constraints(cfg: GRUConfig, count: int, constraints) -> Optional[Constraints]:
-    """None, a Constraints object for ``count`` names, or a dict of make_constraints keywords."""
+def as_constraints(cfg: GRUConfig, count: int, constraints):
+    """None, a Constraints or Automaton object for ``count`` names, or a dict of make_constraints keywords
+    (``regex`` / ``exclude`` among them give an Automaton)."""
+    if isinstance(constraints, Automaton):
+        return _check_automaton(cfg, count, constraints)
     if constraints is None or isinstance(constraints, Constraints):
         c = constraints
     elif isinstance(constraints, dict):
         c = make_constraints(cfg, count, **constraints)
     else:
         raise ValueError("constraints: a Constraints object or a dict of make_constraints keywords expected")
+    if isinstance(c, Automaton):
+        return _check_automaton(cfg, count, c)
     if c is not None:
         if (c.idx.shape != (count, cfg.max_len) or c.tab.ndim != 2 or c.tab.shape[1] != -(-cfg.vocab // 32)
                 or c.vocab != cfg.vocab):
@@ -658,8 +672,19 @@ def as_constraints(cfg: GRUConfig, count: int, constraints) -> Optional[Constrai
 
 
 def check_prefix_allowed(cons: Optional[Constraints], prefix: np.ndarray, plen: np.ndarray) -> None:
-    """ValueError when a forced char is not in its step's set."""
+    """ValueError when a forced char is not in its step's set (an Automaton: when the walk from the
+    name's start state rejects it)."""
     if cons is None or not len(plen) or not plen.any():
+        return
+    if isinstance(cons, Automaton):
+        lines, state = cons.lines(), cons.start.astype(np.int64)
+        for l in range(prefix.shape[1]):
+            c = prefix[:, l].astype(np.int64)
+            bad = (plen > l) & ~lines[state, c]
+            if bad.any():
+                n = int(np.flatnonzero(bad)[0])
+                raise ValueError(f"prefix {n}: char {int(prefix[n, l])} at position {l} is not allowed by the constraint")
+            state = np.where(plen > l, cons.nxt[state, c].astype(np.int64), state)
         return
     ML = prefix.shape[1]
     ok = np.take_along_axis(cons.allowed(), prefix.astype(np.int64)[:, :, None], 2)[:, :, 0]
@@ -667,6 +692,508 @@ def check_prefix_allowed(cons: Optional[Constraints], prefix: np.ndarray, plen: 
     if bad.any():
         n, l = (int(v) for v in np.argwhere(bad)[0])
         raise ValueError(f"prefix {n}: char {int(prefix[n, l])} at position {l} is not allowed by the constraint")
+
+
+# Automaton constraints (docs/DESIGN.md §4g): the allowed set depends on what the name has emitted, not on
+# the step number.  A name carries a state q; its set at a step is line q of ``tab`` and after the step's
+# char c -- sampled, greedy or forced -- the state is nxt[q][c].  Everything else in the rules above is
+# unchanged: Constraints is the special case "state = step".
+#   * state 0 is the free state (line all ones, nxt[0][*] = 0): unconstrained names of a mixed batch;
+#   * nxt[q][eos] = 0, so a finished row, which keeps stepping, stays in range;
+#   * nxt[q][c] = 0 for c outside tab[q]: never taken by the sampler; ``score`` walks known rows on the
+#     host and such a row is -inf at that step whatever follows, so its later steps use line 0;
+#   * the step counter is folded into the state: the builder takes the product of the language DFA with
+#     l = 0 .. max_len and keeps at (q, l) only the chars from whose successor an accepting state is
+#     still reachable within the remaining chars and the length bounds.  EOS is allowed iff q accepts and
+#     l >= min_len, and at l = max_len - 1 (the config's) a char is allowed iff its successor accepts, as
+#     a full-length row has no EOS step.  A name can never reach a dead end.
+# beam: a state per beam; a child's state is nxt[parent's state][c], a carried or dead beam's is 0.
+AUTOMATON_MAX_STATES = 65535
+
+
+class Automaton:
+    """tab uint32 [S, V/32] (the states' allowed sets, the EOS bit set where the state accepts), nxt
+    uint16 [S, V] (the successor), start int32 [count] (the names' start states); S <= 65535."""
+
+    def __init__(self, tab: np.ndarray, nxt: np.ndarray, start: np.ndarray, vocab: Optional[int] = None):
+        self.tab, self.nxt, self.start = tab, nxt, start
+        self.vocab = int(nxt.shape[1]) if vocab is None else int(vocab)
+
+    @property
+    def states(self) -> int:
+        return int(self.tab.shape[0])
+
+    rows = states   # the table's lines, as Constraints.rows
+
+    def lines(self) -> np.ndarray:
+        """The table as bool [S, V]."""
+        bits = (self.tab[:, :, None] >> np.arange(32, dtype=np.uint32)[None, None, :]) & np.uint32(1)
+        return bits.reshape(self.tab.shape[0], -1).astype(bool)[:, :self.vocab]
+
+    def slice(self, start: int, count: int) -> "Automaton":
+        """Names start .. start + count - 1 (the tables are shared)."""
+        return Automaton(self.tab, self.nxt, np.ascontiguousarray(self.start[start:start + count]), self.vocab)
+
+    def for_rows(self, cfg: GRUConfig, rows: np.ndarray) -> Constraints:
+        """The per-(row, step) lines of known output rows, as ``score`` needs them: row n walks from
+        start[n]; after a char outside its set (the row is -inf from there) the later steps use line 0.
+        The lines used are renumbered into a table of their own (ValueError above 1024 distinct ones)."""
+        ML, V = cfg.max_len, cfg.vocab
+        c = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, ML + 1)[:, :ML].astype(np.int64)
+        if c.shape[0] != self.start.shape[0]:
+            raise ValueError(f"constraints for {self.start.shape[0]} rows, {c.shape[0]} rows given")
+        state = self.start.astype(np.int64)
+        idx = np.zeros((c.shape[0], ML), np.int64)
+        for l in range(ML):
+            idx[:, l] = state
+            state = self.nxt[state, np.minimum(c[:, l], V - 1)].astype(np.int64)   # (0 after EOS: the steps past it are masked)
+        seen: Dict[bytes, int] = {self.tab[0].tobytes(): 0}
+        used = np.unique(idx)
+        remap = np.zeros(self.states, np.int32)
+        for u in used:
+            remap[u] = seen.setdefault(self.tab[u].tobytes(), len(seen))
+        if len(seen) > CONSTRAINT_MAX_ROWS:
+            raise ValueError(f"the rows pass through {len(seen)} distinct allowed sets, more than {CONSTRAINT_MAX_ROWS}: "
+                             "score them in smaller groups")
+        tab = np.stack([np.frombuffer(k, dtype=np.uint32) for k in seen])
+        return Constraints(np.ascontiguousarray(tab), remap[idx], V)
+
+
+def _check_automaton(cfg: GRUConfig, count: int, a: Automaton) -> Automaton:
+    words, V = -(-cfg.vocab // 32), cfg.vocab
+    if (a.tab.ndim != 2 or a.tab.shape[1] != words or a.nxt.shape != (a.tab.shape[0], V) or a.start.shape != (count,)
+            or a.vocab != V):
+        raise ValueError(f"constraints: an automaton with tab [S, {words}], nxt [S, {V}] and start [{count}] expected, got "
+                         f"{a.tab.shape}, {a.nxt.shape} and {a.start.shape}")
+    if not 1 <= a.states <= AUTOMATON_MAX_STATES:
+        raise ValueError(f"constraints: 1 .. {AUTOMATON_MAX_STATES} automaton states expected, got {a.states}")
+    if (a.start.size and (a.start.min() < 0 or a.start.max() >= a.states)) or int(a.nxt.max()) >= a.states:
+        raise ValueError("constraints: a start or nxt entry outside the automaton")
+    return a
+
+
+_RX_SPECIAL = frozenset(b"|()*+?{}[]^$")
+
+
+def _parse_regex(rx: bytes, cfg: GRUConfig, cs: np.ndarray):
+    """Regex -> AST: ("set", bool [V]) | ("cat", [..]) | ("alt", [..]) | ("rep", x, m, n or None).  The
+    atoms are ``_parse_pattern``'s (a backslash makes the next byte literal, whatever it is); on top of them
+    groups, ``|``, ``* + ?`` and ``{m} {m,} {m,n}``.  Anchors and ``(?`` forms raise."""
+    n = len(rx)
+    pos = [0]
+
+    def err(msg):
+        raise ValueError(f"regex {rx!r}: {msg}")
+
+    def alt():
+        parts = [cat()]
+        while pos[0] < n and rx[pos[0]] == 0x7C:
+            pos[0] += 1
+            parts.append(cat())
+        return parts[0] if len(parts) == 1 else ("alt", parts)
+
+    def cat():
+        items = []
+        while pos[0] < n and rx[pos[0]] not in (0x7C, 0x29):
+            items.append(rep())
+        return ("cat", items)
+
+    def number():
+        i = pos[0]
+        while pos[0] < n and 0x30 <= rx[pos[0]] <= 0x39:
+            pos[0] += 1
+        return int(rx[i:pos[0]]) if pos[0] > i else None
+
+    def rep():
+        x = atom()
+        if pos[0] < n and rx[pos[0]] in b"*+?{":
+            c = rx[pos[0]]
+            pos[0] += 1
+            if c == 0x2A:
+                x = ("rep", x, 0, None)
+            elif c == 0x2B:
+                x = ("rep", x, 1, None)
+            elif c == 0x3F:
+                x = ("rep", x, 0, 1)
+            else:
+                m = number()
+                if m is None:
+                    err("'{' needs a count ({m}, {m,} or {m,n}; write \\{ for the char)")
+                hi = m
+                if pos[0] < n and rx[pos[0]] == 0x2C:
+                    pos[0] += 1
+                    hi = number()
+                if pos[0] >= n or rx[pos[0]] != 0x7D:
+                    err("a '{' without its '}'")
+                pos[0] += 1
+                if hi is not None and hi < m:
+                    err(f"{{{m},{hi}}} runs backwards")
+                x = ("rep", x, m, hi)
+            if pos[0] < n and rx[pos[0]] in b"*+?{":
+                err("a quantifier after a quantifier (group the first: (a*)?)")
+        return x
+
+    def atom():
+        c = rx[pos[0]]
+        if c == 0x28:
+            if pos[0] + 1 < n and rx[pos[0] + 1] == 0x3F:
+                err("'(?' forms are not supported")
+            pos[0] += 1
+            x = alt()
+            if pos[0] >= n or rx[pos[0]] != 0x29:
+                err("a '(' without its ')'")
+            pos[0] += 1
+            return x
+        i = pos[0]
+        if c == 0x5C:
+            if i + 1 >= n:
+                err("ends in a backslash")
+            pos[0] += 2
+        elif c == 0x5B:
+            j = i + 1
+            if j < n and rx[j] == 0x5E:
+                j += 1
+            while j < n and rx[j] != 0x5D:
+                j += 2 if rx[j] == 0x5C else 1
+            if j >= n:
+                err("a class without its ']'")
+            pos[0] = j + 1
+        elif c in _RX_SPECIAL:
+            err(f"a {chr(c)!r} that is no operator here (anchors are not supported; write \\{chr(c)} for the char)")
+        else:
+            pos[0] += 1
+        try:
+            return ("set", _parse_pattern(rx[i:pos[0]], cfg, cs)[0])
+        except ValueError as e:
+            raise ValueError(str(e).replace("pattern", "regex", 1)) from None
+
+    x = alt()
+    if pos[0] < n:
+        err("a ')' without its '('")
+    return x
+
+
+def _rx_nullable(x) -> bool:
+    if x[0] == "set":
+        return False
+    if x[0] == "cat":
+        return all(_rx_nullable(y) for y in x[1])
+    if x[0] == "alt":
+        return any(_rx_nullable(y) for y in x[1])
+    return x[2] == 0 or _rx_nullable(x[1])
+
+
+def _regex_dfa(rx: bytes, cfg: GRUConfig, cs: np.ndarray):
+    """(delta int32 [Q, V] with -1 = no move, accept bool [Q]) of the regex's language, state 0 the start:
+    Thompson's construction, then the subset construction over the classes of chars that no set of the
+    regex tells apart."""
+    ML, V = cfg.max_len, cfg.vocab
+    ast = _parse_regex(rx, cfg, cs)
+    eps: List[List[int]] = []
+    moves: List[List[Tuple[int, int]]] = []
+    sets: List[np.ndarray] = []
+    set_id: Dict[bytes, int] = {}
+
+    def new() -> int:
+        if len(eps) >= 50000:
+            raise ValueError(f"regex {rx!r} is too large")
+        eps.append([])
+        moves.append([])
+        return len(eps) - 1
+
+    def build(x, a: int) -> int:
+        """x's fragment from state a; returns its end state."""
+        if x[0] == "set":
+            k = set_id.setdefault(x[1].tobytes(), len(sets))
+            if k == len(sets):
+                sets.append(x[1])
+            b = new()
+            moves[a].append((k, b))
+            return b
+        if x[0] == "cat":
+            for y in x[1]:
+                a = build(y, a)
+            return a
+        if x[0] == "alt":
+            b = new()
+            for y in x[1]:
+                s = new()
+                eps[a].append(s)
+                eps[build(y, s)].append(b)
+            return b
+        _, y, m, hi = x
+        # within max_len chars more copies than that only add empty matches: x{m,n} with n >= max(m, ML) is x{m,}
+        if _rx_nullable(y):
+            m = 0
+        elif m > ML:
+            return new()   # too long for any name: a fragment whose end is never reached
+        if hi is not None and hi >= max(m, ML):
+            hi = None
+        for _ in range(m):
+            a = build(y, a)
+        if hi is None:   # star
+            s, b = new(), new()
+            eps[a] += [s, b]
+            eps[build(y, s)] += [s, b]
+            return b
+        b = new()
+        eps[a].append(b)
+        for _ in range(hi - m):
+            a = build(y, a)
+            eps[a].append(b)
+        return b
+
+    s0 = new()
+    end = build(ast, s0)
+    # chars that lie in the same sets move alike
+    if sets:
+        _, cls = np.unique(np.stack(sets).T, axis=0, return_inverse=True)
+        cls = cls.reshape(-1)
+    else:
+        cls = np.zeros(V, np.int64)
+    ncls = int(cls.max()) + 1
+    member = np.zeros((len(sets), ncls), bool)
+    for k, st in enumerate(sets):
+        member[k, cls[st]] = True
+
+    def closure(states) -> frozenset:
+        seen, todo = set(states), list(states)
+        while todo:
+            for t in eps[todo.pop()]:
+                if t not in seen:
+                    seen.add(t)
+                    todo.append(t)
+        return frozenset(seen)
+
+    d0 = closure([s0])
+    ids = {d0: 0}
+    order = [d0]
+    rows = []
+    i = 0
+    while i < len(order):
+        cur = order[i]
+        i += 1
+        tg: List[set] = [set() for _ in range(ncls)]
+        for a in cur:
+            for k, b in moves[a]:
+                for j in np.flatnonzero(member[k]):
+                    tg[j].add(b)
+        row = np.full(ncls, -1, np.int32)
+        for j in range(ncls):
+            if tg[j]:
+                d = closure(tg[j])
+                if d not in ids:
+                    if len(order) >= 200000:
+                        raise ValueError(f"regex {rx!r} needs too many states")
+                    ids[d] = len(order)
+                    order.append(d)
+                row[j] = ids[d]
+        rows.append(row)
+    delta = np.stack(rows)[:, cls]
+    return np.ascontiguousarray(delta), np.array([end in d for d in order])
+
+
+def _exclude_dfa(names, cfg: GRUConfig):
+    """(delta, accept) of "every string but these": the names' trie plus a co-accepting sink (the last
+    state).  Names longer than max_len cannot be emitted anyway and are skipped."""
+    ML, V = cfg.max_len, cfg.vocab
+    kids: List[Dict[int, int]] = [{}]
+    listed = [False]
+    for i, nm in enumerate(names):
+        b = _as_bytes(nm, "exclude name")
+        if any(c >= V for c in b):
+            raise ValueError(f"exclude: name {i} ({nm!r}) holds a byte >= vocab ({V})")
+        if cfg.eos in b:
+            raise ValueError(f"exclude: name {i} ({nm!r}) contains the EOS byte {cfg.eos}")
+        if len(b) > ML:
+            continue
+        q = 0
+        for c in b:
+            t = kids[q].get(c)
+            if t is None:
+                t = kids[q][c] = len(kids)
+                kids.append({})
+                listed.append(False)
+            q = t
+        listed[q] = True
+    T = len(kids)
+    delta = np.full((T + 1, V), T, np.int32)
+    for q, kd in enumerate(kids):
+        for c, t in kd.items():
+            delta[q, c] = t
+    return delta, ~np.array(listed + [False])
+
+
+def _product_dfa(d1, a1, d2, a2):
+    """The intersection of two DFAs (the second total), only the pairs reachable from (0, 0)."""
+    Q2 = d2.shape[0]
+    ids = {0: 0}
+    order = [0]
+    rows = []
+    i = 0
+    while i < len(order):
+        q1, q2 = divmod(order[i], Q2)
+        i += 1
+        n1 = d1[q1].astype(np.int64)
+        key = np.where(n1 >= 0, n1 * Q2 + d2[q2], -1)
+        row = np.full(key.shape, -1, np.int32)
+        for k in np.unique(key[key >= 0]):
+            t = ids.get(int(k))
+            if t is None:
+                t = ids[int(k)] = len(order)
+                order.append(int(k))
+            row[key == k] = t
+        rows.append(row)
+    o = np.array(order)
+    return np.stack(rows), a1[o // Q2] & a2[o % Q2]
+
+
+def _name_automaton(cfg: GRUConfig, regex, exclude, charset, min_len, max_len):
+    """One name's states: (sets bool [S, V], nxt int32 [S, V] with local numbers, -1 = none); state 0 is
+    (start, step 0).  The product of the language DFA with the step counter, pruned so that no state is
+    a dead end."""
+    ML, V, eos = cfg.max_len, cfg.vocab, cfg.eos
+    if not 0 <= eos < V:
+        raise ValueError(f"eos {eos} outside the vocabulary of {V}")
+    cs = np.ones(V, bool)
+    if charset is not None:
+        b = np.frombuffer(_as_bytes(charset, "charset"), dtype=np.uint8)
+        if (b >= V).any():
+            raise ValueError(f"charset names a byte >= vocab ({V})")
+        if (b == eos).any():
+            raise ValueError(f"charset names the EOS byte {eos} (lengths are set by min_len / max_len)")
+        cs[:] = False
+        cs[b] = True
+    cs[eos] = False
+    lo = 0 if min_len is None else int(min_len)
+    hi = ML if max_len is None else int(max_len)
+    if lo < 0 or hi < 0 or hi > ML:
+        raise ValueError(f"min_len >= 0 and 0 <= max_len <= {ML} expected, got {min_len!r} and {max_len!r}")
+    if regex is None:   # charset*
+        delta, acc = np.where(cs, 0, -1).astype(np.int32)[None, :], np.ones(1, bool)
+    else:
+        delta, acc = _regex_dfa(_as_bytes(regex, "regex"), cfg, cs)
+    if exclude is not None:
+        delta, acc = _product_dfa(delta, acc, *_exclude_dfa(exclude, cfg))
+    what = f"(regex {regex!r}, {0 if exclude is None else len(exclude)} excluded, charset {charset!r}, min_len {lo}, max_len {hi})"
+    # ok[l][q]: from q after l chars a name can still end within the bounds
+    dc = np.maximum(delta, 0)
+    ok = [None] * (hi + 1)
+    ok[hi] = acc & (hi >= lo)
+    for l in range(hi - 1, -1, -1):
+        ok[l] = (acc & (l >= lo)) | ((delta >= 0) & ok[l + 1][dc]).any(1)
+    if not ok[0][0]:
+        raise ValueError(f"no name is allowed {what}")
+    sets, nxts = [], []
+    front, base = np.array([0]), 0
+    for l in range(hi + 1):
+        if l >= ML:   # (hi == ML) a full-length row has no EOS step
+            break
+        s = np.zeros((len(front), V), bool)
+        nx = np.full((len(front), V), -1, np.int64)
+        if l < hi:
+            d = delta[front]
+            s = (d >= 0) & ok[l + 1][np.maximum(d, 0)]
+            if l + 1 < ML and l + 1 <= hi:
+                nfront = np.unique(d[s])
+                nx = np.where(s, base + len(front) + np.searchsorted(nfront, np.where(s, d, nfront[0] if len(nfront) else 0)), -1)
+            else:
+                nfront = np.zeros(0, np.int64)
+        else:
+            nfront = np.zeros(0, np.int64)
+        s[:, eos] = acc[front] & (l >= lo)
+        sets.append(s)
+        nxts.append(nx)
+        base += len(front)
+        front = nfront
+        if not len(front):
+            break
+    return np.concatenate(sets), np.concatenate(nxts)
+
+
+def _pack_lines(bits: np.ndarray, V: int) -> np.ndarray:
+    words = -(-V // 32)
+    bits = np.concatenate([bits, np.zeros((bits.shape[0], words * 32 - V), bool)], 1)
+    w = (bits.reshape(bits.shape[0], words, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)
+    return np.ascontiguousarray(w.astype(np.uint32))
+
+
+def _merge_states(tab: np.ndarray, nxt: np.ndarray, start: np.ndarray):
+    """States with equal (line, successor row) are one state; repeated until nothing merges.  State 0
+    stays state 0 (the survivors keep their order of first appearance)."""
+    mix = np.random.default_rng(0).integers(1, 2 ** 62, tab.shape[1] + nxt.shape[1], dtype=np.int64) | 1
+    while True:
+        key = np.concatenate([tab.astype(np.int64), nxt], 1)
+        with np.errstate(over="ignore"):
+            h = (key * mix).sum(1)   # a hash first (wrapping int64): sorting whole rows is slow for a large trie
+        _, first, inv = np.unique(h, return_index=True, return_inverse=True)
+        if not (key == key[first[inv.reshape(-1)]]).all():   # a collision: the exact way
+            _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        if len(first) == tab.shape[0]:
+            return tab, nxt, start
+        order = np.argsort(first)
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        inv, first = rank[inv.reshape(-1)], first[order]
+        tab, nxt, start = tab[first], inv[nxt[first]], inv[start]
+
+
+def _exclude_key(v):
+    if v is None:
+        return None
+    return tuple(sorted({_as_bytes(x, "exclude name") for x in v}))
+
+
+def make_automaton(cfg: GRUConfig, count: int, regex=None, exclude=None, charset=None, min_len=None,
+                   max_len=None) -> Automaton:
+    """``make_constraints(regex=, exclude=)``.  ``regex`` (str / bytes over latin-1 bytes, matched against the
+    whole name): ``_parse_pattern``'s atoms -- literals, ``\\c``, ``.`` and classes, ``.`` and negated classes
+    inside charset -- plus groups ``( )``, alternation ``|`` and the quantifiers ``* + ? {m} {m,} {m,n}``: a
+    subset of Python ``re`` (but for ``\\`` before a letter or digit, which is that byte here).  ``exclude``: a
+    list of names none of which may be generated (one list for every name, or a list of lists / None
+    per name; names longer than cfg.max_len are skipped).  They combine with each other -- the
+    intersection -- and with ``charset`` (alone: the chars a name without a regex may use), ``min_len`` and
+    ``max_len``.  A name with none of the five is free (state 0).  ValueError for a language that is empty
+    within the bounds, a byte >= vocab, the EOS byte in the regex, charset or a listed name, a malformed
+    regex and more than 65535 states after merging."""
+    count = int(count)
+    ML, V = cfg.max_len, cfg.vocab
+    if exclude is not None and not isinstance(exclude, (str, bytes)) and all(isinstance(x, (str, bytes)) for x in exclude):
+        ex = [_exclude_key(exclude)] * count
+        ex_single = True
+    elif exclude is None:
+        ex, ex_single = [None] * count, True
+    else:
+        if isinstance(exclude, (str, bytes)):
+            raise ValueError("exclude: a list of names expected")
+        if len(exclude) != count:
+            raise ValueError(f"exclude: one list of names or {count} lists expected, got {len(exclude)}")
+        ex, ex_single = [_exclude_key(x) for x in exclude], False
+    given = ((regex, "regex"), (charset, "charset"), (min_len, "min_len"), (max_len, "max_len"))
+    cols = [_per_name_obj(v, count, w) for v, w in given]
+    if count == 0 and ex_single and all(v is None or isinstance(v, (str, bytes)) or np.ndim(v) == 0 for v, _ in given):
+        _name_automaton(cfg, regex, _exclude_key(exclude), charset, min_len, max_len)   # still validate single values
+    sets = [np.ones((1, V), bool)]
+    nxts = [np.zeros((1, V), np.int64)]
+    total = 1
+    first: Dict[tuple, int] = {}
+    start = np.zeros(count, np.int64)
+    for n in range(count):
+        key = tuple(None if v is None else (_as_bytes(v, "regex / charset") if isinstance(v, (str, bytes)) else int(v))
+                    for v in (cols[0][n], cols[1][n], cols[2][n], cols[3][n])) + (ex[n],)
+        if all(v is None for v in key):
+            continue   # a free name: state 0
+        if key not in first:
+            s, nx = _name_automaton(cfg, key[0], key[4], key[1], key[2], key[3])
+            first[key] = total
+            sets.append(s)
+            nxts.append(np.where(nx >= 0, nx + total, 0))
+            total += s.shape[0]
+        start[n] = first[key]
+    tab, nxt, start = _merge_states(_pack_lines(np.concatenate(sets), V), np.concatenate(nxts), start)
+    if tab.shape[0] > AUTOMATON_MAX_STATES:
+        raise ValueError(f"{tab.shape[0]} automaton states, more than {AUTOMATON_MAX_STATES}")
+    return Automaton(tab, np.ascontiguousarray(nxt.astype(np.uint16)), np.ascontiguousarray(start.astype(np.int32)), V)
 
 
 def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray,
@@ -777,6 +1304,9 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
     hs = [torch.zeros(N, H, dtype=dt) for _ in range(cfg.layers)]
     cur = torch.full((N,), cfg.sos, dtype=torch.int64)
     alive = torch.ones(N, dtype=torch.bool)
+    aut = cons if isinstance(cons, Automaton) else None
+    if aut is not None:   # §4g: the set is the line of the name's state, which advances with the chosen char
+        alines, astate = aut.lines(), aut.start.astype(np.int64)
     for l in range(ML):
         inp = params["embedding"][cur]
         for k in range(cfg.layers):
@@ -791,10 +1321,12 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
             prob = torch.softmax(logits, -1)
             sel = sample_inverse_cdf(prob, rf[:, l].to(prob.dtype))
         else:
-            sel = sample_controlled(logits, rf[:, l], controls=ctl,
-                                    allowed=None if cons is None else cons.allowed(l))
+            allowed = None if cons is None else (alines[astate] if aut is not None else cons.allowed(l))
+            sel = sample_controlled(logits, rf[:, l], controls=ctl, allowed=allowed)
             forced = torch.from_numpy(ctl.plen > l)
             sel = torch.where(forced, torch.from_numpy(ctl.prefix[:, l].astype(np.int64)), sel)
+            if aut is not None:   # every step, a forced one and a finished row's included (nxt[q][eos] = 0)
+                astate = aut.nxt[astate, sel.numpy()].astype(np.int64)
         out[alive.numpy(), l] = sel[alive].numpy().astype(np.uint8)
         alive &= sel != cfg.eos
         cur = sel
@@ -869,13 +1401,14 @@ def beam_inputs(cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int
 def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_char: int = -1, allowed=None):
     """Steps 3-4 for one name: lp [W, V], score [W], state [W] -> the W new beams in order as (parent,
     chr, score, j), parent -1 for a dead slot, chr -1 for a carry or a dead slot.  ``allowed``: bool [V],
-    the name's set at this step (None: everything): a live beam offers only chars in it, carries are
-    not masked."""
+    the name's set at this step (None: everything), or bool [W, V], a set per beam: a live beam offers
+    only chars in it, carries are not masked."""
     W, V = lp.shape
     cand = np.full((W, V), -np.inf, dtype=lp.dtype)
     offered = np.zeros((W, V), dtype=bool)
-    ok = np.ones(V, bool) if allowed is None else np.asarray(allowed, dtype=bool)
+    oks = np.ones(V, bool) if allowed is None else np.asarray(allowed, dtype=bool)
     for b in range(W):
+        ok = oks[b] if oks.ndim == 2 else oks   # [W, V]: a set per beam (an Automaton, §4g)
         if state[b] == BEAM_LIVE:
             if forced_char >= 0:
                 if ok[forced_char]:
@@ -928,6 +1461,10 @@ def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.n
     state[:, 0] = BEAM_LIVE
     hs = [torch.zeros(N * W, H, dtype=dt) for _ in range(cfg.layers)]
     cur = torch.full((N * W,), cfg.sos, dtype=torch.int64)
+    aut = cons if isinstance(cons, Automaton) else None
+    if aut is not None:   # §4g: a state per beam; beam 0 starts in the name's start state, carried and dead beams sit in 0
+        alines, astate = aut.lines(), np.zeros((N, W), np.int64)
+        astate[:, 0] = aut.start
     for l in range(ML):
         inp = params["embedding"][cur]
         for k in range(cfg.layers):
@@ -939,12 +1476,13 @@ def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.n
         if dt != torch.float64:
             logits = logits.to(torch.float32)
         lp = torch.log_softmax(logits, -1).numpy().reshape(N, W, V)
+        nastate = None if aut is None else np.zeros_like(astate)
         gather = np.zeros(N * W, np.int64)
         nrows, nscore, nstate, nntok = np.zeros_like(rows), np.full_like(score, -np.inf), np.zeros_like(state), np.zeros_like(ntok)
         nxt = np.full(N * W, cfg.sos, np.int64)
         for n in range(N):
             sel = beam_select(lp[n], score[n], state[n], int(pre[n, l]) if l < plen[n] else -1,
-                              None if cons is None else cons.allowed(l)[n])
+                              None if cons is None else (alines[astate[n]] if aut is not None else cons.allowed(l)[n]))
             for k, (b, c, s, _) in enumerate(sel):
                 if b < 0:
                     continue
@@ -957,11 +1495,15 @@ def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.n
                     continue
                 nrows[n, k, l] = c
                 nntok[n, k] = l + 1
+                if aut is not None:
+                    nastate[n, k] = aut.nxt[astate[n, b], c]
                 nstate[n, k] = BEAM_FIN if c == cfg.eos else BEAM_LIVE
                 if c != cfg.eos:
                     nxt[n * W + k] = c
         g = torch.from_numpy(gather)
         hs = [h[g] for h in hs]
         rows, score, state, ntok = nrows, nscore, nstate, nntok
+        if aut is not None:
+            astate = nastate
         cur = torch.from_numpy(nxt)
     return BeamResult(rows, score, ntok, (state != BEAM_DEAD).sum(1).astype(np.int32), cfg.eos)
