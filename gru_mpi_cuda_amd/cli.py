@@ -243,6 +243,10 @@ def cmd_generate(args) -> int:
         ctl["prefix"] = [pres[i % len(pres)] for i in range(N)]   # cycled over the names
     if _constraints_from(args) is not None:
         ctl["constraints"] = _constraints_from(args)
+    if args.persist_constraints is not None:
+        if args.persist_constraints < 0:
+            raise SystemExit("--persist-constraints needs a count >= 0")
+        ctl["persist_constraints"] = args.persist_constraints
     ctx = None
     if args.cpu:
         from .parallel.dist import DistCtx
@@ -516,6 +520,9 @@ def main(argv=None) -> int:
     g.add_argument("--prefix-file", dest="prefix_file", default=None,
                    help="one prefix per line, cycled over the names")
     _constraint_args(g)
+    g.add_argument("--persist-constraints", dest="persist_constraints", type=int, nargs="?", const=64, default=None,
+                   metavar="N", help="constrained batches of up to N names (bare flag: 64) run as one constrained "
+                                     "persistent launch instead of the per-char graph (opt-in; docs/DESIGN.md §4e)")
     g.add_argument("--exclude-emitted", dest="exclude_emitted", action="store_true",
                    help="distinct names: every batch's names are excluded from the later batches")
     g.add_argument("--emit-batch", dest="emit_batch", type=int, default=256,

@@ -263,6 +263,9 @@ PYBIND11_MODULE(_C, m) {
       .def("uses_persist", &Generator::uses_persist)
       .def("uses_persist_ctl", &Generator::uses_persist_ctl)
       .def("set_persist_ctl_max", &Generator::set_persist_ctl_max)
+      .def("uses_persist_con", &Generator::uses_persist_con)
+      .def("set_persist_con_max", &Generator::set_persist_con_max)
+      .def("persist_con_launches", &Generator::persist_con_launches)
       .def("set_global_names", &Generator::set_global_names)
       .def("inject_persist_error", &Generator::inject_persist_error)
       .def("dump_graph", &Generator::dump_graph);
@@ -784,6 +787,8 @@ PYBIND11_MODULE(_C, m) {
   // reset and the scorer's two kernels
   m.def("gen_persist_supported", &gen_persist_supported);
   m.def("gen_persist_ctl_supported", &gen_persist_ctl_supported);
+  m.def("gen_persist_con_supported", &gen_persist_con_supported);
+  m.def("gen_persist_con_bytes", []() { return (long)sizeof(GenPersistCon); });
   m.def("gen_persist_ws_floats", &gen_persist_ws_floats);
   m.def("gen_persist_sync_words", &gen_persist_sync_words);
   m.def("gen_persist_fill_ws", [](uintptr_t ws, int H, int L, int V, int ML, uintptr_t s) {
@@ -810,6 +815,21 @@ PYBIND11_MODULE(_C, m) {
     a.inv_temp = GP(const float, d, "inv_temp"); a.top_k = GP(const int, d, "top_k");
     a.top_p = GP(const float, d, "top_p"); a.plen = GP(const int, d, "plen");
     a.prefix = GP(const unsigned char, d, "prefix");
+    // constraints (SampleCtlArgs' fields and rules: gen_persist_con_mode throws on an inconsistent set):
+    // stored into the caller's device struct `con` (gen_persist_con_bytes) in stream order, then the launch
+    GenPersistCon h;
+    h.allow_tab = GP(const unsigned, d, "allow_tab"); h.allow_idx = GP(const int, d, "allow_idx");
+    h.allow_next = GP(const unsigned short, d, "allow_next"); h.allow_start = GP(const int, d, "allow_start");
+    h.allow_state = GP(int, d, "allow_state"); h.allow_rows = get<int>(d, "allow_rows", 0);
+    a.con_mode = gen_persist_con_mode(h);
+    if (a.con_mode != kGenConNone) {
+      GenPersistCon* dev = GP(GenPersistCon, d, "con");
+      if (!dev) throw std::runtime_error("gen_persist: a constrained launch needs `con`, gen_persist_con_bytes() of device memory");
+      if (!a.inv_temp || !a.top_k || !a.top_p || !a.plen || !a.prefix)
+        throw std::runtime_error("gen_persist: constraints go with the five sampling controls");
+      gen_persist_con_store(dev, h, S(s));
+      a.con = dev;
+    }
     gen_persist_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });

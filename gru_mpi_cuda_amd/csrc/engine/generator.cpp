@@ -62,6 +62,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   const char* gp = std::getenv("GK_GEN_PERSIST");
   if (gp && gp[0] == '0') persist_ = false;
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CTL_MAX")) persist_ctl_max_ = std::atoi(cm);
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_CON_MAX")) persist_con_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -80,7 +81,14 @@ bool Generator::uses_persist_ctl(int n) const {
   return persist_ && d_.fp32 && n <= persist_ctl_max_ && gen_persist_ctl_supported(d_.H, d_.L, d_.V, n, d_.max_len);
 }
 
+bool Generator::uses_persist_con(int n, bool automaton) const {
+  // opt-in (persist_con_max_ = 0 by default): docs/DESIGN.md §4e has the reason
+  return uses_persist_ctl(n) && n <= persist_con_max_ &&
+         gen_persist_con_supported(d_.H, d_.L, d_.V, n, d_.max_len, automaton ? kGenConAuto : kGenConMask);
+}
+
 Generator::~Generator() {
+  if (pcon_) (void)hipFree(pcon_);
   graphs_.clear();
   sgraphs_.clear();
   scgraphs_.clear();
@@ -298,6 +306,17 @@ bool Generator::persist_launch(const float* rf, int n, const Ctl* c, unsigned ch
   a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_; a.probs = probe_;
   a.rf = rf; a.out = out;
   if (c) { a.inv_temp = c->inv_temp; a.top_k = c->top_k; a.top_p = c->top_p; a.plen = c->plen; a.prefix = c->prefix; }
+  if (c && c->allow_tab) {   // constrained: the device struct, stored in stream order ahead of the launch
+    GenPersistCon h;
+    h.allow_tab = c->allow_tab; h.allow_idx = c->allow_idx; h.allow_next = c->allow_next; h.allow_start = c->allow_start;
+    h.allow_rows = c->allow_rows;
+    a.con_mode = gen_persist_con_mode(h);
+    // (the first such launch allocates; the previous persistent launch has been waited for -- its error
+    // read-back below -- so nothing on any stream still reads the struct)
+    if (!pcon_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pcon_), sizeof(GenPersistCon)));
+    gen_persist_con_store(pcon_, h, s);
+    a.con = pcon_;
+  }
   a.ws = pws_; a.sync = psync_; a.err = err_; a.dbg = persist_dbg_;
   if (ppar_ < 0) {   // first launch: both sets' tagged slots -> kEmpty; later launches refill in-kernel
     gen_persist_fill_ws(pws_, d_.H, d_.L, d_.V, ML, s);
@@ -316,6 +335,7 @@ bool Generator::persist_launch(const float* rf, int n, const Ctl* c, unsigned ch
     inject_ = false;
   }
   gen_persist_f32(a, s);
+  if (a.con) ++persist_con_launches_;
   // small batch, latency-bound launch: check its error word now.  A spin timeout means the
   // workgroups were not co-resident (something else held CUs): the batch's output is garbage,
   // so say so, stop using the persistent path and regenerate the batch on the per-char graph.
@@ -421,23 +441,39 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
     throw std::runtime_error("Generator::generate_ctl: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   const int ML = d_.max_len;
-  if (aut) {   // before the error word is cleared: growing the buffers synchronises
+  // a batch that takes the constrained persistent launch reads the caller's tables in place: a call made
+  // of such batches alone stages nothing and allocates nothing
+  bool graph_batch = false;
+  for (int start = 0; start < N; start += Bmax_)
+    if (!(masked && uses_persist_con(std::min(Bmax_, N - start), aut))) graph_batch = true;
+  bool aut_staged = false;
+  if (aut && graph_batch) {   // before the error word is cleared: growing the buffers synchronises
     ctl_alloc();
     automaton_stage(c.allow_tab, c.allow_next, c.allow_rows, s);
+    aut_staged = true;
   }
   if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   bool tab_staged = false;
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
-    // (a constrained batch never: the persistent variants have no mask, docs/DESIGN.md §4e)
-    if (!masked && uses_persist_ctl(n)) {   // one controlled launch on the caller's arrays at this batch's rows
+    // (a constrained batch only where the caller opted in: uses_persist_con, docs/DESIGN.md §4e)
+    if (masked ? uses_persist_con(n, aut) : uses_persist_ctl(n)) {   // one launch on the caller's arrays at this batch's rows
       Ctl b;
       b.inv_temp = c.inv_temp + start; b.top_k = c.top_k + start; b.top_p = c.top_p + start; b.plen = c.plen + start;
       b.prefix = c.prefix + (size_t)start * ML;
+      if (masked) {   // table and next by pointer; idx and start at the batch's rows
+        b.allow_tab = c.allow_tab; b.allow_rows = c.allow_rows; b.allow_next = c.allow_next;
+        if (aut) b.allow_start = c.allow_start + start;
+        else b.allow_idx = c.allow_idx + (size_t)start * ML;
+      }
       if (persist_launch(rf + (size_t)start * ML, n, &b, out + (size_t)start * (ML + 1), start + n >= N, s)) continue;
     }
     ctl_alloc();   // first batch on this path: allocates (and synchronises) before anything is captured
+    if (aut && !aut_staged) {   // (a constrained persistent launch hit its spin limit: the graph after all)
+      automaton_stage(c.allow_tab, c.allow_next, c.allow_rows, s);
+      aut_staged = true;
+    }
     HIP_CHECK(hipMemcpyAsync(rf_, rf + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     // this batch's slice of every control array: the graph reads rows 0 .. n - 1 of the buffers
     HIP_CHECK(hipMemcpyAsync(cinv_, c.inv_temp + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));

@@ -42,9 +42,11 @@ class Generator {
   // of an arena of their own (allocated by the first batch that takes it) into which each batch's
   // slice is copied, so one recording per n serves every value.
   // Constraints (docs/DESIGN.md §4e; allow_tab [allow_rows][V / 32] and allow_idx [N][max_len], device
-  // pointers, both or neither, allow_rows <= kAllowRows): every batch of a constrained call takes the
-  // per-char graph -- the persistent variants have no mask -- in a recording of its own per n, whose
-  // sampler reads the table and the batch's idx slice from two more buffers of that arena.
+  // pointers, both or neither, allow_rows <= kAllowRows): a batch of a constrained call takes the
+  // per-char graph in a recording of its own per n, whose sampler reads the table and the batch's idx
+  // slice from two more buffers of that arena -- unless uses_persist_con(n, automaton) holds (opt-in,
+  // off by default): then ONE constrained persistent launch on the caller's arrays, the table and
+  // `next` by pointer, idx and start at the batch's rows: no staging, no arena, no recording.
   struct Ctl {
     const float* inv_temp = nullptr; const int* top_k = nullptr; const float* top_p = nullptr;
     const int* plen = nullptr; const unsigned char* prefix = nullptr;
@@ -69,6 +71,12 @@ class Generator {
   // exists (gen_persist_ctl_supported); off with GK_GEN_PERSIST=0 or set_persist(false)
   bool uses_persist_ctl(int n) const;
   void set_persist_ctl_max(int n) { persist_ctl_max_ = n; }
+  // Constrained generate_ctl() batches of n names run as one constrained persistent launch: up to
+  // GK_GEN_PERSIST_CON_MAX / set_persist_con_max(n) names -- 0 by default, the path is opt-in
+  // (docs/DESIGN.md §4e) -- where uses_persist_ctl(n) holds and a constrained variant of the mode exists
+  bool uses_persist_con(int n, bool automaton) const;
+  void set_persist_con_max(int n) { persist_con_max_ = n; }
+  long persist_con_launches() const { return persist_con_launches_; }   // constrained persistent launches so far
   // Teacher-forced scoring of N output rows (device [N][max_len+1], the generate() format): per token
   // log softmax(logits)[target] and the target's rank, per name their sum and the token count (all
   // device pointers: tok_logp / rank [N][max_len], name_logp / n_tok [N]).  Always the exact-fp32
@@ -141,8 +149,8 @@ class Generator {
   void reset_batch(int Bp, bool bf16, hipStream_t s);
   void score_alloc();
   void ctl_alloc();
-  // one persistent launch for n names (c: the controlled one, its arrays already at this batch's rows)
-  // and its error-word read-back.  false: the launch hit its spin limit -- the persistent path is now
+  // one persistent launch for n names (c: the controlled one, its arrays already at this batch's rows;
+  // with c->allow_tab the constrained one) and its error-word read-back.  false: the launch hit its spin limit -- the persistent path is now
   // off, the bit is cleared and the caller regenerates the batch on its per-char graph
   bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
   // ctl: score_ctl_logprob_f32 as the last launch; allow_rows > 0: with the constraint buffers
@@ -184,6 +192,12 @@ class Generator {
   int global_n_ = 0;            // set_global_names
   int persist_max_ = 64;        // names per batch up to which the persistent launch is used
   int persist_ctl_max_ = 64;    // ... with sampling controls (GK_GEN_PERSIST_CTL_MAX)
+  int persist_con_max_ = 0;     // ... with constraints (GK_GEN_PERSIST_CON_MAX): opt-in
+  long persist_con_launches_ = 0;
+  // the constrained launch's device struct (plain allocation, made by the first such launch).  Written
+  // in stream order before its launch; every persistent launch ends with its error-word read-back, so
+  // no earlier launch can still read it when the next one's store is queued
+  GenPersistCon* pcon_ = nullptr;
   int persist_max_bf16_ = 40;   // ... in the bf16 mode (it runs exact fp32, faster up to ~40 names:
                                 // profiles/r5_gen_persist_vs_bf16_graph_final.jsonl)
   unsigned long long* persist_dbg_ = nullptr;

@@ -21,7 +21,7 @@
 // A third copy scores rows under this distribution: score_ctl_logprob_f32_kernel (score_ctl.hip,
 // tests/test_score_ctl_gpu.py).
 //
-// Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy has none): a row's
+// Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy's: MASKED, gen_sample_ctl.h): a row's
 // allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one
 // 32-bit word of that line -- one load per lane and row -- and a masked char takes y = -inf after the
 // temperature scale and is in no kept set.  MASK = false is the kernel as it was.

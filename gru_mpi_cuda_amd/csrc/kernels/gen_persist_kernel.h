@@ -68,8 +68,8 @@
 // Reference: the per-char loop of /root/reference/namegensf.cu:661-884, for all names at once.
 //
 // This header is the kernel; gen_persist.hip instantiates the plain variants and holds the host
-// side, gen_persist_ctl.hip instantiates the controlled ones (a translation unit of their own: the
-// two compile side by side).
+// side, gen_persist_ctl.hip instantiates the controlled ones and gen_persist_con.hip the constrained
+// ones (translation units of their own: the three compile side by side).
 #pragma once
 #include <stdexcept>
 #include "kernels.h"
@@ -299,11 +299,11 @@ template <int B_, int E_, class F> DEV void static_for(F&& f) {
 }
 
 // the controlled variants' per-name scalar controls in LDS: [0] inv_temp, [1] top_k, [2] top_p,
-// [3] plen (as words).  A plain variant allocates nothing.
-template <bool CTL>
+// [3] plen (as words); the automaton variants add [4], the name's state.  A plain variant allocates nothing.
+template <bool CTL, int ROWS>
 DEV unsigned (*ctl_lds())[kNmax] {
   if constexpr (CTL) {
-    __shared__ unsigned s[4][kNmax];
+    __shared__ unsigned s[ROWS][kNmax];
     return s;
   } else {
     return nullptr;
@@ -311,9 +311,17 @@ DEV unsigned (*ctl_lds())[kNmax] {
 }
 
 // CTL: sampling controls (a.inv_temp .. a.prefix set), with the sampler instance for PER = V / 64
-// values per lane only; plain variants (CTL = false, PER = 0) hold both instances
-template <int KJ, int L, bool CTL = false, int PER_CTL = 0>
+// values per lane only; plain variants (CTL = false, PER = 0) hold both instances.
+// CON (with CTL; gen_persist_con.hip, docs/DESIGN.md §4e / §4g): kConMask -- name n's set at char t - 1
+// is table line a.con->allow_idx[n ML + t - 1]; kConAuto -- the line is the name's automaton state, a
+// fifth row of the LDS control block that every sampler of the name advances after its pick.  Only
+// what happens between "the logits are in registers" and the pick differs from CON = 0 (plus one LDS
+// word and one 2-byte load after it): every wait, poll, publish and their order are the plain kernel's.
+// The fields of *a.con are read where they are used, never kept across the sampler.
+constexpr int kConNone = 0, kConMask = 1, kConAuto = 2;
+template <int KJ, int L, bool CTL = false, int PER_CTL = 0, int CON = kConNone>
 __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
+  static_assert(CON == kConNone || CTL, "a constrained variant is a controlled one");
   constexpr int U = KJ / 8, H = 32 * KJ, KW = H / 8, NT = 2 * L - 1, R3 = 3 * U;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fr = lane & 15, q4 = lane >> 4;
@@ -400,13 +408,14 @@ __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
     if (tid == 0 && ML < kStampT) sStamp[ML][14] = t_entry;   // (row ML has no layer phases)
   }
   if (tid < kNmax) { sid[tid] = a.sos; sal[tid] = tid < N ? 1 : 0; }
-  unsigned (*const sctl)[kNmax] = ctl_lds<CTL>();
+  unsigned (*const sctl)[kNmax] = ctl_lds<CTL, (CON == kConAuto ? 5 : 4)>();
   if constexpr (CTL) {   // once per launch: four dependent global loads per name and char otherwise
     if (tid < N) {
       sctl[0][tid] = __float_as_uint(a.inv_temp[tid]);
       sctl[1][tid] = (unsigned)a.top_k[tid];
       sctl[2][tid] = __float_as_uint(a.top_p[tid]);
       sctl[3][tid] = (unsigned)a.plen[tid];
+      if constexpr (CON == kConAuto) sctl[4][tid] = (unsigned)a.con->allow_start[tid];
     }
   }
   if (dist ? b < N : b == 0)   // each output row has one writer: its sampler (every row: workgroup 0)
@@ -702,10 +711,48 @@ __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
             forced = 0;
           }
         }
+        unsigned ok = 0u;   // CON: bit e = this lane's char e is in the name's set (dead before the top-k search)
+        if constexpr (CON != kConNone) {
+          // the name's table line, a uniform value read on every step of every name, alive or not.  One
+          // outside the table is flagged by the name's single writer and taken as line 0: no address is
+          // formed from it
+          int line;
+          if constexpr (CON == kConAuto) line = __builtin_amdgcn_readfirstlane((int)sctl[4][n]);
+          else line = __builtin_amdgcn_readfirstlane(a.con->allow_idx[(size_t)opaque_s(n) * ML + (t - 1)]);
+          if (line < 0 || line >= a.con->allow_rows) {
+            if (lane == 0) {
+              if (dist || b == 0) {
+                __hip_atomic_fetch_or(a.err, 16u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                a.err[1] = (unsigned)line;
+                a.err[2] = (unsigned)n;
+              }
+              if constexpr (CON == kConAuto) sctl[4][n] = 0u;   // the walk continues from state 0
+            }
+            line = 0;
+          }
+          if (forced < 0)   // a forced step reads no mask
+            ok = a.con->allow_tab[(size_t)line * (V >> 5) + ((lane * PER) >> 5)] >> ((lane * PER) & 31);
+        }
         const float it = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[0][n]));
         const int tk = __builtin_amdgcn_readfirstlane((int)sctl[1][n]);
         const float tp = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[2][n]));
-        return ctl_sample_wave<PER>(xv, V, rnd, prow, it, tk, tp, forced);
+        const int sel = ctl_sample_wave<PER, CON != kConNone>(xv, V, rnd, prow, it, tk, tp, forced, ok);
+        if constexpr (CON == kConAuto) {
+          // after every pick, a forced one included: state <- next[state][sel], the state re-read from LDS
+          // (in range: checked above) instead of held across the sampler; 0 <= sel < V on every branch
+          // (the struct through a vector register: the sampler's arrays are dead here, while the scalar
+          // file is what the variants at the 256-VGPR cap have none left of)
+          if (lane == 0) {
+            const GenPersistCon* cp = a.con;
+            asm volatile("" : "+v"(cp));
+            const unsigned q = sctl[4][n];
+            const unsigned nx = cp->allow_next[(size_t)q * V + sel];
+            sctl[4][n] = nx;
+            int* const st = cp->allow_state;
+            if ((dist || b == 0) && st) st[n] = (int)nx;
+          }
+        }
+        return sel;
       } else {
         return softmax_sample_wave(xv, PER, V, rnd, prow);
       }

@@ -37,9 +37,15 @@ DEV void ctl_one_hot(float* prow, int sel) {
 // (0: greedy), top_k (<= 0 or >= V: off), top_p (>= 1: off), forced (>= 0: this char, nothing else is
 // looked at).  Returns the chosen index, identical in every lane; prow (nullable) gets the
 // renormalised filtered row, one-hot for a forced or greedy char.
-template <int PER>
+//
+// MASKED (the constrained variants, gen_persist_con.hip; docs/DESIGN.md §4e / §4g): bit e of `ok` = char
+// lane * PER + e is in the row's set.  An entry outside it is -inf after the temperature scale, so it is
+// filtered like any other; and, as in gen_ctl.hip's MASK instantiations, only a kept char is a hit of
+// the CDF search (a lane past the last kept char can hold a running sum one ulp above an earlier
+// lane's).  A forced step does not look at `ok`.  MASKED = false is the sampler as it was.
+template <int PER, bool MASKED = false>
 DEV int ctl_sample_wave(float (&y)[PER], int V, float rnd, float* prow, float inv_temp, int top_k, float top_p,
-                        int forced) {
+                        int forced, unsigned ok = 0u) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   if (forced >= 0) {   // the uniform of this step is ignored
@@ -51,6 +57,8 @@ DEV int ctl_sample_wave(float (&y)[PER], int V, float rnd, float* prow, float in
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     y[e] = y[e] * scale;
+    if constexpr (MASKED)
+      if (!((ok >> e) & 1u)) y[e] = -INFINITY;
     mx = fmaxf(mx, y[e]);
   }
   mx = wave_max_dpp(mx);
@@ -125,7 +133,7 @@ DEV int ctl_sample_wave(float (&y)[PER], int V, float rnd, float* prow, float in
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     psum += p[e];
-    if (hit == V && psum > rnd) hit = lane * PER + e;
+    if (hit == V && psum > rnd && (!MASKED || y[e] != -INFINITY)) hit = lane * PER + e;
   }
   hit = wave_min_dpp(hit);
   last = -wave_min_dpp(-last);   // the highest kept index (V - 1 with nothing filtered)

@@ -453,6 +453,26 @@ void gen_reset(const GenResetArgs& a, hipStream_t s);
 // the hand-offs are those of the plain launch.  A prefix byte >= V ORs 16 into err[0] (err[1] = the
 // byte, err[2] = the name) and is taken as 0.  probs is the renormalised filtered distribution, one-hot
 // for a forced or greedy last char.  Neutral controls (1, 0, 1, plen 0) give the plain launch's bytes.
+// Constraints (docs/DESIGN.md §4e / §4g; con != nullptr, with the five controls): the constrained
+// variants (gen_persist_con.hip) apply sample_ctl_f32's MASK / AUTO rule inside the launch.  `con` is a
+// DEVICE pointer to a GenPersistCon, whose fields are SampleCtlArgs' at this launch's rows, and con_mode
+// says which rule it holds (gen_persist_con_mode checks a host copy and returns it).  Per-position
+// (kGenConMask): name n's line at char t is allow_idx[n ML + t], read on every step of every name; a
+// value outside [0, allow_rows) ORs 16 into err[0] (err[1] = the value, err[2] = the name) and is taken
+// as line 0.  Automaton (kGenConAuto): the name starts in allow_start[n] (the same rule for a state out
+// of range, the walk continuing from state 0), every pick -- a forced one included -- moves it to
+// allow_next[state][char], and the nullable allow_state[n] receives each new state, so after the launch
+// it holds the end of the walk over the chars the launch ran.  A forced step reads no mask.  The
+// workspace, `sync` and every hand-off are the controlled launch's.
+struct GenPersistCon {
+  const unsigned* allow_tab = nullptr;           // [allow_rows][V / 32]
+  const int* allow_idx = nullptr;                // [N][ML]   (per-position)
+  const unsigned short* allow_next = nullptr;    // [allow_rows][V]   (automaton)
+  const int* allow_start = nullptr;              // [N]   (automaton)
+  int* allow_state = nullptr;                    // nullable [N]   (automaton): written only
+  int allow_rows = 0;
+};
+constexpr int kGenConNone = 0, kGenConMask = 1, kGenConAuto = 2;
 struct GenPersistArgs {
   const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
   const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
@@ -473,7 +493,20 @@ struct GenPersistArgs {
   const float* top_p = nullptr;            // [N]
   const int* plen = nullptr;               // [N]  forced chars of the name, <= ML
   const unsigned char* prefix = nullptr;   // [N][ML]
+  const GenPersistCon* con = nullptr;      // nullable, DEVICE memory: the launch's constraint (gen_persist_con_store)
+  int con_mode = kGenConNone;              // what *con holds
 };
+// the rule a field set asks for, by SampleCtlArgs' rules (throws on an inconsistent one: allow_tab with
+// exactly one of allow_idx / allow_next; allow_next and allow_start together, never with allow_idx;
+// allow_state only with an automaton; allow_rows >= 1, at most 65535 states)
+int gen_persist_con_mode(const GenPersistCon& h);
+// *dev = h in stream order (a one-thread kernel: no host synchronise, no pinned staging).  The caller
+// keeps *dev unchanged until the launch that reads it has finished
+void gen_persist_con_store(GenPersistCon* dev, const GenPersistCon& h, hipStream_t s);
+// ... and a constrained variant of that mode exists for the shape (each has scratch 0 and two waves per
+// SIMD: gen_persist_con.hip); false: the per-char constrained graph is the path
+bool gen_persist_con_supported(int H, int L, int V, int N, int ML, int mode);
+void gen_persist_con_launch(const GenPersistArgs& a, hipStream_t s);   // (gen_persist_f32 dispatches here)
 bool gen_persist_supported(int H, int L, int V, int N, int ML);
 // ... and a controlled variant exists for the shape (each has scratch 0 and two waves per SIMD:
 // gen_persist_ctl.hip); false: the per-char controlled graph is the path

@@ -43,11 +43,13 @@ class HipGenerator:
     as often as fp32, but that sample cannot separate a 2^-16 product error from fp32 on near-tie
     samples (parity unpinned);
     "bf16": bf16 MFMA fast mode (fused step kernels, bf16 weight copies).
-    Small batches run the exact fp32 persistent kernel in both fp32 modes."""
+    Small batches run the exact fp32 persistent kernel in both fp32 modes.
+    ``persist_constraints`` = N (opt-in, default 0; docs/DESIGN.md §4e): constrained batches of up to N
+    names (at most 64) run as one constrained persistent launch instead of the per-char graph."""
 
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
-                 precision: str = "fp32"):
+                 precision: str = "fp32", persist_constraints: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -71,6 +73,15 @@ class HipGenerator:
                     sos=cfg.sos, eos=cfg.eos, max_batch=max_batch, fp32=_MODE[precision])
         self.g = self.C.Generator(dims, self.flat.data_ptr(), offsets)
         self.g.refresh_weights(self._s())
+        self.set_persist_constraints(persist_constraints)
+
+    def set_persist_constraints(self, n: int) -> None:
+        """Constrained batches of up to ``n`` names take the constrained persistent launch where the
+        shape has one (``g.uses_persist_con``); 0 turns it off (the default)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"persist_constraints must be >= 0, got {n}")
+        self.g.set_persist_con_max(n)
 
     def _s(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -103,8 +114,9 @@ class HipGenerator:
         the controlled path (fp32 / bf16x3 only): per batch one controlled persistent launch where
         ``g.uses_persist_ctl(batch)`` says so (small batches), else the controlled per-char graph.
         ``constraints`` (a cpu_ref.Constraints for the ``n`` names, or a dict of cpu_ref.make_constraints
-        keywords; docs/DESIGN.md §4e): every name samples inside its per-position allowed sets, always on
-        the controlled per-char graph.  With ``regex`` / ``exclude`` among the keywords, or a
+        keywords; docs/DESIGN.md §4e): every name samples inside its per-position allowed sets, on the
+        controlled per-char graph, or -- batches of up to ``persist_constraints`` names -- in one
+        constrained persistent launch.  With ``regex`` / ``exclude`` among the keywords, or a
         cpu_ref.Automaton (docs/DESIGN.md §4g), the sets follow what the name has emitted so far: the same
         graph with a per-row state that the sampler advances.  Bad values raise ValueError before anything
         is launched."""
@@ -391,12 +403,14 @@ def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: i
 
 
 def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
-            prefix=None, constraints=None) -> None:
+            prefix=None, constraints=None, persist_constraints=None) -> None:
     """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
     scalars or one value per name of the job; every rank takes its names' slice.  ``constraints``: a
     cpu_ref.Constraints / cpu_ref.Automaton for the N names or a dict of make_constraints keywords
-    (docs/DESIGN.md §4e, §4g: ``regex`` / ``exclude``), sliced by global name index like the prefixes."""
+    (docs/DESIGN.md §4e, §4g: ``regex`` / ``exclude``), sliced by global name index like the prefixes.
+    ``persist_constraints``: HipGenerator.set_persist_constraints for this and later calls (None: as it
+    is); the CPU path ignores it."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len
@@ -407,6 +421,8 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
     if constraints is not None:
         ctl["constraints"] = _slice_constraints(cfg, constraints, N, start, count)
     if _S.gen is not None:
+        if persist_constraints is not None:
+            _S.gen.set_persist_constraints(persist_constraints)
         _S.gen.g.set_global_names(N)   # bf16 mode: the same arithmetic path at every world size
         mine = _S.gen.generate(random_floats, start, count, **ctl)
         if ctx.world > 1:
