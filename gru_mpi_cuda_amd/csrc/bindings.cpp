@@ -560,6 +560,7 @@ PYBIND11_MODULE(_C, m) {
     const GemmVariants& v = gemm_variants();
     py::dict d;
     d["mfma"] = v.mfma; d["phased"] = v.phased; d["sched"] = v.sched; d["groupm"] = v.groupm; d["onehot"] = v.onehot;
+    d["small_ring"] = v.small_ring;
     return d;
   });
   m.def("set_gemm_variants", [](py::dict d) {
@@ -572,6 +573,10 @@ PYBIND11_MODULE(_C, m) {
       else if (k == "sched") v.sched = x;
       else if (k == "groupm") v.groupm = x;
       else if (k == "onehot") v.onehot = x;
+      else if (k == "small_ring") {
+        if (x != 0 && x != 3 && x != 4) throw std::runtime_error("set_gemm_variants: small_ring is 0, 3 or 4");
+        v.small_ring = x;
+      }
       else throw std::runtime_error("set_gemm_variants: unknown field " + k);
     }
   });

@@ -10,6 +10,9 @@
 //   * LDS: NKB x (64 + 64) rows x 128 B = NKB x 16 KiB (NKB <= 8: two workgroups per CU up to 4);
 //   * split-K slabs, fused bias (unsplit) and fused row sums of A as in gemm_lds;
 //   * grouped launch for several independent products (dW_ih0 and dEmb share one).
+// Since round 9 the default body streams the K-slice through an LDS-DMA ring instead (gemm_small_ring_body
+// below, GemmVariants::small_ring): the same tile, image and arithmetic order, so the same results; the
+// burst body above stays for fp32-A jobs, behind the switch and as the reference of the bitwise tests.
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -143,6 +146,176 @@ DEV void gemm_small_body(const GemmArgs& a, int id, int ntn, int ntm, u16 (*lds)
   }
 }
 
+// ------------------------------------------------------------------ the ring body (GemmVariants::small_ring)
+// The same tile, the same per-wave staging assignment and the same swizzled 16 KiB image per 64-deep
+// k-block (A rows, then B rows), but the K-slice is ONE stream: the k-blocks go through a ring of S LDS
+// slots, block kb + S - 1 is issued while block kb is multiplied, and a wave waits only for its own 4
+// LDS-DMA instructions of block kb (counted vmcnt: loads retire in order) before the barrier that
+// publishes the block.  Every accumulator sees the MFMAs of gemm_small_body in the same order (kb
+// ascending, ks 0..1) and rs[] the same additions, so slabs and row sums are bitwise the burst body's.
+// As in onehot.hip the slots are separate LDS objects, the k loop is unrolled by S and the ring is read
+// with inline-asm ds_reads under a counted lgkmcnt: hipcc's LDS-DMA alias tracking would otherwise put
+// a vmcnt(0) in front of the reads (up to 4 (S - 1) DMA instructions are in flight).  bf16 A only.
+typedef __attribute__((address_space(3))) const void* gs_lds_cptr;
+typedef unsigned gs_u32x4 __attribute__((ext_vector_type(4)));
+DEV gs_u32x4 gs_rd128(const u16* p) {
+  gs_u32x4 v;
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((gs_lds_cptr)p) : "memory");
+  return v;
+}
+template <int N> DEV void gs_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// wait until the oldest of `ahead + 1` in-flight k-blocks has landed (4 LDS-DMA instructions per wave
+// per k-block)
+template <int A> DEV void gs_wait_ahead(int ahead) {
+  if (ahead >= A) { gs_vm_wait<4 * A>(); return; }
+  if constexpr (A > 0) gs_wait_ahead<A - 1>(ahead);
+}
+
+// slot: u16 [2][64 * 64] (A image, B image); r3 is unused for S = 3.  nk: 64-deep blocks per K-slice
+template <int S, bool BIAS, bool ROWSUM>
+DEV void gemm_small_ring_body(const GemmArgs& a, int id, int ntn, int ntm, int nk, u16* r0, u16* r1, u16* r2, u16* r3) {
+  static_assert(S == 3 || S == 4, "ring of 3 or 4 slots");
+  const int tn = id % ntn, tm = (id / ntn) % ntm, sp = id / (ntn * ntm);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int wm = w >> 1, wn = w & 1;
+  const int lr = lane & 15, lq = lane >> 4;
+  const int row0 = tm * 64, col0 = tn * 64;
+  const int srow = lane >> 3, sslot = lane & 7;
+
+  // wave w stages rows 16w .. 16w+15 of A and B of every block (two instructions each)
+  const u16 *srcA[2], *srcB[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = w * 16 + q * 8 + srow;
+    const int c = sslot ^ ((r >> 1) & 7);
+    const size_t ko = (size_t)sp * nk * 64 + c * 8;
+    srcA[q] = a.A + (size_t)(row0 + r) * a.lda + ko;
+    srcB[q] = a.B + (size_t)(col0 + r) * a.ldb + ko;
+  }
+  auto stage = [&](u16* slot, int kb) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      __builtin_amdgcn_global_load_lds(srcA[q] + kb * 64, (lds_void_s*)(&slot[(w * 16 + q * 8) * 64]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(srcB[q] + kb * 64, (lds_void_s*)(&slot[64 * 64 + (w * 16 + q * 8) * 64]), 16, 0, 0);
+    }
+  };
+#pragma unroll
+  for (int s = 0; s < S - 1; ++s)
+    if (s < nk) stage(s == 0 ? r0 : s == 1 ? r1 : r2, s);
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_rs = ROWSUM && a.rowsumA && tn == 0 && wn == 0;
+  float rs[2] = {0.f, 0.f};
+
+  // fragment offsets inside a slot (the same for every block)
+  int oa[2][2], ob[2][2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int c = ks * 4 + lq;
+      const int ra = wm * 32 + t * 16 + lr, rb = wn * 32 + t * 16 + lr;
+      oa[ks][t] = ra * 64 + ((c ^ ((ra >> 1) & 7)) * 8);
+      ob[ks][t] = 64 * 64 + rb * 64 + ((c ^ ((rb >> 1) & 7)) * 8);
+    }
+
+  // block kb from slot R; block kb + S - 1 goes into slot N (the one read at kb - 1)
+  auto block = [&](const u16* R, u16* N, int kb) {
+    gs_wait_ahead<S - 2>(min(S - 2, nk - 1 - kb));
+    // publishes block kb (every wave's DMA share) and proves every wave is done with slot N
+    lds_barrier();
+    if (kb + S - 1 < nk) stage(N, kb + S - 1);
+    gs_u32x4 ua[2][2], ub[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        ua[ks][t] = gs_rd128(R + oa[ks][t]);
+        ub[ks][t] = gs_rd128(R + ob[ks][t]);
+      }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    bf16x8 af[2][2], bfr[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        asm volatile("" : "+v"(ua[ks][t]), "+v"(ub[ks][t]));   // (ordered after the wait)
+        af[ks][t] = __builtin_bit_cast(bf16x8, ua[ks][t]);
+        bfr[ks][t] = __builtin_bit_cast(bf16x8, ub[ks][t]);
+      }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(af[ks][i], bfr[ks][j], acc[i][j]);
+      if (do_rs) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) rs[t] += (float)af[ks][t][e];
+      }
+    }
+  };
+  if constexpr (S == 4) {
+    for (int kb = 0; kb < nk; kb += 4) {
+      block(r0, r3, kb);
+      if (kb + 1 < nk) block(r1, r0, kb + 1);
+      if (kb + 2 < nk) block(r2, r1, kb + 2);
+      if (kb + 3 < nk) block(r3, r2, kb + 3);
+    }
+  } else {
+    for (int kb = 0; kb < nk; kb += 3) {
+      block(r0, r2, kb);
+      if (kb + 1 < nk) block(r1, r0, kb + 1);
+      if (kb + 2 < nk) block(r2, r1, kb + 2);
+    }
+  }
+
+  float* C = a.C + (size_t)sp * a.M * a.ldc;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int col = col0 + wn * 32 + j * 16 + lr;
+    const float bb = BIAS ? a.bias[col] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = row0 + wm * 32 + i * 16 + lq * 4 + e;
+        float* dst = C + (size_t)row * a.ldc + col;
+        const float v = acc[i][j][e] + bb;
+        if (a.accumulate) *dst += v; else *dst = v;
+      }
+  }
+  if (do_rs) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      float v = rs[t];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if (lane < 16) a.rowsumA[(size_t)sp * a.M + row0 + wm * 32 + t * 16 + lane] = v;
+    }
+  }
+}
+
+// the ring's slots as separate LDS objects (see above): S x 16 KiB, 64 / S workgroups' worth of a CU's
+// 160 KiB -- two workgroups per CU at S = 4, three at S = 3
+#define GS_RING_SLOTS(S)                                                  \
+  __shared__ __attribute__((aligned(16))) u16 r0[2 * 64 * 64];            \
+  __shared__ __attribute__((aligned(16))) u16 r1[2 * 64 * 64];            \
+  __shared__ __attribute__((aligned(16))) u16 r2[2 * 64 * 64];            \
+  __shared__ __attribute__((aligned(16))) u16 r3[S == 4 ? 2 * 64 * 64 : 8];
+
+template <int S, bool BIAS, bool ROWSUM>
+__global__ void __launch_bounds__(256, S == 3 ? 3 : 2) gemm_small_ring_kernel(GemmArgs a, int ntn, int ntm, int nk) {
+  GS_RING_SLOTS(S)
+  gemm_small_ring_body<S, BIAS, ROWSUM>(a, xcd_remap_s(blockIdx.x, gridDim.x), ntn, ntm, nk, r0, r1, r2, r3);
+}
+
 template <int NKB, bool BIAS, bool ROWSUM>
 __global__ void __launch_bounds__(256, NKB <= 4 ? 2 : 1) gemm_small_kernel(GemmArgs a, int ntn, int ntm, int nch) {
   __shared__ __attribute__((aligned(16))) u16 lds[NKB][2][64 * 64];
@@ -185,6 +358,58 @@ __global__ void __launch_bounds__(256, NKB <= 4 ? 2 : 1) gemm_small_prep_kernel(
   gemm_small_body<NKB, BIAS, false>(a, xcd_remap_s(blockIdx.x, ng), ntn, ntm, lds, nch);
 }
 
+// the ring forms: a job's K-slice is nk[k] = nch[k] x NKB blocks of one stream (SmallGroup::nch then holds
+// the block count per K-slice, not chunks)
+template <int S, bool BIAS, bool ROWSUM>
+__global__ void __launch_bounds__(256, S == 3 ? 3 : 2) gemm_small_ring_group_kernel(SmallGroup g) {
+  GS_RING_SLOTS(S)
+  int k = 0, id;
+  if (g.per_xcd) {
+    const int x = blockIdx.x % 8, loc = blockIdx.x / 8;
+    while (k + 1 < g.n && loc >= g.xs[k + 1]) ++k;
+    id = x * (g.xs[k + 1] - g.xs[k]) + (loc - g.xs[k]);
+  } else {
+    const int gid = xcd_remap_s(blockIdx.x, gridDim.x);
+    while (k + 1 < g.n && gid >= g.start[k + 1]) ++k;
+    id = gid - g.start[k];
+  }
+  gemm_small_ring_body<S, BIAS, ROWSUM>(g.job[k], id, g.ntn[k], g.ntm[k], g.nch[k], r0, r1, r2, r3);
+}
+
+template <int S, bool BIAS>
+__global__ void __launch_bounds__(256, S == 3 ? 3 : 2) gemm_small_ring_prep_kernel(GemmArgs a, int ntn, int ntm, PrepJob pj,
+                                                                                    int nprep, int nk) {
+  GS_RING_SLOTS(S)
+  const int ng = ntn * ntm * a.splits;
+  if ((int)blockIdx.x >= ng) {
+    prep_batch_body(pj, (int)blockIdx.x - ng, nprep);
+    return;
+  }
+  gemm_small_ring_body<S, BIAS, false>(a, xcd_remap_s(blockIdx.x, ng), ntn, ntm, nk, r0, r1, r2, r3);
+}
+
+// GemmVariants::small_ring for a product: the ring's slot count, or 0 = the burst body (the switch at 0,
+// and every fp32-A job: its A is staged with per-thread converts, which the ring does not do)
+static int ring_slots(const GemmArgs* jobs, int n) {
+  const int v = gemm_variants().small_ring;
+  if (v == 0) return 0;
+  if (v != 3 && v != 4) throw std::runtime_error("gemm_small: small_ring is 0, 3 or 4");
+  for (int k = 0; k < n; ++k)
+    if (jobs[k].A32) return 0;
+  return v;
+}
+
+template <class Launch>
+static void dispatch_ring(int S, bool bias, bool rs, const Launch& L) {
+  if (S == 3) {
+    if (rs) { if (bias) L.template ring<3, true, true>(); else L.template ring<3, false, true>(); }
+    else { if (bias) L.template ring<3, true, false>(); else L.template ring<3, false, false>(); }
+  } else {
+    if (rs) { if (bias) L.template ring<4, true, true>(); else L.template ring<4, false, true>(); }
+    else { if (bias) L.template ring<4, true, false>(); else L.template ring<4, false, false>(); }
+  }
+}
+
 // 64-deep blocks per chunk (0 = unsupported); *nch = chunks per K-slice (slices of n x 512 stream)
 static int small_blocks(const GemmArgs& a, int* nch) {
   *nch = 1;
@@ -222,11 +447,17 @@ struct SmallLaunch {
   template <int N, bool B, bool R> void go() const {
     hipLaunchKernelGGL((gemm_small_kernel<N, B, R>), dim3(ntn * ntm * a.splits), dim3(256), 0, s, a, ntn, ntm, nch);
   }
+  template <int S, bool B, bool R> void ring() const {   // (nch: blocks per K-slice)
+    hipLaunchKernelGGL((gemm_small_ring_kernel<S, B, R>), dim3(ntn * ntm * a.splits), dim3(256), 0, s, a, ntn, ntm, nch);
+  }
 };
 struct SmallGroupLaunch {
   const SmallGroup& g; int tot; hipStream_t s;
   template <int N, bool B, bool R> void go() const {
     hipLaunchKernelGGL((gemm_small_group_kernel<N, B, R>), dim3(tot), dim3(256), 0, s, g);
+  }
+  template <int S, bool B, bool R> void ring() const {
+    hipLaunchKernelGGL((gemm_small_ring_group_kernel<S, B, R>), dim3(tot), dim3(256), 0, s, g);
   }
 };
 
@@ -234,6 +465,10 @@ void gemm_small(const GemmArgs& a, hipStream_t s) {
   int nch = 1;
   const int nkb = small_blocks(a, &nch);
   if (!nkb) throw std::runtime_error("gemm_small: unsupported shape");
+  if (const int S = ring_slots(&a, 1)) {
+    dispatch_ring(S, a.bias && a.splits == 1, a.rowsumA != nullptr, SmallLaunch{a, a.N / 64, a.M / 64, nkb * nch, s});
+    return;
+  }
   dispatch_nkb(nkb, a.bias && a.splits == 1, a.rowsumA != nullptr, SmallLaunch{a, a.N / 64, a.M / 64, nch, s});
 }
 
@@ -245,10 +480,19 @@ void gemm_small_with_prep(const GemmArgs& a, const PrepJob& p, hipStream_t s) {
   // past one round of workgroups at one per CU (the 128 KiB 8-block image): 4-block chunks, two per CU
   // (config 5's 256 x 6144 table, 384 tiles: 41.5 -> 29.9 us, step 7.938-7.963 -> 7.920-7.928 ms,
   // profiles/r6_prep4_c5_ab.jsonl); the same k order, so the same table
-  int nkb2 = nkb;
-  if (nkb == 8 && ntn * ntm * a.splits > 256) { nkb2 = 4; nch *= 2; }
   const dim3 grid(ntn * ntm * a.splits + nprep), block(256);
   const bool bias = a.bias && a.splits == 1;
+  if (const int S = ring_slots(&a, 1)) {   // one stream, whatever the tile count
+    const int nk = nkb * nch;
+#define GP_RING(S_)                                                                                                        \
+    if (bias) hipLaunchKernelGGL((gemm_small_ring_prep_kernel<S_, true>), grid, block, 0, s, a, ntn, ntm, p, nprep, nk);  \
+    else hipLaunchKernelGGL((gemm_small_ring_prep_kernel<S_, false>), grid, block, 0, s, a, ntn, ntm, p, nprep, nk);
+    if (S == 3) { GP_RING(3) } else { GP_RING(4) }
+#undef GP_RING
+    return;
+  }
+  int nkb2 = nkb;
+  if (nkb == 8 && ntn * ntm * a.splits > 256) { nkb2 = 4; nch *= 2; }
 #define GP_CASE(N)                                                                                        \
   case N:                                                                                                 \
     if (bias) hipLaunchKernelGGL((gemm_small_prep_kernel<N, true>), grid, block, 0, s, a, ntn, ntm, p, nprep, nch); \
@@ -297,6 +541,11 @@ void gemm_small_group(const GemmArgs* jobs, int n, hipStream_t s) {
     g.xs[k + 1] = g.xs[k] + nt / 8;
   }
   g.start[n] = tot;
+  if (const int S = ring_slots(jobs, n)) {
+    for (int k = 0; k < n; ++k) g.nch[k] *= nkb;   // blocks per K-slice
+    dispatch_ring(S, bias, rs, SmallGroupLaunch{g, tot, s});
+    return;
+  }
   dispatch_nkb(nkb, bias, rs, SmallGroupLaunch{g, tot, s});
 }
 

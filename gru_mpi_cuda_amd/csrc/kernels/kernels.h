@@ -118,6 +118,9 @@ struct GemmVariants {
   int groupm = 4;   // grouped raster run length (tile-rows)
   int onehot = 1;   // one-hot dP products with V = 256 on the streaming kernel (onehot.hip), 1: 128-column x
                     // 64-token k-tiles, 2: 64 x 128, 3: 32 x 256; 0: the one-hot gemm_lds kernel
+  int small_ring = 4;   // gemm_small (single, grouped, with the batch preparation): a K-slice as one stream of
+                        // 64-deep blocks through an LDS-DMA ring of this many 16 KiB slots (3 or 4); 0: the
+                        // burst body (whole chunks staged, then multiplied), which fp32-A jobs always take
 };
 GemmVariants& gemm_variants();
 // LDS-staged large-H step kernels: H % 64 == 0, Bp % 128 == 0, no fused input projection
