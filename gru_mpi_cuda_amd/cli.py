@@ -216,6 +216,47 @@ def _constraints_from(args):
     return kw or None
 
 
+def _bias_item(text: str):
+    """--logit-bias CHARS=VALUE -> (bytes, float); CHARS literal latin-1 (the last '=' splits)."""
+    chars, sep, val = text.rpartition("=")
+    try:
+        if not sep or not chars:
+            raise ValueError
+        return chars.encode("latin-1"), float(val)
+    except ValueError:   # (UnicodeEncodeError is one)
+        raise argparse.ArgumentTypeError(f"CHARS=VALUE expected (CHARS latin-1, VALUE a number), got {text!r}")
+
+
+def _soft_args(p) -> None:
+    p.add_argument("--logit-bias", dest="logit_bias", type=_bias_item, action="append", default=None,
+                   metavar="CHARS=VALUE", help="add VALUE to the logit of every char in CHARS (repeatable; soft "
+                                               "preferences: docs/DESIGN.md §4h)")
+    p.add_argument("--eos-bias", dest="eos_bias", type=float, default=None, metavar="X",
+                   help="add X to the end-of-name char's logit (negative: longer names)")
+    p.add_argument("--presence-penalty", dest="presence_penalty", type=float, default=None, metavar="X",
+                   help="deduct X from the logit of every char the name already holds")
+    p.add_argument("--frequency-penalty", dest="frequency_penalty", type=float, default=None, metavar="X",
+                   help="deduct X per earlier occurrence of a char in the name")
+
+
+def _soft_from(args, eos: int) -> dict:
+    """The soft-control keywords of --logit-bias / --eos-bias / --presence-penalty / --frequency-penalty
+    (empty: none given).  Values for the same char add up."""
+    kw = {}
+    if args.logit_bias is not None or args.eos_bias is not None:
+        bias = {}
+        for chars, val in args.logit_bias or []:
+            for c in chars:
+                bias[c] = bias.get(c, 0.0) + val
+        if args.eos_bias is not None:
+            bias[int(eos)] = bias.get(int(eos), 0.0) + args.eos_bias
+        kw["logit_bias"] = bias
+    for key in ("presence_penalty", "frequency_penalty"):
+        if getattr(args, key) is not None:
+            kw[key] = getattr(args, key)
+    return kw
+
+
 def cmd_generate(args) -> int:
     from .engine import generator as G
     from .utils.data import random_floats
@@ -254,6 +295,7 @@ def cmd_generate(args) -> int:
     t0 = time.perf_counter()
     G.namegen_initialize(N, args.seed, args.ckpt, cfg, fmt, ctx=ctx, precision=args.precision)
     out = np.zeros(N * (ml + 1), dtype=np.uint8)
+    ctl.update(_soft_from(args, G._S.cfg.eos))   # (the EOS id is the checkpoint's)
     t1 = time.perf_counter()
     if args.exclude_emitted:
         _generate_distinct(G, args, N, ml, ctl, out)
@@ -364,6 +406,7 @@ def cmd_score(args) -> int:
         ctl["prefix"] = [pres[i % len(pres)] for i in range(rows.shape[0])]   # cycled over the rows, as generate does
     if _constraints_from(args) is not None:
         ctl["constraints"] = _constraints_from(args)
+    ctl.update(_soft_from(args, cfg.eos))
     t0 = time.perf_counter()
     if args.cpu or not torch.cuda.is_available():
         out = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows, **ctl)
@@ -497,6 +540,7 @@ def main(argv=None) -> int:
     sc.add_argument("--prefix", default=None, help="`generate`'s --prefix: every name is forced to start with these chars")
     sc.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line, cycled over the names")
     _constraint_args(sc)
+    _soft_args(sc)
     sc.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(sc)
     g = sub.add_parser("generate", help="namegen_initialize / namegen / namegen_finalize")
@@ -520,6 +564,7 @@ def main(argv=None) -> int:
     g.add_argument("--prefix-file", dest="prefix_file", default=None,
                    help="one prefix per line, cycled over the names")
     _constraint_args(g)
+    _soft_args(g)
     g.add_argument("--persist-constraints", dest="persist_constraints", type=int, nargs="?", const=64, default=None,
                    metavar="N", help="constrained batches of up to N names (bare flag: 64) run as one constrained "
                                      "persistent launch instead of the per-char graph (opt-in; docs/DESIGN.md §4e)")

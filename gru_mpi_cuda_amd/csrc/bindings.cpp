@@ -210,8 +210,12 @@ PYBIND11_MODULE(_C, m) {
       })
       .def("generate_ctl", [](Generator& g, uintptr_t rf, int N, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p,
                               uintptr_t plen, uintptr_t prefix, uintptr_t out, uintptr_t s, uintptr_t allow_tab,
-                              uintptr_t allow_idx, int allow_rows, uintptr_t allow_next, uintptr_t allow_start) {
+                              uintptr_t allow_idx, int allow_rows, uintptr_t allow_next, uintptr_t allow_start,
+                              uintptr_t soft_tab, uintptr_t soft_idx, int soft_rows, uintptr_t soft_pres,
+                              uintptr_t soft_freq) {
         Generator::Ctl c;
+        c.soft_tab = Pp<const float>(soft_tab); c.soft_idx = Pp<const int>(soft_idx); c.soft_rows = soft_rows;
+        c.soft_pres = Pp<const float>(soft_pres); c.soft_freq = Pp<const float>(soft_freq);
         c.allow_next = Pp<const unsigned short>(allow_next); c.allow_start = Pp<const int>(allow_start);
         c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
         c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
@@ -220,26 +224,33 @@ PYBIND11_MODULE(_C, m) {
       }, py::arg("rf"), py::arg("N"), py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"), py::arg("plen"),
          py::arg("prefix"), py::arg("out"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
          py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0,
-         py::arg("allow_start") = (uintptr_t)0)
+         py::arg("allow_start") = (uintptr_t)0, py::arg("soft_tab") = (uintptr_t)0, py::arg("soft_idx") = (uintptr_t)0,
+         py::arg("soft_rows") = 0, py::arg("soft_pres") = (uintptr_t)0, py::arg("soft_freq") = (uintptr_t)0)
+      .def("soft_graphs", &Generator::soft_graphs)
       .def("automaton_graphs", &Generator::automaton_graphs)
       .def("ctl_workspace_bytes", &Generator::ctl_workspace_bytes)
       .def("ctl_graphs", &Generator::ctl_graphs)
       .def("score", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
                        uintptr_t n_tok, uintptr_t s, uintptr_t inv_temp, uintptr_t top_k, uintptr_t top_p, uintptr_t plen,
-                       uintptr_t prefix, uintptr_t n_kept, uintptr_t allow_tab, uintptr_t allow_idx, int allow_rows) {
+                       uintptr_t prefix, uintptr_t n_kept, uintptr_t allow_tab, uintptr_t allow_idx, int allow_rows,
+                       uintptr_t soft_tab, uintptr_t soft_idx, int soft_rows, uintptr_t soft_pres, uintptr_t soft_freq) {
         // inv_temp set: the controlled score (every control array and n_kept are then required)
         Generator::Ctl c;
+        c.soft_tab = Pp<const float>(soft_tab); c.soft_idx = Pp<const int>(soft_idx); c.soft_rows = soft_rows;
+        c.soft_pres = Pp<const float>(soft_pres); c.soft_freq = Pp<const float>(soft_freq);
         c.inv_temp = Pp<const float>(inv_temp); c.top_k = Pp<const int>(top_k); c.top_p = Pp<const float>(top_p);
         c.plen = Pp<const int>(plen); c.prefix = Pp<const unsigned char>(prefix);
         c.allow_tab = Pp<const unsigned>(allow_tab); c.allow_idx = Pp<const int>(allow_idx); c.allow_rows = allow_rows;
-        const bool ctl = inv_temp || top_k || top_p || plen || prefix || n_kept || allow_tab || allow_idx;
+        const bool ctl = inv_temp || top_k || top_p || plen || prefix || n_kept || allow_tab || allow_idx || soft_tab ||
+                         soft_idx || soft_pres || soft_freq;
         g.score(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
                 Pp<int>(n_tok), S(s), ctl ? &c : nullptr, Pp<int>(n_kept));
       }, py::arg("rows"), py::arg("N"), py::arg("tok_logp"), py::arg("rank"), py::arg("name_logp"), py::arg("n_tok"),
          py::arg("stream"), py::arg("inv_temp") = (uintptr_t)0, py::arg("top_k") = (uintptr_t)0,
          py::arg("top_p") = (uintptr_t)0, py::arg("plen") = (uintptr_t)0, py::arg("prefix") = (uintptr_t)0,
          py::arg("n_kept") = (uintptr_t)0, py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
-         py::arg("allow_rows") = 0)
+         py::arg("allow_rows") = 0, py::arg("soft_tab") = (uintptr_t)0, py::arg("soft_idx") = (uintptr_t)0,
+         py::arg("soft_rows") = 0, py::arg("soft_pres") = (uintptr_t)0, py::arg("soft_freq") = (uintptr_t)0)
       .def("score_workspace_bytes", &Generator::score_workspace_bytes)
       .def("score_graphs", &Generator::score_graphs)
       .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
@@ -784,6 +795,9 @@ PYBIND11_MODULE(_C, m) {
     c.allow_tab = GP(const unsigned, d, "allow_tab"); c.allow_idx = GP(const int, d, "allow_idx");
     c.allow_rows = get<int>(d, "allow_rows", 0);
     c.allow_state = GP(int, d, "allow_state"); c.allow_next = GP(const unsigned short, d, "allow_next");
+    c.soft_tab = GP(const float, d, "soft_tab"); c.soft_idx = GP(const int, d, "soft_idx");
+    c.soft_rows = get<int>(d, "soft_rows", 0);
+    c.soft_pres = GP(const float, d, "soft_pres"); c.soft_freq = GP(const float, d, "soft_freq");
     sample_ctl_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });
@@ -918,6 +932,9 @@ PYBIND11_MODULE(_C, m) {
     c.prefix = GP(const unsigned char, d, "prefix"); c.row0 = get<int>(d, "row0", 0); c.err = GP(unsigned, d, "err");
     c.allow_tab = GP(const unsigned, d, "allow_tab"); c.allow_idx = GP(const int, d, "allow_idx");
     c.allow_rows = get<int>(d, "allow_rows", 0); c.n_kept = GP(int, d, "n_kept");
+    c.soft_tab = GP(const float, d, "soft_tab"); c.soft_idx = GP(const int, d, "soft_idx");
+    c.soft_rows = get<int>(d, "soft_rows", 0);
+    c.soft_pres = GP(const float, d, "soft_pres"); c.soft_freq = GP(const float, d, "soft_freq");
     score_ctl_logprob_f32(c, S(s));
     HIP_LAUNCH_CHECK();
   });

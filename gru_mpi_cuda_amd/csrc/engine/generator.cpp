@@ -95,7 +95,12 @@ Generator::~Generator() {
   cgraphs_.clear();
   bgraphs_.clear();
   agraphs_.clear();
-  abgraphs_.clear();
+  csgraphs_.clear();
+  asgraphs_.clear();
+  scsgraphs_.clear();
+  for (SoftBufs* b : {&gsoft_, &ssoft_})
+    for (void* p : {(void*)b->tab, (void*)b->idx, (void*)b->pres, (void*)b->freq})
+      if (p) (void)hipFree(p);
   for (void* p : {(void*)atab_, (void*)anxt_, (void*)astart_, (void*)astate_, (void*)abstart_, (void*)abstate_[0],
                   (void*)abstate_[1]})
     if (p) (void)hipFree(p);
@@ -246,7 +251,7 @@ int Generator::product_f32(const float* A32, const u16* A3, const float* W32, co
   return g.splits;
 }
 
-void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows, bool automaton) {
+void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows, bool automaton, int soft_rows) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n, 64);
   const bool x3 = split3();
@@ -287,6 +292,10 @@ void Generator::record_steps_f32(int n, hipStream_t s, bool ctl, int allow_rows,
       c.row0 = 0; c.err = err_;
       if (automaton) { c.allow_tab = atab_; c.allow_next = anxt_; c.allow_state = astate_; c.allow_rows = allow_rows; }
       else if (allow_rows > 0) { c.allow_tab = ctab_; c.allow_idx = cidx_; c.allow_rows = allow_rows; }
+      if (soft_rows > 0) {
+        c.soft_tab = gsoft_.tab; c.soft_idx = gsoft_.idx; c.soft_rows = soft_rows;
+        c.soft_pres = gsoft_.pres; c.soft_freq = gsoft_.freq;
+      }
       sample_ctl_f32(c, s);
     } else {
       sample_f32(q, s);
@@ -401,6 +410,23 @@ void Generator::ctl_alloc() {
   cready_ = true;
 }
 
+// The soft-control buffers of generate_ctl() and score(): a generator that never gets a soft call never
+// allocates them, and they are in no arena, so no workspace size changes.
+void Generator::soft_alloc() {
+  if (gsoft_.tab) return;
+  const size_t B = Bmax_, V = d_.V;
+  for (SoftBufs* b : {&gsoft_, &ssoft_}) {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->tab), (size_t)kSoftRows * V * 4));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->idx), B * 4));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->pres), B * 4));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&b->freq), B * 4));
+    HIP_CHECK(hipMemset(b->tab, 0, (size_t)kSoftRows * V * 4));
+    HIP_CHECK(hipMemset(b->idx, 0, B * 4));
+    HIP_CHECK(hipMemset(b->pres, 0, B * 4));
+    HIP_CHECK(hipMemset(b->freq, 0, B * 4));
+  }
+}
+
 void Generator::automaton_stage(const unsigned* tab, const unsigned short* next, int states, hipStream_t s) {
   const size_t B = Bmax_, V = d_.V;
   if (!astate_) {
@@ -412,6 +438,7 @@ void Generator::automaton_stage(const unsigned* tab, const unsigned short* next,
   if (states > acap_) {   // grow: the recordings hold the old addresses
     HIP_CHECK(hipDeviceSynchronize());
     agraphs_.clear();
+    asgraphs_.clear();
     abgraphs_.clear();
     if (atab_) HIP_CHECK(hipFree(atab_));
     if (anxt_) HIP_CHECK(hipFree(anxt_));
@@ -439,13 +466,20 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
   const bool masked = c.allow_tab != nullptr;
   if (!aut && (masked != (c.allow_idx != nullptr) || (masked && (c.allow_rows < 1 || c.allow_rows > kAllowRows))))
     throw std::runtime_error("Generator::generate_ctl: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
+  const bool soft = c.soft_tab != nullptr;
+  if (soft != (c.soft_idx != nullptr) || soft != (c.soft_pres != nullptr) || soft != (c.soft_freq != nullptr) ||
+      (soft && (c.soft_rows < 1 || c.soft_rows > kSoftRows)))
+    throw std::runtime_error("Generator::generate_ctl: soft controls need soft_tab, soft_idx, soft_pres, soft_freq and "
+                             "1 <= soft_rows <= 256");
   if (N <= 0) return;
   const int ML = d_.max_len;
+  const int sr = soft ? c.soft_rows : 0;
+  if (soft) soft_alloc();   // first soft call: allocates before the error word is cleared and anything is captured
   // a batch that takes the constrained persistent launch reads the caller's tables in place: a call made
   // of such batches alone stages nothing and allocates nothing
   bool graph_batch = false;
   for (int start = 0; start < N; start += Bmax_)
-    if (!(masked && uses_persist_con(std::min(Bmax_, N - start), aut))) graph_batch = true;
+    if (soft || !(masked && uses_persist_con(std::min(Bmax_, N - start), aut))) graph_batch = true;
   bool aut_staged = false;
   if (aut && graph_batch) {   // before the error word is cleared: growing the buffers synchronises
     ctl_alloc();
@@ -455,10 +489,13 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
   if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   bool tab_staged = false;
+  if (soft)   // the bias lines once per call
+    HIP_CHECK(hipMemcpyAsync(gsoft_.tab, c.soft_tab, (size_t)sr * d_.V * 4, hipMemcpyDeviceToDevice, s));
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
-    // (a constrained batch only where the caller opted in: uses_persist_con, docs/DESIGN.md §4e)
-    if (masked ? uses_persist_con(n, aut) : uses_persist_ctl(n)) {   // one launch on the caller's arrays at this batch's rows
+    // (a constrained batch only where the caller opted in: uses_persist_con, docs/DESIGN.md §4e; a soft
+    // batch never: the persistent sampler has no soft terms, §4h)
+    if (!soft && (masked ? uses_persist_con(n, aut) : uses_persist_ctl(n))) {   // one launch on the caller's arrays at this batch's rows
       Ctl b;
       b.inv_temp = c.inv_temp + start; b.top_k = c.top_k + start; b.top_p = c.top_p + start; b.plen = c.plen + start;
       b.prefix = c.prefix + (size_t)start * ML;
@@ -482,9 +519,27 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
     HIP_CHECK(hipMemcpyAsync(cplen_, c.plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(cprefix_, c.prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
     const int ar = masked ? c.allow_rows : 0;
+    if (soft) {   // this batch's lines and penalties
+      HIP_CHECK(hipMemcpyAsync(gsoft_.idx, c.soft_idx + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(gsoft_.pres, c.soft_pres + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(gsoft_.freq, c.soft_freq + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    }
     if (aut) {   // the tables are staged: this batch's start states, then its graph
       HIP_CHECK(hipMemcpyAsync(astart_, c.allow_start + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-      if (use_graph_) {
+      if (use_graph_ && soft) {   // a soft recording, in the map of its own (the same cap)
+        if (asgraphs_.size() >= kAutoGraphs && !asgraphs_.count(std::make_tuple(n, ar, sr))) {
+          HIP_CHECK(hipStreamSynchronize(s));
+          asgraphs_.clear();
+        }
+        auto& g = asgraphs_[std::make_tuple(n, ar, sr)];
+        if (!g) {
+          g.reset(new Graph());
+          g->begin(cap_);
+          record_steps_f32(n, cap_, true, ar, true, sr);
+          g->end(cap_);
+        }
+        g->launch(s);
+      } else if (use_graph_) {
         // every state count has a recording of its own, and a caller that grows an exclusion list call by
         // call never comes back to one: keep the latest few
         if (agraphs_.size() >= kAutoGraphs && !agraphs_.count(std::make_pair(n, ar))) {
@@ -500,7 +555,7 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
         }
         g->launch(s);
       } else {
-        record_steps_f32(n, s, true, ar, true);
+        record_steps_f32(n, s, true, ar, true, sr);
       }
       HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
       continue;
@@ -512,7 +567,16 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
       }
       HIP_CHECK(hipMemcpyAsync(cidx_, c.allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     }
-    if (use_graph_) {
+    if (use_graph_ && soft) {   // a soft recording: the bias table's line count is baked in as well
+      auto& g = csgraphs_[std::make_tuple(n, ar, sr)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_steps_f32(n, cap_, true, ar, false, sr);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else if (use_graph_) {
       // the recording bakes the table's line count in (the sampler checks every entry against it),
       // so it is part of the key; 0 = the unconstrained graph, the only one an unconstrained call sees
       auto& g = cgraphs_[std::make_pair(n, ar)];
@@ -524,7 +588,7 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
       }
       g->launch(s);
     } else {
-      record_steps_f32(n, s, true, ar);
+      record_steps_f32(n, s, true, ar, false, sr);
     }
     HIP_CHECK(hipMemcpyAsync(out + (size_t)start * (ML + 1), out_, (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
   }
@@ -577,7 +641,7 @@ void Generator::score_ctl_alloc() {
 
 // The schedule for a padded batch of Bp rows (the name count is read from sn_ by score_prep, so one
 // recording serves every count that pads to Bp): 2 L ML + L + 2 launches, a single chain.
-void Generator::record_score(int Bp, hipStream_t s, bool ctl, int allow_rows) {
+void Generator::record_score(int Bp, hipStream_t s, bool ctl, int allow_rows, int soft_rows) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int cap = std::max(Bmax_, kF32SlabRows);
   ScorePrepArgs p;
@@ -623,6 +687,10 @@ void Generator::record_score(int Bp, hipStream_t s, bool ctl, int allow_rows) {
     c.s = q; c.inv_temp = scinv_; c.top_k = sctopk_; c.top_p = sctopp_; c.plen = scplen_; c.prefix = scprefix_;
     c.row0 = 0; c.err = err_; c.n_kept = snkept_;
     if (allow_rows > 0) { c.allow_tab = sctab_; c.allow_idx = scidx_; c.allow_rows = allow_rows; }
+    if (soft_rows > 0) {
+      c.soft_tab = ssoft_.tab; c.soft_idx = ssoft_.idx; c.soft_rows = soft_rows;
+      c.soft_pres = ssoft_.pres; c.soft_freq = ssoft_.freq;
+    }
     score_ctl_logprob_f32(c, s);
   } else {
     score_logprob_f32(q, s);
@@ -634,7 +702,12 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
                       hipStream_t s, const Ctl* c, int* n_kept) {
   GK_TRACE("gk.score");
   const bool masked = c && c->allow_tab != nullptr;
+  const bool soft = c && c->soft_tab != nullptr;
   if (c) {
+    if (soft != (c->soft_idx != nullptr) || soft != (c->soft_pres != nullptr) || soft != (c->soft_freq != nullptr) ||
+        (soft && (c->soft_rows < 1 || c->soft_rows > kSoftRows)))
+      throw std::runtime_error("Generator::score: soft controls need soft_tab, soft_idx, soft_pres, soft_freq and "
+                               "1 <= soft_rows <= 256");
     if (!c->inv_temp || !c->top_k || !c->top_p || !c->plen || !c->prefix || !n_kept)
       throw std::runtime_error("Generator::score: a controlled score needs every control array and n_kept");
     if (masked != (c->allow_idx != nullptr) || (masked && (c->allow_rows < 1 || c->allow_rows > kAllowRows)))
@@ -647,11 +720,15 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
   if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::score needs max_len <= 64 and vocab <= 512");
   score_alloc();   // first call: allocates (and synchronises) before anything is captured
   if (c) score_ctl_alloc();   // ... the first controlled one its control buffers
+  if (soft) soft_alloc();     // ... the first soft one the soft-control buffers
+  const int sr = soft ? c->soft_rows : 0;
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   const int ar = masked ? c->allow_rows : 0;
   if (masked)   // the table once per call
     HIP_CHECK(hipMemcpyAsync(sctab_, c->allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+  if (soft)     // the bias lines once per call
+    HIP_CHECK(hipMemcpyAsync(ssoft_.tab, c->soft_tab, (size_t)sr * d_.V * 4, hipMemcpyDeviceToDevice, s));
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
     const int Bp = rup(n, 64);
@@ -665,8 +742,22 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
       HIP_CHECK(hipMemcpyAsync(scprefix_, c->prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
       if (masked)
         HIP_CHECK(hipMemcpyAsync(scidx_, c->allow_idx + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+      if (soft) {
+        HIP_CHECK(hipMemcpyAsync(ssoft_.idx, c->soft_idx + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(ssoft_.pres, c->soft_pres + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(ssoft_.freq, c->soft_freq + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+      }
     }
-    if (use_graph_) {
+    if (use_graph_ && soft) {   // a soft recording, in the map of its own
+      auto& g = scsgraphs_[std::make_tuple(Bp, ar, sr)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_score(Bp, cap_, true, ar, sr);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else if (use_graph_) {
       // an uncontrolled call: the graphs it had.  A controlled recording bakes the table's line count in
       // (every entry is checked against it), so that is part of its key; 0 = unconstrained
       auto& g = c ? scgraphs_[std::make_pair(Bp, ar)] : sgraphs_[Bp];
@@ -678,7 +769,7 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
       }
       g->launch(s);
     } else {
-      record_score(Bp, s, c != nullptr, ar);
+      record_score(Bp, s, c != nullptr, ar, sr);
     }
     HIP_CHECK(hipMemcpyAsync(tok_logp + (size_t)start * ML, stok_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(rank + (size_t)start * ML, srank_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));

@@ -54,9 +54,15 @@ class Generator {
     // Automaton (docs/DESIGN.md §4g; both set with allow_tab, never with allow_idx; allow_rows = the
     // states, <= kAutoStates): allow_next [allow_rows][V], allow_start [N] the names' start states
     const unsigned short* allow_next = nullptr; const int* allow_start = nullptr;
+    // Soft controls (docs/DESIGN.md §4h; all four set, or all null; 1 <= soft_rows <= kSoftRows):
+    // soft_tab [soft_rows][V] the bias lines, soft_idx / soft_pres / soft_freq [N] the names' line and
+    // penalties.  They combine with the constraints and with an automaton.
+    const float* soft_tab = nullptr; const int* soft_idx = nullptr; int soft_rows = 0;
+    const float* soft_pres = nullptr; const float* soft_freq = nullptr;
   };
   static constexpr int kAllowRows = 1024;   // lines of a constraint table
   static constexpr int kAutoStates = 65535; // states of an automaton
+  static constexpr int kSoftRows = 256;     // lines of a soft-control bias table
   static constexpr size_t kAutoGraphs = 16; // automaton recordings kept per map (a full map is dropped before the next one)
   // An automaton-constrained generate_ctl() / beam() (score() never sees one: the host walks its known
   // rows into an allow_idx) uploads tab and next once per call into buffers that
@@ -64,7 +70,16 @@ class Generator {
   // batch takes the controlled per-char graph (beam: its graph) in a recording of its own per (n,
   // states), whose head resets the per-row state buffer from the batch's start states and whose
   // sampler (select) advances it.  Growing the buffers drops those recordings.
+  // A soft generate_ctl() / score() (c.soft_tab set) copies the bias table once per call and each batch's
+  // soft_idx / soft_pres / soft_freq slice into buffers of their own -- plain allocations made by the first
+  // soft call, so the arenas and the workspace sizes of calls without soft controls stay what they are.
+  // Every soft batch takes the controlled per-char graph (uses_persist_ctl / uses_persist_con are not
+  // consulted: the persistent sampler has no soft terms), in recordings of their own, kept in maps apart
+  // from the others': a call without soft controls never replays a soft recording, nor the reverse.
   void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
+  int soft_graphs() const {   // soft recordings so far (generation and scoring)
+    return (int)(csgraphs_.size() + asgraphs_.size() + scsgraphs_.size());
+  }
   size_t ctl_workspace_bytes() const { return carena_.bytes(); }   // 0 until a batch takes the per-char controlled graph
   // generate_ctl() batches of n names run as one controlled persistent launch (exact fp32, as the plain
   // one): up to GK_GEN_PERSIST_CTL_MAX names (default and at most 64), where a controlled variant
@@ -114,7 +129,9 @@ class Generator {
   int automaton_graphs() const { return (int)(agraphs_.size() + abgraphs_.size()); }   // ... with an automaton
   void set_use_graph(bool g) { use_graph_ = g; }
   // optional: device [Bp][V] softmax of the last generated step (tests)
-  void set_probe(float* probs) { probe_ = probs; graphs_.clear(); cgraphs_.clear(); agraphs_.clear(); }
+  void set_probe(float* probs) {
+    probe_ = probs; graphs_.clear(); cgraphs_.clear(); agraphs_.clear(); csgraphs_.clear(); asgraphs_.clear();
+  }
   // Small batches (fp32 modes: <= GK_GEN_PERSIST_MAX names, default and at most 64; bf16 mode: <= 24):
   // one persistent launch per batch (gen_persist.hip, exact fp32) instead of the per-char graph.
   // On by default; GK_GEN_PERSIST=0 or set_persist(false) turns it off.
@@ -140,7 +157,9 @@ class Generator {
   void record_steps(int n_active, hipStream_t s);
   // ctl: sample_ctl_f32 as the sampler node; allow_rows > 0: with the constraint buffers
   // automaton: allow_rows states, the sampler reads atab_ / anxt_ / astate_ and the head resets astate_
-  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false, int allow_rows = 0, bool automaton = false);
+  // soft: the sampler reads the soft-control buffers too (soft_rows lines)
+  void record_steps_f32(int n_active, hipStream_t s, bool ctl = false, int allow_rows = 0, bool automaton = false,
+                        int soft_rows = 0);
   // one product of the fp32 / bf16x3 path: C = h W^T (+ bias) -> splits (slabs of M x N at C).  fp32
   // reads A32 / W32; bf16x3 the split copies A3 ([hi|hi|lo] rows) / W3 ([hi|lo|hi] rows)
   int product_f32(const float* A32, const u16* A3, const float* W32, const u16* W3, const float* bias, int M, int N,
@@ -154,7 +173,8 @@ class Generator {
   // off, the bit is cleared and the caller regenerates the batch on its per-char graph
   bool persist_launch(const float* rf, int n, const Ctl* c, unsigned char* out, bool last_batch, hipStream_t s);
   // ctl: score_ctl_logprob_f32 as the last launch; allow_rows > 0: with the constraint buffers
-  void record_score(int Bp, hipStream_t s, bool ctl = false, int allow_rows = 0);
+  void record_score(int Bp, hipStream_t s, bool ctl = false, int allow_rows = 0, int soft_rows = 0);
+  void soft_alloc();
   void score_ctl_alloc();
   void beam_alloc();
   void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false);
@@ -260,6 +280,17 @@ class Generator {
   int* abstate_[2] = {nullptr, nullptr};        // [Bmax] x2 the beam rows' states, by step parity
   std::map<std::pair<int, int>, std::unique_ptr<Graph>> agraphs_;          // keyed by (n, states)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> abgraphs_;   // keyed by (names, W, states)
+  // soft controls (plain allocations, made by the first soft call): one set for generate_ctl(), one for score()
+  struct SoftBufs {
+    float* tab = nullptr;                       // [kSoftRows][V] the call's bias lines
+    int* idx = nullptr;                         // [Bmax] the current batch's lines
+    float *pres = nullptr, *freq = nullptr;     // [Bmax] each: its penalties
+  };
+  SoftBufs gsoft_, ssoft_;
+  // soft recordings, keyed as cgraphs_ / agraphs_ / scgraphs_ with the bias table's line count added
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> csgraphs_;    // (n, constraint lines or 0, soft lines)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> asgraphs_;    // (n, states, soft lines)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> scsgraphs_;   // (Bp, constraint lines or 0, soft lines)
   static constexpr int kF32SlabRows = 2048;   // fp32 split-K slab capacity (rows x 3H)
 };
 

@@ -16,10 +16,13 @@
 // order, so neutral controls give the plain sampler's bytes.
 //
 // The persistent generator's controlled variants carry a second copy of this rule, ctl_sample_wave
-// (gen_sample_ctl.h), written for a kernel with no registers to spare: a change to one belongs in
-// the other (tests/test_sampling_ctl_gpu.py holds this one, tests/test_gen_persist_ctl_gpu.py that).
-// A third copy scores rows under this distribution: score_ctl_logprob_f32_kernel (score_ctl.hip,
-// tests/test_score_ctl_gpu.py).
+// (gen_sample_ctl.h), written for a kernel with no registers to spare: a change to the kept-set rule in
+// one belongs in the other (tests/test_sampling_ctl_gpu.py holds this one,
+// tests/test_gen_persist_ctl_gpu.py that).  A third copy scores rows under this distribution:
+// score_ctl_logprob_f32_kernel (score_ctl.hip, tests/test_score_ctl_gpu.py).
+// The soft terms below (SOFT) exist only in this copy and the scoring one: a soft batch always takes
+// the per-char graph, because the persistent launch has no registers left for a lane's bias and count
+// values and its cost there has not been measured (docs/DESIGN.md §4h).  ctl_sample_wave is unchanged.
 //
 // Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy's: MASKED, gen_sample_ctl.h): a row's
 // allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one
@@ -30,6 +33,14 @@
 // function of the step but a per-row state in device memory.  Every lane reads it (one uniform 4-byte
 // load), and once the char is known lane 0 stores the successor, a 2-byte load from allow_next -- on a
 // forced step too, which reads no mask but still advances.  AUTO = false is the kernel as it was.
+//
+// Soft controls (docs/DESIGN.md §4h, the SOFT instantiations, with any MASK / AUTO): a row has a line of
+// a table of fp32 logit biases (one uniform index load, V/64 loads per lane), a presence and a frequency
+// penalty.  n[c] counts char c among the row's own output bytes 0 .. step-1 -- at most max_len
+// wave-uniform byte loads, each compared against the lane's chars, skipped when both penalties are 0 --
+// and v = (x + bias) - (frequency * n (+ presence if n > 0)), three fp32 operations in this order with
+// contraction off, takes x's place before the temperature scale.  A forced step reads none of it.
+// SOFT = false is the kernel as it was.
 #include "kernels.h"
 #include "common.h"
 #include "gen_sample.h"
@@ -43,7 +54,7 @@ DEV unsigned order_key(float f) {
   return (b >> 31) ? ~b : (b | 0x80000000u);
 }
 
-template <int MAXPER, bool MASK, bool AUTO = false>
+template <int MAXPER, bool MASK, bool AUTO = false, bool SOFT = false>
 __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
 #pragma clang fp contract(off)
   const SampleF32Args& a = c.s;
@@ -99,6 +110,39 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
       }
       ok = c.allow_tab[(size_t)ar * (V >> 5) + ((lane * per) >> 5)] >> ((lane * per) & 31);
     }
+    float sbias[SOFT ? MAXPER : 1];   // SOFT: this lane's biases and penalties
+    float spen[SOFT ? MAXPER : 1];
+    if constexpr (SOFT) {
+      int sr = c.soft_idx[cb];
+      if (sr < 0 || sr >= c.soft_rows) {   // never expected (the host builds both): flag it, no bias
+        if (c.err && lane == 0) {
+          atomicOr(c.err, 16u);
+          c.err[1] = (unsigned)sr;
+          c.err[2] = (unsigned)b;
+        }
+        sr = 0;
+      }
+      const float* brow = c.soft_tab + (size_t)sr * V + lane * per;
+      const float pres = c.soft_pres[cb], freq = c.soft_freq[cb];
+      int cnt[MAXPER];
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) cnt[e] = 0;
+      if (pres != 0.f || freq != 0.f) {   // (with both 0 every penalty is +0 whatever the counts are)
+        const unsigned char* orow = a.out + (size_t)b * (a.max_len + 1);
+        for (int j = 0; j < a.step; ++j) {
+          const int ch = orow[j];
+#pragma unroll
+          for (int e = 0; e < MAXPER; ++e) cnt[e] += (e < per && lane * per + e == ch) ? 1 : 0;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) {
+        sbias[e] = e < per ? brow[e] : 0.f;
+        float pn = freq * (float)cnt[e];
+        if (cnt[e] > 0) pn = pn + pres;
+        spen[e] = pn;
+      }
+    }
     float y[MAXPER];
     float mx = -INFINITY;
 #pragma unroll
@@ -107,6 +151,7 @@ __global__ void __launch_bounds__(64) sample_ctl_f32_kernel(SampleCtlArgs c) {
         float v = x[e];
         for (int s2 = 1; s2 < a.splits; ++s2) v += x[s2 * a.slab + e];   // split-K slabs, fixed order
         if (a.bias) v += a.bias[lane * per + e];
+        if constexpr (SOFT) v = (v + sbias[e]) - spen[e];
         y[e] = v * scale;
         if constexpr (MASK)
           if (!((ok >> e) & 1u)) y[e] = -INFINITY;
@@ -247,8 +292,26 @@ void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s) {
     throw std::runtime_error("sample_ctl_f32: allow_state and allow_next are set together, with allow_tab and without allow_idx");
   if (c.allow_state && c.allow_rows > 65535)
     throw std::runtime_error("sample_ctl_f32: an automaton has at most 65535 states");
+  const bool soft = c.soft_tab != nullptr;
+  if (soft != (c.soft_idx != nullptr) || soft != (c.soft_pres != nullptr) || soft != (c.soft_freq != nullptr) ||
+      (soft && c.soft_rows < 1))
+    throw std::runtime_error("sample_ctl_f32: soft_tab, soft_idx, soft_pres and soft_freq are set together, with soft_rows >= 1");
   if (a.N <= 0) return;
   const dim3 grid(a.N), block(64);
+  if (soft) {   // the SOFT instantiations; every other call launches what it launched before
+    if (c.allow_state) {
+      if (a.V == 256) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true, true, true>), grid, block, 0, s, c);
+      else if (a.V == 512) hipLaunchKernelGGL((sample_ctl_f32_kernel<8, true, true, true>), grid, block, 0, s, c);
+      else throw std::runtime_error("sample_ctl_f32: the automaton instantiations need V = 256 or 512");
+    } else if (a.V == 256) {
+      if (mask) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true, false, true>), grid, block, 0, s, c);
+      else hipLaunchKernelGGL((sample_ctl_f32_kernel<4, false, false, true>), grid, block, 0, s, c);
+    } else {
+      if (mask) hipLaunchKernelGGL((sample_ctl_f32_kernel<8, true, false, true>), grid, block, 0, s, c);
+      else hipLaunchKernelGGL((sample_ctl_f32_kernel<8, false, false, true>), grid, block, 0, s, c);
+    }
+    return;
+  }
   if (c.allow_state) {
     if (a.V == 256) hipLaunchKernelGGL((sample_ctl_f32_kernel<4, true, true>), grid, block, 0, s, c);
     else if (a.V == 512) hipLaunchKernelGGL((sample_ctl_f32_kernel<8, true, true>), grid, block, 0, s, c);

@@ -402,6 +402,16 @@ struct SampleCtlArgs {
   // mask but still advances).  The host builds allow_next with every entry < allow_rows.
   int* allow_state = nullptr;                    // nullable [..]: read and written
   const unsigned short* allow_next = nullptr;    // nullable [allow_rows][V]
+  // Soft controls (docs/DESIGN.md §4h; all four set, or all null): on a step that is not forced the
+  // sampler runs on v[c] = (x[c] + soft_tab[soft_idx[b + row0]][c]) - pen[c], pen = soft_freq[b + row0] *
+  // n[c] (+ soft_pres[b + row0] if n[c] > 0), n[c] = the count of byte c among out[b][0 .. step-1]; three
+  // fp32 operations in this order.  An index outside [0, soft_rows) is the allow_idx rule: 16 into
+  // err[0], line 0.
+  const float* soft_tab = nullptr;               // nullable [soft_rows][V]
+  const int* soft_idx = nullptr;                 // nullable [..]
+  int soft_rows = 0;
+  const float* soft_pres = nullptr;              // nullable [..]
+  const float* soft_freq = nullptr;              // nullable [..]
 };
 void sample_ctl_f32(const SampleCtlArgs& c, hipStream_t s);
 // state[i] = start[i] for i < n, 0 (the free state) for n <= i < Bp: the head of an automaton batch as
@@ -571,6 +581,13 @@ struct ScoreCtlArgs {
   const int* allow_idx = nullptr;          // nullable [..][ML]
   int allow_rows = 0;
   int* n_kept = nullptr;                   // [Bp][ML]
+  // Soft controls (SampleCtlArgs' fields and rule; the counts are those of the name's targets before
+  // the position; rank stays the model's)
+  const float* soft_tab = nullptr;         // nullable [soft_rows][V]
+  const int* soft_idx = nullptr;           // nullable [..]
+  int soft_rows = 0;
+  const float* soft_pres = nullptr;        // nullable [..]
+  const float* soft_freq = nullptr;        // nullable [..]
 };
 void score_ctl_logprob_f32(const ScoreCtlArgs& c, hipStream_t s);
 

@@ -13,6 +13,12 @@
 // third copy of that rule (gen_ctl.hip, gen_sample_ctl.h: ctl_sample_wave): a change to one belongs in
 // the others (tests/test_score_ctl_gpu.py holds this one).  With nothing filtered every statistic is
 // formed by the operations of score_logprob_f32_kernel in its order, so neutral controls give its bytes.
+//
+// Soft controls (docs/DESIGN.md §4h, the SOFT instantiations; gen_ctl.hip's and this copy only, the
+// persistent sampler has none): the name's bias line and two penalties are read once before the loop, and
+// the counts n[c] of the scored row's bytes before position l are kept per lane as the loop advances (the
+// targets are the row's bytes).  v = (x + bias) - pen takes x's place in the kept-set rule; rank stays
+// the model's, on the raw logits.  SOFT = false is the kernel as it was.
 #include <cmath>
 #include <stdexcept>
 #include "kernels.h"
@@ -30,7 +36,7 @@ DEV unsigned score_order_key(float f) {
 
 // One wave per name (block b of Bp): rows b >= N have n_tok = 0, read no control and only write their
 // masked outputs.
-template <int MAXPER, bool MASK>
+template <int MAXPER, bool MASK, bool SOFT = false>
 __global__ void __launch_bounds__(64) score_ctl_logprob_f32_kernel(ScoreCtlArgs c) {
 #pragma clang fp contract(off)
   const ScoreLogprobArgs& a = c.s;
@@ -46,6 +52,33 @@ __global__ void __launch_bounds__(64) score_ctl_logprob_f32_kernel(ScoreCtlArgs 
     pl = c.plen[cb];
   }
   const float scale = it == 0.f ? 1.f : it;
+  float sbias[SOFT ? MAXPER : 1];   // SOFT: this lane's biases, the name's penalties and the counts so far
+  int scnt[SOFT ? MAXPER : 1];
+  float pres = 0.f, freq = 0.f;
+  if constexpr (SOFT) {
+#pragma unroll
+    for (int e = 0; e < MAXPER; ++e) {
+      sbias[e] = 0.f;
+      scnt[e] = 0;
+    }
+    if (nt > 0) {
+      int sr = c.soft_idx[cb];
+      if (sr < 0 || sr >= c.soft_rows) {   // never expected (the host builds both): flag it, no bias
+        if (c.err && lane == 0) {
+          atomicOr(c.err, 16u);
+          c.err[1] = (unsigned)sr;
+          c.err[2] = (unsigned)b;
+        }
+        sr = 0;
+      }
+      const float* brow = c.soft_tab + (size_t)sr * V + lane * per;
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e)
+        if (e < per) sbias[e] = brow[e];
+      pres = c.soft_pres[cb];
+      freq = c.soft_freq[cb];
+    }
+  }
   float sum = 0.f;
   for (int l = 0; l < nt; ++l) {
     const size_t row = (size_t)l * a.Bp + b;
@@ -99,7 +132,13 @@ __global__ void __launch_bounds__(64) score_ctl_logprob_f32_kernel(ScoreCtlArgs 
       float mx = -INFINITY;
 #pragma unroll
       for (int e = 0; e < MAXPER; ++e) {
-        y[e] = e < per ? xv[e] * scale : -INFINITY;
+        float v = xv[e];
+        if constexpr (SOFT) {
+          float pn = freq * (float)scnt[e];
+          if (scnt[e] > 0) pn = pn + pres;
+          v = (v + sbias[e]) - pn;
+        }
+        y[e] = e < per ? v * scale : -INFINITY;
         if constexpr (MASK)
           if (!((ok >> e) & 1u)) y[e] = -INFINITY;
         mx = fmaxf(mx, y[e]);
@@ -187,6 +226,10 @@ __global__ void __launch_bounds__(64) score_ctl_logprob_f32_kernel(ScoreCtlArgs 
         lp = kt ? (yt - mx) - logf(se) : -INFINITY;
       }
     }
+    if constexpr (SOFT) {   // the row's byte at l joins the counts of the later positions (a forced one too)
+#pragma unroll
+      for (int e = 0; e < MAXPER; ++e) scnt[e] += (e < per && lane * per + e == t) ? 1 : 0;
+    }
     sum += lp;   // step order, the same value in every lane; -inf stays -inf (no +inf ever joins it)
     if (lane == 0) {
       a.tok_logp[(size_t)b * ML + l] = lp;
@@ -218,8 +261,22 @@ void score_ctl_logprob_f32(const ScoreCtlArgs& c, hipStream_t s) {
   const bool mask = c.allow_tab != nullptr;
   if (mask && (c.allow_rows < 1 || 32 % (a.V / 64)))
     throw std::runtime_error("score_ctl_logprob_f32: constraints need allow_rows >= 1 and V / 64 in {1, 2, 4, 8}");
+  const bool soft = c.soft_tab != nullptr;
+  if (soft != (c.soft_idx != nullptr) || soft != (c.soft_pres != nullptr) || soft != (c.soft_freq != nullptr) ||
+      (soft && c.soft_rows < 1))
+    throw std::runtime_error("score_ctl_logprob_f32: soft_tab, soft_idx, soft_pres and soft_freq are set together, with soft_rows >= 1");
   if (a.Bp <= 0) return;
   const dim3 grid(a.Bp), block(64);
+  if (soft) {   // the SOFT instantiations; every other call launches what it launched before
+    if (a.V <= 256) {
+      if (mask) hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<4, true, true>), grid, block, 0, s, c);
+      else hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<4, false, true>), grid, block, 0, s, c);
+    } else {
+      if (mask) hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<8, true, true>), grid, block, 0, s, c);
+      else hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<8, false, true>), grid, block, 0, s, c);
+    }
+    return;
+  }
   if (a.V <= 256) {
     if (mask) hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<4, true>), grid, block, 0, s, c);
     else hipLaunchKernelGGL((score_ctl_logprob_f32_kernel<4, false>), grid, block, 0, s, c);

@@ -107,8 +107,22 @@ class HipGenerator:
     def _constraint_args(t) -> tuple:
         return tuple(0 if v is None else (v if isinstance(v, int) else v.data_ptr()) for v in t)
 
+    def _soft_tensors(self, soft):
+        """A Soft object's arrays on the device (docs/DESIGN.md §4h): the tuple holds the tensors alive;
+        ``_soft_kwargs`` turns it into the native call's keywords."""
+        return (torch.from_numpy(np.ascontiguousarray(soft.tab, dtype=np.float32)).to(self.dev),
+                torch.from_numpy(np.ascontiguousarray(soft.idx, dtype=np.int32)).to(self.dev), soft.rows,
+                torch.from_numpy(np.ascontiguousarray(soft.presence, dtype=np.float32)).to(self.dev),
+                torch.from_numpy(np.ascontiguousarray(soft.frequency, dtype=np.float32)).to(self.dev))
+
+    @staticmethod
+    def _soft_kwargs(t) -> dict:
+        return dict(soft_tab=t[0].data_ptr(), soft_idx=t[1].data_ptr(), soft_rows=t[2], soft_pres=t[3].data_ptr(),
+                    soft_freq=t[4].data_ptr())
+
     def generate_device(self, rf_dev: torch.Tensor, n: int, *, temperature=None, top_k=None, top_p=None,
-                        prefix=None, constraints=None) -> torch.Tensor:
+                        prefix=None, constraints=None, logit_bias=None, presence_penalty=None,
+                        frequency_penalty=None) -> torch.Tensor:
         """``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` (scalars or one value per name; semantics:
         cpu_ref.make_controls, docs/DESIGN.md §4b): any that is not None -- a neutral value too -- takes
         the controlled path (fp32 / bf16x3 only): per batch one controlled persistent launch where
@@ -118,12 +132,18 @@ class HipGenerator:
         controlled per-char graph, or -- batches of up to ``persist_constraints`` names -- in one
         constrained persistent launch.  With ``regex`` / ``exclude`` among the keywords, or a
         cpu_ref.Automaton (docs/DESIGN.md §4g), the sets follow what the name has emitted so far: the same
-        graph with a per-row state that the sampler advances.  Bad values raise ValueError before anything
+        graph with a per-row state that the sampler advances.
+        ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` (cpu_ref.make_soft's arguments;
+        docs/DESIGN.md §4h): soft preferences -- a per-char additive bias (a dict {chars: value}, V values, or
+        one of those per name), a deduction for every char the name already holds and one per earlier
+        occurrence.  Any that is not None takes the controlled per-char graph, whatever the batch size, and
+        combines with every control and constraint above.  Bad values raise ValueError before anything
         is launched."""
         ML = self.cfg.max_len
         ctl = None
         cons = cpu_ref.as_constraints(self.cfg, max(n, 0), constraints)
-        if cons is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        soft = cpu_ref.as_soft(self.cfg, max(n, 0), None, logit_bias, presence_penalty, frequency_penalty)
+        if cons is not None or soft is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
             if self.precision == "bf16":
                 raise ValueError('sampling controls and constraints need precision "fp32" or "bf16x3" (the bf16 '
                                  "mode samples inside its fused FC kernel)")
@@ -138,22 +158,30 @@ class HipGenerator:
             if cons is not None:
                 held = self._constraint_tensors(cons)
                 extra = self._constraint_args(held)
-            self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s(), *extra)
+            skw = {}
+            if soft is not None:
+                sheld = self._soft_tensors(soft)
+                skw = self._soft_kwargs(sheld)
+            self.g.generate_ctl(rf_dev.data_ptr(), n, *[t.data_ptr() for t in dev], out.data_ptr(), self._s(), *extra,
+                                **skw)
             err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
             if err:
                 raise RuntimeError(f"HipGenerator.generate: device error word {err}")
         return out[:n]
 
     def generate(self, rfloats: np.ndarray, start: int = 0, count: Optional[int] = None, *, temperature=None,
-                 top_k=None, top_p=None, prefix=None, constraints=None) -> np.ndarray:
-        """Names ``start .. start+count-1`` of the job.  The controls and constraints are generate_device's;
-        per-name values are indexed by the generated names (``count`` entries)."""
+                 top_k=None, top_p=None, prefix=None, constraints=None, logit_bias=None, presence_penalty=None,
+                 frequency_penalty=None) -> np.ndarray:
+        """Names ``start .. start+count-1`` of the job.  The controls, constraints and soft controls are
+        generate_device's; per-name values are indexed by the generated names (``count`` entries)."""
         ML = self.cfg.max_len
         N = (rfloats.size // ML - start) if count is None else count
         rf = torch.from_numpy(np.ascontiguousarray(rfloats[start * ML:(start + N) * ML], dtype=np.float32))
         rf = rf.to(self.dev)
         return self.generate_device(rf, N, temperature=temperature, top_k=top_k, top_p=top_p,
-                                    prefix=prefix, constraints=constraints).cpu().numpy()
+                                    prefix=prefix, constraints=constraints, logit_bias=logit_bias,
+                                    presence_penalty=presence_penalty,
+                                    frequency_penalty=frequency_penalty).cpu().numpy()
 
     def load_state(self, params: Dict[str, torch.Tensor]) -> None:
         """New weights (cfg-shaped tensors) into the flat buffer; every derived copy and table follows."""
@@ -164,7 +192,7 @@ class HipGenerator:
         self.g.refresh_weights(self._s())
 
     def score(self, rows: np.ndarray, *, temperature=None, top_k=None, top_p=None, prefix=None,
-              constraints=None) -> "ScoreResult":
+              constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None) -> "ScoreResult":
         """Teacher-forced log-likelihood of output rows ([N, MAX_LEN+1] or flat uint8, the format
         ``generate`` writes; semantics: cpu_ref.score_inputs).  Always exact fp32 arithmetic, whatever
         ``precision`` this generator samples with.  A byte >= vocab at a scored position raises
@@ -173,12 +201,16 @@ class HipGenerator:
         or one value per row; the rule: cpu_ref.score, docs/DESIGN.md §4f): any that is not None -- a neutral
         value too -- scores the rows under the distribution ``generate`` samples from with these settings:
         exp(name_logp) is the probability that it emits exactly that row, -inf marks a row it cannot emit,
-        and the result carries n_kept.  Every precision mode takes them.  Bad values raise ValueError
+        and the result carries n_kept.  ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty``
+        (``generate``'s soft controls, docs/DESIGN.md §4h) do the same; their counts are those of the scored
+        row's bytes before the position.  Every precision mode takes them all.  Bad values raise ValueError
         before anything is launched."""
         ML = self.cfg.max_len
-        ctl = cons = None
-        if constraints is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        ctl = cons = soft = None
+        soft_given = any(v is not None for v in (logit_bias, presence_penalty, frequency_penalty))
+        if constraints is not None or soft_given or any(v is not None for v in (temperature, top_k, top_p, prefix)):
             count = np.ascontiguousarray(rows, dtype=np.uint8).size // (ML + 1)
+            soft = cpu_ref.as_soft(self.cfg, count, None, logit_bias, presence_penalty, frequency_penalty)
             cons = cpu_ref.as_constraints(self.cfg, count, constraints)
             ctl = cpu_ref.make_controls(self.cfg, count, temperature, top_k, top_p, prefix)
             cpu_ref.check_prefix_allowed(cons, ctl.prefix, ctl.plen)
@@ -207,8 +239,12 @@ class HipGenerator:
             if cons is not None:
                 held = self._constraint_tensors(cons)
                 extra = self._constraint_args(held)
+            skw = {}
+            if soft is not None:
+                sheld = self._soft_tensors(soft)
+                skw = self._soft_kwargs(sheld)
             self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s(),
-                         *[t.data_ptr() for t in dev], nk.data_ptr(), *extra)
+                         *[t.data_ptr() for t in dev], nk.data_ptr(), *extra, **skw)
         err = self.g.read_error()   # synchronises: the control tensors stay alive until the call is done
         if err:
             raise RuntimeError(f"HipGenerator.score: device error word {err}")
@@ -384,6 +420,16 @@ def _slice_control(v, N: int, start: int, count: int):
     return v[start:start + count]
 
 
+def _slice_logit_bias(v, N: int, start: int, count: int):
+    """This rank's part of ``logit_bias``: one row (a dict or V values) applies to every name, a list of N
+    rows is sliced by global name index."""
+    if cpu_ref._soft_is_single(v):
+        return v
+    if len(v) != N:
+        raise ValueError(f"logit_bias: one row or {N} rows expected, got {len(v)}")
+    return v[start:start + count]
+
+
 def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: int):
     """This rank's part of the job's constraints: a Constraints object's idx rows by global name index
     (the table is shared), a keyword dict's per-name values like any control."""
@@ -403,14 +449,16 @@ def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: i
 
 
 def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
-            prefix=None, constraints=None, persist_constraints=None) -> None:
+            prefix=None, constraints=None, persist_constraints=None, logit_bias=None, presence_penalty=None,
+            frequency_penalty=None) -> None:
     """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
     scalars or one value per name of the job; every rank takes its names' slice.  ``constraints``: a
     cpu_ref.Constraints / cpu_ref.Automaton for the N names or a dict of make_constraints keywords
     (docs/DESIGN.md §4e, §4g: ``regex`` / ``exclude``), sliced by global name index like the prefixes.
     ``persist_constraints``: HipGenerator.set_persist_constraints for this and later calls (None: as it
-    is); the CPU path ignores it."""
+    is); the CPU path ignores it.  ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty``: the soft
+    controls (docs/DESIGN.md §4h), one value for every name or one per name of the job, sliced likewise."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len
@@ -420,6 +468,11 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
            (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("prefix", prefix)) if v is not None}
     if constraints is not None:
         ctl["constraints"] = _slice_constraints(cfg, constraints, N, start, count)
+    if logit_bias is not None:
+        ctl["logit_bias"] = _slice_logit_bias(logit_bias, N, start, count)
+    for k, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+        if v is not None:
+            ctl[k] = _slice_control(v, N, start, count)
     if _S.gen is not None:
         if persist_constraints is not None:
             _S.gen.set_persist_constraints(persist_constraints)

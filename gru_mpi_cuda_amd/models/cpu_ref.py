@@ -225,7 +225,7 @@ def score_inputs(cfg: GRUConfig, rows: np.ndarray):
 
 
 def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, top_k=None, top_p=None, prefix=None,
-          constraints=None):
+          constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None, soft=None):
     """log P of output rows under the model, teacher-forced from a zero hidden state (score_inputs).
 
     Returns numpy (tok_logp [N, ML], name_logp [N], n_tok [N] int32, rank [N, ML] int32) in the dtype
@@ -244,10 +244,16 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, to
         tok_logp = (y_t - max_K y) - log sum_K exp(y_j - max_K y) for t in K and exactly -inf outside.
     Never NaN; name_logp is the step-order sum, so one -inf makes it -inf: exp(name_logp) is the
     probability that ``generate`` with these settings emits exactly this row.  rank stays the model's
-    rank on the raw logits, n_tok is read from the row alone."""
+    rank on the raw logits, n_tok is read from the row alone.
+
+    ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` or ``soft`` (``generate``'s; docs/DESIGN.md
+    §4h): they take the controlled rule too, on v = (x + bias) - pen with the counts of the scored row's
+    bytes before the position; n_kept is the adjusted kept set's size, rank stays the model's."""
     ctl = cons = None
-    if constraints is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+    soft_given = soft is not None or any(v is not None for v in (logit_bias, presence_penalty, frequency_penalty))
+    if constraints is not None or soft_given or any(v is not None for v in (temperature, top_k, top_p, prefix)):
         count = np.ascontiguousarray(rows, dtype=np.uint8).size // (cfg.max_len + 1)
+        soft = as_soft(cfg, count, soft, logit_bias, presence_penalty, frequency_penalty)
         cons = as_constraints(cfg, count, constraints)
         ctl = make_controls(cfg, count, temperature, top_k, top_p, prefix)
         check_prefix_allowed(cons, ctl.prefix, ctl.plen)
@@ -274,7 +280,7 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, to
     rank = torch.where(mask, rank, torch.full_like(rank, -1))
     n_kept = None
     if ctl is not None:
-        lp, n_kept = _score_controlled(logits, tgt, mask, ctl, cons)
+        lp, n_kept = _score_controlled(logits, tgt, mask, ctl, cons, soft, rows)
     name = torch.zeros(N, dtype=lp.dtype)
     for l in range(ML):   # step order, as the device sums
         name = name + lp[:, l]
@@ -282,7 +288,8 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, to
     return out if ctl is None else out + (n_kept,)
 
 
-def _score_controlled(logits: torch.Tensor, tgt: np.ndarray, mask: torch.Tensor, ctl: "Controls", cons):
+def _score_controlled(logits: torch.Tensor, tgt: np.ndarray, mask: torch.Tensor, ctl: "Controls", cons,
+                      soft: Optional["Soft"] = None, rows_u8: Optional[np.ndarray] = None):
     """tok_logp [N, ML] (torch) and n_kept [N, ML] int32 of ``score``'s controlled rule: per step the kept
     set of ``_filter`` and the log-softmax over it, formed in the log domain (no log of a rounded
     probability)."""
@@ -299,8 +306,9 @@ def _score_controlled(logits: torch.Tensor, tgt: np.ndarray, mask: torch.Tensor,
         if not live.any():
             continue
         t = torch.from_numpy(np.maximum(tgt[:, l], 0))
-        _, keep = _filter(logits[:, l], ctl.inv_temp, ctl.top_k, ctl.top_p, None if cons is None else cons.allowed(l))
-        y = logits[:, l] * scale                               # _filter's y: rounded once, in the logits' dtype
+        xl = logits[:, l] if soft is None else soft_adjust(logits[:, l], soft, rows_u8[:, :l])   # §4h
+        _, keep = _filter(xl, ctl.inv_temp, ctl.top_k, ctl.top_p, None if cons is None else cons.allowed(l))
+        y = xl * scale                               # _filter's y: rounded once, in the logits' dtype
         # (with everything kept and T == 1 these are the plain call's operations: its bytes)
         ls = torch.log_softmax(torch.where(keep, y, ninf), -1)
         step = torch.where(keep[rows, t], ls[rows, t], ninf)
@@ -1196,12 +1204,187 @@ def make_automaton(cfg: GRUConfig, count: int, regex=None, exclude=None, charset
     return Automaton(tab, np.ascontiguousarray(nxt.astype(np.uint16)), np.ascontiguousarray(start.astype(np.int32)), V)
 
 
-def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray,
-            allowed: Optional[np.ndarray] = None):
-    """Steps 2-7 on logits x [N, V] with Controls arrays of N entries (and the rows' allowed sets, bool
-    [N, V], None: everything) -> (probs [N, V], keep [N, V])."""
+# Soft controls (docs/DESIGN.md §4h): preferences instead of rules.  A name has a row of V additive logit
+# biases, a presence penalty and a frequency penalty.  At a step l that its prefix does not force, with the
+# model's logits x (fp32, after the FC bias):
+#     n[c] = how often byte c occurs among the row's bytes 0 .. l-1 (forced chars count, SOS is not there)
+#     pen  = frequency * float(n[c]);  if n[c] > 0: pen = pen + presence
+#     v[c] = (x[c] + bias[c]) - pen            three fp32 operations in this order, never fused
+# and v takes x's place in steps 2-7 above: the temperature scale, the mask, greedy, top-k and top-p all
+# see the adjusted values.  A forced step reads none of it.  All-zero values leave v bitwise x (x + 0 and
+# v - 0 are exact, and the top-k key folds -0 into +0), so neutral soft controls give the call's bytes
+# without them.  Every value is finite and at most 1e4 in magnitude: a ban is charset's job, and a finite
+# bias never empties an allowed set.  The penalties count bytes, so they need a vocabulary of at most 256.
+SOFT_MAX_ROWS = 256
+SOFT_MAX_ABS = 1e4
+
+
+class Soft:
+    """Soft controls of ``count`` names: tab float32 [R, V] (line 0 all zero, lines distinct, R <= 256), idx
+    int32 [count] (a name's line), presence / frequency float32 [count]."""
+
+    def __init__(self, tab: np.ndarray, idx: np.ndarray, presence: np.ndarray, frequency: np.ndarray):
+        self.tab, self.idx, self.presence, self.frequency = tab, idx, presence, frequency
+
+    @property
+    def rows(self) -> int:
+        return int(self.tab.shape[0])
+
+    @property
+    def vocab(self) -> int:
+        return int(self.tab.shape[1])
+
+    def bias(self) -> np.ndarray:
+        """The names' bias rows, float32 [count, V]."""
+        return self.tab[self.idx]
+
+    def slice(self, start: int, count: int) -> "Soft":
+        """Names start .. start + count - 1 (the table is shared)."""
+        return Soft(self.tab, np.ascontiguousarray(self.idx[start:start + count]),
+                    np.ascontiguousarray(self.presence[start:start + count]),
+                    np.ascontiguousarray(self.frequency[start:start + count]))
+
+
+def _soft_value(v, what: str) -> float:
+    try:
+        f = float(v)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"{what}: a number expected, got {v!r}") from e
+    if not math.isfinite(f) or abs(f) > SOFT_MAX_ABS:
+        raise ValueError(f"{what} must be finite and at most {SOFT_MAX_ABS:g} in magnitude, got {v!r}")
+    return f
+
+
+def _soft_row(cfg: GRUConfig, spec) -> np.ndarray:
+    """One name's bias row, float32 [V]: None (zeros), a dict {chars or id: value} (a char named by several
+    keys gets their sum) or V values."""
+    V = cfg.vocab
+    if spec is None:
+        return np.zeros(V, np.float32)
+    if isinstance(spec, dict):
+        row = np.zeros(V, np.float64)
+        for key, val in spec.items():
+            f = _soft_value(val, f"logit_bias[{key!r}]")
+            if isinstance(key, (str, bytes)):
+                ids = list(_as_bytes(key, "logit_bias key"))
+            elif isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                ids = [int(key)]
+            else:
+                raise ValueError(f"logit_bias: a key is a str, bytes or an int id, got {key!r}")
+            for c in ids:
+                if not 0 <= c < V:
+                    raise ValueError(f"logit_bias key {key!r} names char {c} outside the vocabulary of {V}")
+                row[c] += f
+    else:
+        try:
+            row = np.asarray(spec, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"logit_bias: a dict or {V} values expected") from e
+        if row.shape != (V,):
+            raise ValueError(f"logit_bias: {V} values expected, got shape {row.shape}")
+    if not np.isfinite(row).all() or (np.abs(row) > SOFT_MAX_ABS).any():
+        raise ValueError(f"logit_bias values must be finite and at most {SOFT_MAX_ABS:g} in magnitude")
+    return row.astype(np.float32)
+
+
+def _soft_is_single(lb) -> bool:
+    if lb is None or isinstance(lb, dict):
+        return True
+    if isinstance(lb, np.ndarray):
+        return lb.ndim == 1 and lb.dtype != object
+    return len(lb) > 0 and all(np.ndim(v) == 0 and v is not None and not isinstance(v, dict) for v in lb)
+
+
+def make_soft(cfg: GRUConfig, count: int, logit_bias=None, presence_penalty=None, frequency_penalty=None) -> Soft:
+    """``logit_bias``: a dict {chars: value} -- keys str / bytes (every char in them) or an int id -- or an
+    array of V values, for every name; or a list of ``count`` of those (None: no bias).  ``presence_penalty``
+    / ``frequency_penalty``: a scalar or ``count`` values (None: 0).  ValueError for a value that is not
+    finite or above 1e4 in magnitude, a wrong length, a key outside the vocabulary, more than 256 distinct
+    bias rows, and a non-zero penalty with a vocabulary above 256 (the output row keeps only a char's low
+    byte)."""
+    count = int(count)
+    if count < 0:
+        raise ValueError("count must be >= 0")
+    V = cfg.vocab
+    pres = _per_name(0.0 if presence_penalty is None else presence_penalty, count, np.float64, "presence_penalty")
+    freq = _per_name(0.0 if frequency_penalty is None else frequency_penalty, count, np.float64, "frequency_penalty")
+    for a, what in ((pres, "presence_penalty"), (freq, "frequency_penalty")):
+        if not np.isfinite(a).all() or (np.abs(a) > SOFT_MAX_ABS).any():
+            raise ValueError(f"{what} must be finite and at most {SOFT_MAX_ABS:g} in magnitude")
+    for v, what in ((presence_penalty, "presence_penalty"), (frequency_penalty, "frequency_penalty")):
+        if v is not None and V > 256 and np.any(np.asarray(v, dtype=np.float64) != 0):
+            raise ValueError(f"{what} needs vocab <= 256 (got {V}): the output row keeps only a char's low byte")
+    lines: Dict[bytes, int] = {np.zeros(V, np.float32).tobytes(): 0}
+    idx = np.zeros(count, np.int32)
+    if _soft_is_single(logit_bias):
+        row = _soft_row(cfg, logit_bias) + np.float32(0)   # (-0 -> +0: one key per value)
+        idx[:] = lines.setdefault(row.tobytes(), len(lines))
+    else:
+        if len(logit_bias) != count:
+            raise ValueError(f"logit_bias: one row or {count} rows expected, got {len(logit_bias)}")
+        for n in range(count):
+            row = _soft_row(cfg, logit_bias[n]) + np.float32(0)
+            idx[n] = lines.setdefault(row.tobytes(), len(lines))
+    if len(lines) > SOFT_MAX_ROWS:
+        raise ValueError(f"{len(lines)} distinct logit_bias rows, more than {SOFT_MAX_ROWS}")
+    tab = np.stack([np.frombuffer(k, dtype=np.float32) for k in lines])        # insertion order = line number
+    return Soft(np.ascontiguousarray(tab), idx, pres.astype(np.float32), freq.astype(np.float32))
+
+
+def as_soft(cfg: GRUConfig, count: int, soft=None, logit_bias=None, presence_penalty=None,
+            frequency_penalty=None) -> Optional[Soft]:
+    """None when nothing is given, a checked ``soft`` object for ``count`` names, or ``make_soft`` of the three
+    keywords (a neutral value too: the caller asked for the controlled path)."""
+    given = any(v is not None for v in (logit_bias, presence_penalty, frequency_penalty))
+    if soft is None:
+        return make_soft(cfg, count, logit_bias, presence_penalty, frequency_penalty) if given else None
+    if given:
+        raise ValueError("soft: give a Soft object or the logit_bias / presence_penalty / frequency_penalty keywords")
+    if not isinstance(soft, Soft):
+        raise ValueError("soft: a Soft object (make_soft) expected")
+    s = soft
+    if (s.tab.ndim != 2 or s.tab.shape[1] != cfg.vocab or s.tab.dtype != np.float32 or s.idx.shape != (count,)
+            or s.presence.shape != (count,) or s.frequency.shape != (count,)):
+        raise ValueError(f"soft: tab float32 [R, {cfg.vocab}] and idx, presence, frequency [{count}] expected, got "
+                         f"{s.tab.shape}, {s.idx.shape}, {s.presence.shape} and {s.frequency.shape}")
+    if not 1 <= s.rows <= SOFT_MAX_ROWS:
+        raise ValueError(f"soft: 1 .. {SOFT_MAX_ROWS} table lines expected, got {s.rows}")
+    if s.idx.size and (s.idx.min() < 0 or s.idx.max() >= s.rows):
+        raise ValueError("soft: an idx entry outside the table")
+    for a in (s.tab, s.presence, s.frequency):
+        if not np.isfinite(a).all() or (np.abs(a) > SOFT_MAX_ABS).any():
+            raise ValueError(f"soft: values must be finite and at most {SOFT_MAX_ABS:g} in magnitude")
+    if cfg.vocab > 256 and (s.presence.any() or s.frequency.any()):
+        raise ValueError(f"soft: the penalties need vocab <= 256 (got {cfg.vocab})")
+    return s
+
+
+def soft_adjust(x: torch.Tensor, soft: Soft, emitted: Optional[np.ndarray]) -> torch.Tensor:
+    """v of the rule above: logits x [N, V], the rows' Soft and their bytes so far, uint8 [N, l] (None: no
+    byte yet).  Three operations in x's dtype, in the rule's order."""
     N, V = x.shape
     dt = x.dtype
+    if emitted is None or emitted.shape[1] == 0:
+        cnt = np.zeros((N, V), np.int64)
+    else:
+        e = np.asarray(emitted).reshape(N, -1).astype(np.int64)
+        cnt = (e[:, :, None] == np.arange(V)[None, None, :]).sum(1)
+    n = torch.from_numpy(cnt).to(dt)
+    b = torch.from_numpy(np.ascontiguousarray(soft.bias())).to(dt)
+    pen = torch.from_numpy(soft.frequency).to(dt).unsqueeze(-1) * n
+    pen = torch.where(n > 0, pen + torch.from_numpy(soft.presence).to(dt).unsqueeze(-1), pen)
+    return (x + b) - pen
+
+
+def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarray,
+            allowed: Optional[np.ndarray] = None, soft: Optional[Soft] = None, emitted: Optional[np.ndarray] = None):
+    """Steps 2-7 on logits x [N, V] with Controls arrays of N entries (and the rows' allowed sets, bool
+    [N, V], None: everything) -> (probs [N, V], keep [N, V]).  ``soft`` (with the rows' bytes so far,
+    ``emitted`` uint8 [N, l]): the rule runs on ``soft_adjust``'s values instead of x."""
+    N, V = x.shape
+    dt = x.dtype
+    if soft is not None:
+        x = soft_adjust(x, soft, emitted)
     inv_t = torch.from_numpy(inv)
     greedy = inv_t == 0
     y = x * torch.where(greedy, torch.ones_like(inv_t), inv_t).to(dt).unsqueeze(-1)
@@ -1231,13 +1414,16 @@ def _filter(x: torch.Tensor, inv: np.ndarray, top_k: np.ndarray, top_p: np.ndarr
     return torch.softmax(torch.where(keep, y, ninf), -1), keep
 
 
-def filter_probs(logits: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0, allowed=None) -> torch.Tensor:
+def filter_probs(logits: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0, allowed=None, soft=None,
+                 emitted=None) -> torch.Tensor:
     """The distribution step 7 samples from: logits [N, V] (or [V]) in fp32 or fp64 (fp64: the oracle),
     the controls scalars or N values.  T == 0 gives the one-hot row of the lowest arg-max.  ``allowed``:
-    bool [N, V] (or [V]), the rows' allowed sets (None: everything)."""
+    bool [N, V] (or [V]), the rows' allowed sets (None: everything).  ``soft`` / ``emitted``: the rows' Soft
+    object and their bytes so far (uint8 [N, l]), docs/DESIGN.md §4h."""
     x = logits.unsqueeze(0) if logits.dim() == 1 else logits
     c = make_controls(GRUConfig(vocab=x.shape[-1]), x.shape[0], temperature, top_k, top_p)
-    probs, _ = _filter(x, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, x.shape))
+    soft = as_soft(GRUConfig(vocab=x.shape[-1]), x.shape[0], soft)
+    probs, _ = _filter(x, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, x.shape), soft, emitted)
     return probs[0] if logits.dim() == 1 else probs
 
 
@@ -1254,11 +1440,12 @@ def _allowed_rows(allowed, shape) -> Optional[np.ndarray]:
 
 
 def sample_controlled(logits: torch.Tensor, r: torch.Tensor, temperature=1.0, top_k=0, top_p=1.0,
-                      controls: Optional[Controls] = None, allowed=None) -> torch.Tensor:
-    """Steps 2-7: logits [N, V], uniforms r [N] (and the rows' allowed sets, bool [N, V]) -> chosen index
-    [N] (int64)."""
+                      controls: Optional[Controls] = None, allowed=None, soft: Optional[Soft] = None,
+                      emitted: Optional[np.ndarray] = None) -> torch.Tensor:
+    """Steps 2-7: logits [N, V], uniforms r [N] (and the rows' allowed sets, bool [N, V]; their Soft object
+    and bytes so far, §4h) -> chosen index [N] (int64)."""
     c = controls or make_controls(GRUConfig(vocab=logits.shape[-1]), logits.shape[0], temperature, top_k, top_p)
-    probs, keep = _filter(logits, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, logits.shape))
+    probs, keep = _filter(logits, c.inv_temp, c.top_k, c.top_p, _allowed_rows(allowed, logits.shape), soft, emitted)
     V = probs.shape[-1]
     cs = torch.empty_like(probs)
     acc = torch.zeros_like(probs[..., 0])
@@ -1273,7 +1460,8 @@ def sample_controlled(logits: torch.Tensor, r: torch.Tensor, temperature=1.0, to
 
 def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0,
              count: Optional[int] = None, temperature=None, top_k=None, top_p=None, prefix=None,
-             constraints=None) -> np.ndarray:
+             constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None,
+             soft=None) -> np.ndarray:
     """Batched version of the reference's per-name loop (namegensf.cu:649-884).
 
     Names ``start .. start+count-1`` of the global job; name n at step l consumes
@@ -1286,14 +1474,17 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
     generated name, i.e. ``count`` entries): any that is not None takes the controlled sampler above
     (neutral values give the plain path's bytes).  ``constraints``: a Constraints object for the ``count``
     names or a dict of ``make_constraints`` keywords; it takes the controlled sampler too, inside each
-    step's allowed set (a table of only line 0 gives the unconstrained bytes).  fp64 params give the
-    oracle."""
+    step's allowed set (a table of only line 0 gives the unconstrained bytes).  ``logit_bias`` /
+    ``presence_penalty`` / ``frequency_penalty`` (``make_soft``'s arguments) or ``soft`` (its result for the
+    ``count`` names): the soft controls of docs/DESIGN.md §4h; any that is not None takes the controlled
+    sampler (neutral values give the bytes without them).  fp64 params give the oracle."""
     ML = cfg.max_len
     N = (rfloats.size // ML - start) if count is None else count
     out = np.zeros((N, ML + 1), dtype=np.uint8)
     ctl = None
     cons = as_constraints(cfg, max(N, 0), constraints)
-    if cons is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+    soft = as_soft(cfg, max(N, 0), soft, logit_bias, presence_penalty, frequency_penalty)
+    if cons is not None or soft is not None or any(v is not None for v in (temperature, top_k, top_p, prefix)):
         ctl = make_controls(cfg, max(N, 0), temperature, top_k, top_p, prefix)
         check_prefix_allowed(cons, ctl.prefix, ctl.plen)
     if N <= 0:
@@ -1322,7 +1513,8 @@ def generate(params: Params, cfg: GRUConfig, rfloats: np.ndarray, start: int = 0
             sel = sample_inverse_cdf(prob, rf[:, l].to(prob.dtype))
         else:
             allowed = None if cons is None else (alines[astate] if aut is not None else cons.allowed(l))
-            sel = sample_controlled(logits, rf[:, l], controls=ctl, allowed=allowed)
+            # (§4h: the counts are those of the output row's bytes, as the device reads them)
+            sel = sample_controlled(logits, rf[:, l], controls=ctl, allowed=allowed, soft=soft, emitted=out[:, :l])
             forced = torch.from_numpy(ctl.plen > l)
             sel = torch.where(forced, torch.from_numpy(ctl.prefix[:, l].astype(np.int64)), sel)
             if aut is not None:   # every step, a forced one and a finished row's included (nxt[q][eos] = 0)
