@@ -28,7 +28,8 @@ KERNELS = ["kernels/gru_step.hip", "kernels/gru_seq.hip", "kernels/fc.hip", "ker
            "kernels/gemm_lds.hip", "kernels/gemm_small.hip", "kernels/gru_step_lds.hip", "kernels/misc.hip",
            "kernels/gen_f32.hip", "kernels/gemm256.hip", "kernels/gen_persist.hip", "kernels/gru_seq_big.hip",
            "kernels/gru_seq16.hip", "kernels/onehot.hip", "kernels/score.hip", "kernels/gen_ctl.hip",
-           "kernels/gen_persist_ctl.hip", "kernels/beam.hip", "kernels/score_ctl.hip", "kernels/gen_persist_con.hip"]
+           "kernels/gen_persist_ctl.hip", "kernels/beam.hip", "kernels/score_ctl.hip", "kernels/gen_persist_con.hip",
+           "kernels/gen_persist_soft.hip"]
 ENGINE = ["runtime/blaslt.cpp", "engine/trainer.cpp", "engine/trainer_seq.cpp", "engine/generator.cpp", "comm/rccl_comm.cpp",
           "comm/watchdog.cpp", "comm/bootstrap.cpp", "data/name_loader.cpp"]
 PYBIND = ["bindings.cpp"]

@@ -288,6 +288,10 @@ def cmd_generate(args) -> int:
         if args.persist_constraints < 0:
             raise SystemExit("--persist-constraints needs a count >= 0")
         ctl["persist_constraints"] = args.persist_constraints
+    if args.persist_soft is not None:
+        if args.persist_soft < 0:
+            raise SystemExit("--persist-soft needs a count >= 0")
+        ctl["persist_soft"] = args.persist_soft
     ctx = None
     if args.cpu:
         from .parallel.dist import DistCtx
@@ -568,6 +572,10 @@ def main(argv=None) -> int:
     g.add_argument("--persist-constraints", dest="persist_constraints", type=int, nargs="?", const=64, default=None,
                    metavar="N", help="constrained batches of up to N names (bare flag: 64) run as one constrained "
                                      "persistent launch instead of the per-char graph (opt-in; docs/DESIGN.md §4e)")
+    g.add_argument("--persist-soft", dest="persist_soft", type=int, nargs="?", const=64, default=None,
+                   metavar="N", help="soft batches (--logit-bias / --presence-penalty / --frequency-penalty) of up "
+                                     "to N names (bare flag: 64) run as one soft persistent launch instead of the "
+                                     "per-char graph (opt-in; docs/DESIGN.md §4h)")
     g.add_argument("--exclude-emitted", dest="exclude_emitted", action="store_true",
                    help="distinct names: every batch's names are excluded from the later batches")
     g.add_argument("--emit-batch", dest="emit_batch", type=int, default=256,

@@ -277,6 +277,9 @@ PYBIND11_MODULE(_C, m) {
       .def("uses_persist_con", &Generator::uses_persist_con)
       .def("set_persist_con_max", &Generator::set_persist_con_max)
       .def("persist_con_launches", &Generator::persist_con_launches)
+      .def("uses_persist_soft", &Generator::uses_persist_soft)
+      .def("set_persist_soft_max", &Generator::set_persist_soft_max)
+      .def("persist_soft_launches", &Generator::persist_soft_launches)
       .def("set_global_names", &Generator::set_global_names)
       .def("inject_persist_error", &Generator::inject_persist_error)
       .def("dump_graph", &Generator::dump_graph);
@@ -807,6 +810,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("gen_persist_supported", &gen_persist_supported);
   m.def("gen_persist_ctl_supported", &gen_persist_ctl_supported);
   m.def("gen_persist_con_supported", &gen_persist_con_supported);
+  m.def("gen_persist_soft_supported", &gen_persist_soft_supported);
   m.def("gen_persist_con_bytes", []() { return (long)sizeof(GenPersistCon); });
   m.def("gen_persist_ws_floats", &gen_persist_ws_floats);
   m.def("gen_persist_sync_words", &gen_persist_sync_words);
@@ -840,12 +844,18 @@ PYBIND11_MODULE(_C, m) {
     h.allow_tab = GP(const unsigned, d, "allow_tab"); h.allow_idx = GP(const int, d, "allow_idx");
     h.allow_next = GP(const unsigned short, d, "allow_next"); h.allow_start = GP(const int, d, "allow_start");
     h.allow_state = GP(int, d, "allow_state"); h.allow_rows = get<int>(d, "allow_rows", 0);
+    // soft controls (SampleCtlArgs' five keys; gen_persist_soft_check throws on an inconsistent set): further
+    // fields of the same struct
+    h.soft_tab = GP(const float, d, "soft_tab"); h.soft_idx = GP(const int, d, "soft_idx");
+    h.soft_rows = get<int>(d, "soft_rows", 0);
+    h.soft_pres = GP(const float, d, "soft_pres"); h.soft_freq = GP(const float, d, "soft_freq");
     a.con_mode = gen_persist_con_mode(h);
-    if (a.con_mode != kGenConNone) {
+    a.soft = gen_persist_soft_check(h) ? 1 : 0;
+    if (a.con_mode != kGenConNone || a.soft) {
       GenPersistCon* dev = GP(GenPersistCon, d, "con");
-      if (!dev) throw std::runtime_error("gen_persist: a constrained launch needs `con`, gen_persist_con_bytes() of device memory");
+      if (!dev) throw std::runtime_error("gen_persist: a constrained or soft launch needs `con`, gen_persist_con_bytes() of device memory");
       if (!a.inv_temp || !a.top_k || !a.top_p || !a.plen || !a.prefix)
-        throw std::runtime_error("gen_persist: constraints go with the five sampling controls");
+        throw std::runtime_error("gen_persist: constraints and soft controls go with the five sampling controls");
       gen_persist_con_store(dev, h, S(s));
       a.con = dev;
     }

@@ -63,6 +63,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   if (gp && gp[0] == '0') persist_ = false;
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CTL_MAX")) persist_ctl_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CON_MAX")) persist_con_max_ = std::atoi(cm);
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_SOFT_MAX")) persist_soft_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -85,6 +86,14 @@ bool Generator::uses_persist_con(int n, bool automaton) const {
   // opt-in (persist_con_max_ = 0 by default): docs/DESIGN.md §4e has the reason
   return uses_persist_ctl(n) && n <= persist_con_max_ &&
          gen_persist_con_supported(d_.H, d_.L, d_.V, n, d_.max_len, automaton ? kGenConAuto : kGenConMask);
+}
+
+bool Generator::uses_persist_soft(int n, int con_mode) const {
+  // opt-in (persist_soft_max_ = 0 by default): docs/DESIGN.md §4h has the measurement
+  if (con_mode != kGenConNone && con_mode != kGenConMask && con_mode != kGenConAuto) return false;
+  if (!uses_persist_ctl(n) || n > persist_soft_max_) return false;
+  if (con_mode != kGenConNone && !uses_persist_con(n, con_mode == kGenConAuto)) return false;
+  return gen_persist_soft_supported(d_.H, d_.L, d_.V, n, d_.max_len, con_mode);
 }
 
 Generator::~Generator() {
@@ -315,11 +324,14 @@ bool Generator::persist_launch(const float* rf, int n, const Ctl* c, unsigned ch
   a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_; a.probs = probe_;
   a.rf = rf; a.out = out;
   if (c) { a.inv_temp = c->inv_temp; a.top_k = c->top_k; a.top_p = c->top_p; a.plen = c->plen; a.prefix = c->prefix; }
-  if (c && c->allow_tab) {   // constrained: the device struct, stored in stream order ahead of the launch
+  if (c && (c->allow_tab || c->soft_tab)) {   // constrained or soft: the device struct, stored in stream order ahead of the launch
     GenPersistCon h;
     h.allow_tab = c->allow_tab; h.allow_idx = c->allow_idx; h.allow_next = c->allow_next; h.allow_start = c->allow_start;
     h.allow_rows = c->allow_rows;
+    h.soft_tab = c->soft_tab; h.soft_idx = c->soft_idx; h.soft_rows = c->soft_rows;
+    h.soft_pres = c->soft_pres; h.soft_freq = c->soft_freq;
     a.con_mode = gen_persist_con_mode(h);
+    a.soft = gen_persist_soft_check(h) ? 1 : 0;
     // (the first such launch allocates; the previous persistent launch has been waited for -- its error
     // read-back below -- so nothing on any stream still reads the struct)
     if (!pcon_) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pcon_), sizeof(GenPersistCon)));
@@ -344,7 +356,8 @@ bool Generator::persist_launch(const float* rf, int n, const Ctl* c, unsigned ch
     inject_ = false;
   }
   gen_persist_f32(a, s);
-  if (a.con) ++persist_con_launches_;
+  if (a.soft) ++persist_soft_launches_;
+  else if (a.con) ++persist_con_launches_;
   // small batch, latency-bound launch: check its error word now.  A spin timeout means the
   // workgroups were not co-resident (something else held CUs): the batch's output is garbage,
   // so say so, stop using the persistent path and regenerate the batch on the per-char graph.
@@ -474,12 +487,21 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
   if (N <= 0) return;
   const int ML = d_.max_len;
   const int sr = soft ? c.soft_rows : 0;
-  if (soft) soft_alloc();   // first soft call: allocates before the error word is cleared and anything is captured
-  // a batch that takes the constrained persistent launch reads the caller's tables in place: a call made
-  // of such batches alone stages nothing and allocates nothing
-  bool graph_batch = false;
-  for (int start = 0; start < N; start += Bmax_)
-    if (soft || !(masked && uses_persist_con(std::min(Bmax_, N - start), aut))) graph_batch = true;
+  const int cmode = aut ? kGenConAuto : masked ? kGenConMask : kGenConNone;
+  // a batch that takes the constrained or the soft persistent launch reads the caller's tables in place: a
+  // call made of such batches alone stages nothing and allocates nothing
+  auto persist_batch = [&](int n) {
+    if (soft) return uses_persist_soft(n, cmode);   // (opt-in: docs/DESIGN.md §4h)
+    return masked ? uses_persist_con(n, aut) : uses_persist_ctl(n);   // (a constrained batch where the caller opted in: §4e)
+  };
+  bool graph_batch = false, soft_graph_batch = false;
+  for (int start = 0; start < N; start += Bmax_) {
+    const bool pb = persist_batch(std::min(Bmax_, N - start));
+    if (soft ? !pb : !(masked && pb)) graph_batch = true;
+    if (soft && !pb) soft_graph_batch = true;
+  }
+  // first soft call with a batch for the graph: allocates before the error word is cleared and anything is captured
+  if (soft_graph_batch) soft_alloc();
   bool aut_staged = false;
   if (aut && graph_batch) {   // before the error word is cleared: growing the buffers synchronises
     ctl_alloc();
@@ -489,13 +511,14 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
   if (!err_clean_) HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   bool tab_staged = false;
-  if (soft)   // the bias lines once per call
+  bool soft_staged = false;
+  if (soft_graph_batch) {   // the bias lines once per call
     HIP_CHECK(hipMemcpyAsync(gsoft_.tab, c.soft_tab, (size_t)sr * d_.V * 4, hipMemcpyDeviceToDevice, s));
+    soft_staged = true;
+  }
   for (int start = 0; start < N; start += Bmax_) {
     const int n = std::min(Bmax_, N - start);
-    // (a constrained batch only where the caller opted in: uses_persist_con, docs/DESIGN.md §4e; a soft
-    // batch never: the persistent sampler has no soft terms, §4h)
-    if (!soft && (masked ? uses_persist_con(n, aut) : uses_persist_ctl(n))) {   // one launch on the caller's arrays at this batch's rows
+    if (persist_batch(n)) {   // one launch on the caller's arrays at this batch's rows
       Ctl b;
       b.inv_temp = c.inv_temp + start; b.top_k = c.top_k + start; b.top_p = c.top_p + start; b.plen = c.plen + start;
       b.prefix = c.prefix + (size_t)start * ML;
@@ -504,12 +527,21 @@ void Generator::generate_ctl(const float* rf, int N, const Ctl& c, unsigned char
         if (aut) b.allow_start = c.allow_start + start;
         else b.allow_idx = c.allow_idx + (size_t)start * ML;
       }
+      if (soft) {   // the bias table by pointer; lines and penalties at the batch's rows
+        b.soft_tab = c.soft_tab; b.soft_rows = sr;
+        b.soft_idx = c.soft_idx + start; b.soft_pres = c.soft_pres + start; b.soft_freq = c.soft_freq + start;
+      }
       if (persist_launch(rf + (size_t)start * ML, n, &b, out + (size_t)start * (ML + 1), start + n >= N, s)) continue;
     }
     ctl_alloc();   // first batch on this path: allocates (and synchronises) before anything is captured
     if (aut && !aut_staged) {   // (a constrained persistent launch hit its spin limit: the graph after all)
       automaton_stage(c.allow_tab, c.allow_next, c.allow_rows, s);
       aut_staged = true;
+    }
+    if (soft && !soft_staged) {   // (a soft persistent launch hit its spin limit: the soft graph after all)
+      soft_alloc();
+      HIP_CHECK(hipMemcpyAsync(gsoft_.tab, c.soft_tab, (size_t)sr * d_.V * 4, hipMemcpyDeviceToDevice, s));
+      soft_staged = true;
     }
     HIP_CHECK(hipMemcpyAsync(rf_, rf + (size_t)start * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
     // this batch's slice of every control array: the graph reads rows 0 .. n - 1 of the buffers

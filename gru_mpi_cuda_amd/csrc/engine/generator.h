@@ -73,9 +73,11 @@ class Generator {
   // A soft generate_ctl() / score() (c.soft_tab set) copies the bias table once per call and each batch's
   // soft_idx / soft_pres / soft_freq slice into buffers of their own -- plain allocations made by the first
   // soft call, so the arenas and the workspace sizes of calls without soft controls stay what they are.
-  // Every soft batch takes the controlled per-char graph (uses_persist_ctl / uses_persist_con are not
-  // consulted: the persistent sampler has no soft terms), in recordings of their own, kept in maps apart
-  // from the others': a call without soft controls never replays a soft recording, nor the reverse.
+  // A soft batch takes the controlled per-char graph, in recordings of their own, kept in maps apart
+  // from the others': a call without soft controls never replays a soft recording, nor the reverse --
+  // unless uses_persist_soft(n, mode) holds (opt-in, off by default): then ONE soft persistent launch on the
+  // caller's arrays, the bias table by pointer, soft_idx / soft_pres / soft_freq at the batch's rows, and a
+  // call made of such batches alone stages nothing, allocates nothing and records nothing.
   void generate_ctl(const float* rf, int N, const Ctl& c, unsigned char* out, hipStream_t s);
   int soft_graphs() const {   // soft recordings so far (generation and scoring)
     return (int)(csgraphs_.size() + asgraphs_.size() + scsgraphs_.size());
@@ -92,6 +94,13 @@ class Generator {
   bool uses_persist_con(int n, bool automaton) const;
   void set_persist_con_max(int n) { persist_con_max_ = n; }
   long persist_con_launches() const { return persist_con_launches_; }   // constrained persistent launches so far
+  // Soft generate_ctl() batches of n names run as one soft persistent launch: up to GK_GEN_PERSIST_SOFT_MAX /
+  // set_persist_soft_max(n) names -- 0 by default, the path is opt-in (docs/DESIGN.md §4h) -- where
+  // uses_persist_ctl(n) holds, for a constrained batch (con_mode = kGenConMask / kGenConAuto) uses_persist_con
+  // as well, and a soft variant of the mode exists (gen_persist_soft_supported: V = 256, max_len <= 64)
+  bool uses_persist_soft(int n, int con_mode) const;
+  void set_persist_soft_max(int n) { persist_soft_max_ = n; }
+  long persist_soft_launches() const { return persist_soft_launches_; }   // soft persistent launches so far
   // Teacher-forced scoring of N output rows (device [N][max_len+1], the generate() format): per token
   // log softmax(logits)[target] and the target's rank, per name their sum and the token count (all
   // device pointers: tok_logp / rank [N][max_len], name_logp / n_tok [N]).  Always the exact-fp32
@@ -214,6 +223,8 @@ class Generator {
   int persist_ctl_max_ = 64;    // ... with sampling controls (GK_GEN_PERSIST_CTL_MAX)
   int persist_con_max_ = 0;     // ... with constraints (GK_GEN_PERSIST_CON_MAX): opt-in
   long persist_con_launches_ = 0;
+  int persist_soft_max_ = 0;    // ... with soft controls (GK_GEN_PERSIST_SOFT_MAX): opt-in
+  long persist_soft_launches_ = 0;
   // the constrained launch's device struct (plain allocation, made by the first such launch).  Written
   // in stream order before its launch; every persistent launch ends with its error-word read-back, so
   // no earlier launch can still read it when the next one's store is queued

@@ -20,9 +20,11 @@
 // one belongs in the other (tests/test_sampling_ctl_gpu.py holds this one,
 // tests/test_gen_persist_ctl_gpu.py that).  A third copy scores rows under this distribution:
 // score_ctl_logprob_f32_kernel (score_ctl.hip, tests/test_score_ctl_gpu.py).
-// The soft terms below (SOFT) exist only in this copy and the scoring one: a soft batch always takes
-// the per-char graph, because the persistent launch has no registers left for a lane's bias and count
-// values and its cost there has not been measured (docs/DESIGN.md §4h).  ctl_sample_wave is unchanged.
+// The soft terms below (SOFT) have three copies: this one, the scoring one, and the persistent
+// generator's soft variants (SOFT in gen_persist_kernel.h, opt-in: docs/DESIGN.md §4h), which adjust the
+// logits just before ctl_sample_wave and count a name's history in LDS instead of its output row.
+// ctl_sample_wave itself is unchanged.  A change to v's formula or to what n[c] counts belongs in all
+// three (tests/test_soft_ctl_gpu.py holds this one, tests/test_gen_persist_soft_gpu.py that).
 //
 // Constraints (docs/DESIGN.md §4e, the MASK instantiations; the persistent copy's: MASKED, gen_sample_ctl.h): a row's
 // allowed chars at this step are one line of a bit table.  A lane's V/64 consecutive chars lie in one

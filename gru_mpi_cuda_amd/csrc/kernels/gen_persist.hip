@@ -53,9 +53,11 @@ void gen_persist_f32(const GenPersistArgs& a, hipStream_t s) {
   if (nctl != 0 && nctl != 5)
     throw std::runtime_error("gen_persist_f32: inv_temp, top_k, top_p, plen and prefix go together (all or none)");
   // constraints: a device struct and its mode, only with the controls (the constrained variants, gen_persist_con.hip)
-  if ((a.con != nullptr) != (a.con_mode != kGenConNone) || (a.con && nctl != 5) ||
+  // (soft: the struct holds soft controls too, or alone -- the soft variants, gen_persist_soft.hip)
+  if ((a.con != nullptr) != (a.con_mode != kGenConNone || a.soft != 0) || (a.con && nctl != 5) ||
       (a.con_mode != kGenConNone && a.con_mode != kGenConMask && a.con_mode != kGenConAuto))
-    throw std::runtime_error("gen_persist_f32: con and con_mode go together, with the five controls");
+    throw std::runtime_error("gen_persist_f32: con, con_mode and soft go together, with the five controls");
+  if (a.soft) { gen_persist_soft_launch(a, s); return; }
   if (a.con) { gen_persist_con_launch(a, s); return; }
   if (nctl == 5) { gen_persist_ctl_launch(a, s); return; }
 #define X(K, LL) \

@@ -65,11 +65,14 @@
 //     instance both live, the variants at the 256-VGPR cap spill.  The four scalar controls of the
 //     launch's names are read into LDS once; a forced step still waits for and reads its logits, then
 //     overrides the pick, so every wait, poll, publish and their order are the plain kernel's.
+//   * Soft controls (SOFT = true: gen_persist_soft.hip; docs/DESIGN.md §4h): logit bias, presence and
+//     frequency penalties applied to the logits in registers just before ctl_sample_wave, the counts
+//     taken from a per-name history of the emitted bytes in LDS.  V = 256 only.
 // Reference: the per-char loop of /root/reference/namegensf.cu:661-884, for all names at once.
 //
 // This header is the kernel; gen_persist.hip instantiates the plain variants and holds the host
-// side, gen_persist_ctl.hip instantiates the controlled ones and gen_persist_con.hip the constrained
-// ones (translation units of their own: the three compile side by side).
+// side, gen_persist_ctl.hip instantiates the controlled ones, gen_persist_con.hip the constrained ones
+// and gen_persist_soft.hip the soft ones (translation units of their own: the four compile side by side).
 #pragma once
 #include <stdexcept>
 #include "kernels.h"
@@ -309,6 +312,18 @@ DEV unsigned (*ctl_lds())[kNmax] {
     return nullptr;
   }
 }
+// the soft variants' history of each name's output bytes (a plain variant allocates nothing): the rows
+// themselves cannot be read back, since up to kDistN names every workgroup samples every name and only
+// workgroup 0 writes them.  One wave writes and reads a name's line, so no barrier protects it.
+template <bool SOFT>
+DEV unsigned (*soft_hist_lds())[kGenSoftML / 4] {
+  if constexpr (SOFT) {
+    __shared__ unsigned s[kNmax][kGenSoftML / 4];
+    return s;
+  } else {
+    return nullptr;
+  }
+}
 
 // CTL: sampling controls (a.inv_temp .. a.prefix set), with the sampler instance for PER = V / 64
 // values per lane only; plain variants (CTL = false, PER = 0) hold both instances.
@@ -318,10 +333,18 @@ DEV unsigned (*ctl_lds())[kNmax] {
 // what happens between "the logits are in registers" and the pick differs from CON = 0 (plus one LDS
 // word and one 2-byte load after it): every wait, poll, publish and their order are the plain kernel's.
 // The fields of *a.con are read where they are used, never kept across the sampler.
+// SOFT (with CTL and any CON; gen_persist_soft.hip, docs/DESIGN.md §4h): the third copy of the soft rule
+// of sample_ctl_f32_kernel (gen_ctl.hip).  On a step that is not forced the logits in registers become
+// v = (x + bias) - pen before ctl_sample_wave scales them, the bias line and the penalties being the
+// name's, the counts those of its history in LDS up to the step before; lane 0 appends the pick's byte
+// (NUL once the name has ended) after it.  Three more rows of the LDS control block hold the name's line,
+// presence and frequency.  The same place as CON's change, and nothing else: every wait, poll, publish
+// and their order are the plain kernel's, and the bias and count registers are dead before the sampler.
 constexpr int kConNone = 0, kConMask = 1, kConAuto = 2;
-template <int KJ, int L, bool CTL = false, int PER_CTL = 0, int CON = kConNone>
+template <int KJ, int L, bool CTL = false, int PER_CTL = 0, int CON = kConNone, bool SOFT = false>
 __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
   static_assert(CON == kConNone || CTL, "a constrained variant is a controlled one");
+  static_assert(!SOFT || (CTL && PER_CTL == 4), "a soft variant is a controlled one with V = 256");
   constexpr int U = KJ / 8, H = 32 * KJ, KW = H / 8, NT = 2 * L - 1, R3 = 3 * U;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int fr = lane & 15, q4 = lane >> 4;
@@ -408,7 +431,9 @@ __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
     if (tid == 0 && ML < kStampT) sStamp[ML][14] = t_entry;   // (row ML has no layer phases)
   }
   if (tid < kNmax) { sid[tid] = a.sos; sal[tid] = tid < N ? 1 : 0; }
-  unsigned (*const sctl)[kNmax] = ctl_lds<CTL, (CON == kConAuto ? 5 : 4)>();
+  constexpr int kSoft0 = CON == kConAuto ? 5 : 4;   // SOFT: rows kSoft0 .. + 2 = the name's line, presence, frequency
+  unsigned (*const sctl)[kNmax] = ctl_lds<CTL, kSoft0 + (SOFT ? 3 : 0)>();
+  unsigned (*const shist)[kGenSoftML / 4] = soft_hist_lds<SOFT>();
   if constexpr (CTL) {   // once per launch: four dependent global loads per name and char otherwise
     if (tid < N) {
       sctl[0][tid] = __float_as_uint(a.inv_temp[tid]);
@@ -416,6 +441,22 @@ __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
       sctl[2][tid] = __float_as_uint(a.top_p[tid]);
       sctl[3][tid] = (unsigned)a.plen[tid];
       if constexpr (CON == kConAuto) sctl[4][tid] = (unsigned)a.con->allow_start[tid];
+      if constexpr (SOFT) {
+        // a line outside the table is flagged by the name's single writer and taken as line 0: no address
+        // is formed from it
+        int sr = a.con->soft_idx[tid];
+        if (sr < 0 || sr >= a.con->soft_rows) {
+          if (dist ? b == tid : b == 0) {
+            __hip_atomic_fetch_or(a.err, 16u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.err[1] = (unsigned)sr;
+            a.err[2] = (unsigned)tid;
+          }
+          sr = 0;
+        }
+        sctl[kSoft0][tid] = (unsigned)sr;
+        sctl[kSoft0 + 1][tid] = __float_as_uint(a.con->soft_pres[tid]);
+        sctl[kSoft0 + 2][tid] = __float_as_uint(a.con->soft_freq[tid]);
+      }
     }
   }
   if (dist ? b < N : b == 0)   // each output row has one writer: its sampler (every row: workgroup 0)
@@ -733,10 +774,60 @@ __global__ void __launch_bounds__(512, 1) gen_persist_kernel(GenPersistArgs a) {
           if (forced < 0)   // a forced step reads no mask
             ok = a.con->allow_tab[(size_t)line * (V >> 5) + ((lane * PER) >> 5)] >> ((lane * PER) & 31);
         }
+        // (scheduling barriers around the adjust: nothing of the sampler is hoisted into it and nothing of it
+        // sinks into the sampler, so its registers are dead where the sampler's go live -- without them the
+        // masked variant at the 256-VGPR cap, H = 1024 and L = 2, spills 12 bytes per lane)
+        if constexpr (SOFT) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (SOFT) {
+          if (forced < 0) {   // a forced step reads none of it
+#pragma clang fp contract(off)
+            // v = (x + bias) - pen, pen = frequency * n (+ presence if n > 0): three fp32 roundings in this
+            // order, in x's place before the sampler's temperature scale.  n[c] counts byte c among the
+            // name's history 0 .. t-2, a word of four bytes per uniform LDS load; with both penalties 0
+            // every pen is +0 whatever the counts are.  cnt[] and the bias values die here.
+            const float pres = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[kSoft0 + 1][n]));
+            const float freq = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[kSoft0 + 2][n]));
+            int cnt[PER];
+#pragma unroll
+            for (int e = 0; e < PER; ++e) cnt[e] = 0;
+            if (pres != 0.f || freq != 0.f) {
+              const int c0 = lane_now() * PER;
+              for (int j = 0; j < t - 1; j += 4) {
+                const unsigned wd = (unsigned)__builtin_amdgcn_readfirstlane((int)shist[n][j >> 2]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                  const int ch = j + k < t - 1 ? (int)((wd >> (8 * k)) & 255u) : -1;
+#pragma unroll
+                  for (int e = 0; e < PER; ++e) cnt[e] += (c0 + e == ch) ? 1 : 0;
+                }
+              }
+            }
+            // (the struct through a vector register, as the automaton's step below: no scalar pair held)
+            const GenPersistCon* cp = a.con;
+            asm volatile("" : "+v"(cp));
+            const int sr = __builtin_amdgcn_readfirstlane((int)sctl[kSoft0][n]);   // in range: checked at the start
+            const float* brow = cp->soft_tab + (size_t)sr * V + lane_now() * PER;
+            float bia[PER];
+#pragma unroll
+            for (int e = 0; e < PER; ++e) bia[e] = brow[e];
+#pragma unroll
+            for (int e = 0; e < PER; ++e) {
+              float pn = freq * (float)cnt[e];
+              if (cnt[e] > 0) pn = pn + pres;
+              xv[e] = (xv[e] + bia[e]) - pn;
+            }
+          }
+        }
+        if constexpr (SOFT) __builtin_amdgcn_sched_barrier(0);
         const float it = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[0][n]));
         const int tk = __builtin_amdgcn_readfirstlane((int)sctl[1][n]);
         const float tp = __uint_as_float(__builtin_amdgcn_readfirstlane(sctl[2][n]));
         const int sel = ctl_sample_wave<PER, CON != kConNone>(xv, V, rnd, prow, it, tk, tp, forced, ok);
+        if constexpr (SOFT) {
+          // the history's byte t-1: what the name's output row holds there (sal[n] is still the state
+          // before this pick, so the EOS byte is counted and every later step appends NUL)
+          if (lane == 0) reinterpret_cast<unsigned char*>(shist[n])[t - 1] = sal[n] ? (unsigned char)sel : (unsigned char)0;
+        }
         if constexpr (CON == kConAuto) {
           // after every pick, a forced one included: state <- next[state][sel], the state re-read from LDS
           // (in range: checked above) instead of held across the sampler; 0 <= sel < V on every branch

@@ -5,9 +5,10 @@
 // It is the rule of sample_ctl_f32_kernel (gen_ctl.hip), which stays the per-char graph's sampler: the
 // two copies sit side by side, and a change to the kept-set rule of one belongs in the other (and in the
 // scorer's copy of it, score_ctl_logprob_f32_kernel in score_ctl.hip).  The soft terms (logit bias,
-// presence and frequency penalties, docs/DESIGN.md §4h) exist only in those two: a soft batch always
-// takes the per-char graph, because this copy has no registers left for a lane's bias and count values
-// and their cost inside the persistent launch has not been measured.  This one is written for a
+// presence and frequency penalties, docs/DESIGN.md §4h) are not in this function: they replace the logits
+// before the temperature scale, so the persistent generator's soft variants (SOFT in gen_persist_kernel.h,
+// the third copy of that rule) adjust y[] just before the call, where a lane's bias and count values are
+// dead again before this function's own registers go live.  This one is written for a
 // kernel whose weights fill the register file: it keeps only y[PER] live (plus q[PER] during the top-p
 // search) where gen_ctl.hip keeps key[] / ex[] / keep[] as well.  A filtered entry is marked by
 // y = -inf, so its expf(y - mx) is exactly the 0 that gen_ctl.hip selects, and every expf / key is

@@ -477,6 +477,14 @@ void gen_reset(const GenResetArgs& a, hipStream_t s);
 // allow_next[state][char], and the nullable allow_state[n] receives each new state, so after the launch
 // it holds the end of the walk over the chars the launch ran.  A forced step reads no mask.  The
 // workspace, `sync` and every hand-off are the controlled launch's.
+// Soft controls (docs/DESIGN.md §4h; soft = 1, with the five controls, V = 256 and ML <= kGenSoftML, with or
+// without a constraint): the soft variants (gen_persist_soft.hip) apply sample_ctl_f32's SOFT rule inside
+// the launch.  The four soft arrays and soft_rows are further fields of the same device struct, at this
+// launch's rows (gen_persist_soft_check checks a host copy).  n[c] counts the bytes of the name's output
+// row before the step -- the sampled or forced chars while the name is alive, its EOS byte included, and
+// NUL for every step after its end -- kept in LDS, since only workgroup 0 writes the rows of a batch of
+// up to 16 names.  A line index outside [0, soft_rows) ORs 16 into err[0] (err[1] = the value, err[2] =
+// the name) and is taken as line 0.  A forced step reads none of it.
 struct GenPersistCon {
   const unsigned* allow_tab = nullptr;           // [allow_rows][V / 32]
   const int* allow_idx = nullptr;                // [N][ML]   (per-position)
@@ -484,8 +492,14 @@ struct GenPersistCon {
   const int* allow_start = nullptr;              // [N]   (automaton)
   int* allow_state = nullptr;                    // nullable [N]   (automaton): written only
   int allow_rows = 0;
+  int soft_rows = 0;
+  const float* soft_tab = nullptr;               // [soft_rows][V]   (soft: all four, or none)
+  const int* soft_idx = nullptr;                 // [N]
+  const float* soft_pres = nullptr;              // [N]
+  const float* soft_freq = nullptr;              // [N]
 };
 constexpr int kGenConNone = 0, kGenConMask = 1, kGenConAuto = 2;
+constexpr int kGenSoftML = 64;   // chars of a name's history in the soft variants' LDS
 struct GenPersistArgs {
   const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
   const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
@@ -508,6 +522,7 @@ struct GenPersistArgs {
   const unsigned char* prefix = nullptr;   // [N][ML]
   const GenPersistCon* con = nullptr;      // nullable, DEVICE memory: the launch's constraint (gen_persist_con_store)
   int con_mode = kGenConNone;              // what *con holds
+  int soft = 0;                            // 1: *con holds soft controls too (the host's dispatch; no kernel reads it)
 };
 // the rule a field set asks for, by SampleCtlArgs' rules (throws on an inconsistent one: allow_tab with
 // exactly one of allow_idx / allow_next; allow_next and allow_start together, never with allow_idx;
@@ -520,6 +535,14 @@ void gen_persist_con_store(GenPersistCon* dev, const GenPersistCon& h, hipStream
 // SIMD: gen_persist_con.hip); false: the per-char constrained graph is the path
 bool gen_persist_con_supported(int H, int L, int V, int N, int ML, int mode);
 void gen_persist_con_launch(const GenPersistArgs& a, hipStream_t s);   // (gen_persist_f32 dispatches here)
+// true: h holds soft controls (throws unless soft_tab, soft_idx, soft_pres and soft_freq are set together,
+// with soft_rows >= 1)
+bool gen_persist_soft_check(const GenPersistCon& h);
+// ... and a soft variant of that constraint mode (kGenConNone included) exists for the shape: V = 256,
+// ML <= kGenSoftML, each with scratch 0 and two waves per SIMD (gen_persist_soft.hip); false: the per-char
+// soft graph is the path
+bool gen_persist_soft_supported(int H, int L, int V, int N, int ML, int con_mode);
+void gen_persist_soft_launch(const GenPersistArgs& a, hipStream_t s);   // (gen_persist_f32 dispatches here)
 bool gen_persist_supported(int H, int L, int V, int N, int ML);
 // ... and a controlled variant exists for the shape (each has scratch 0 and two waves per SIMD:
 // gen_persist_ctl.hip); false: the per-char controlled graph is the path

@@ -45,11 +45,15 @@ class HipGenerator:
     "bf16": bf16 MFMA fast mode (fused step kernels, bf16 weight copies).
     Small batches run the exact fp32 persistent kernel in both fp32 modes.
     ``persist_constraints`` = N (opt-in, default 0; docs/DESIGN.md §4e): constrained batches of up to N
-    names (at most 64) run as one constrained persistent launch instead of the per-char graph."""
+    names (at most 64) run as one constrained persistent launch instead of the per-char graph.
+    ``persist_soft`` = N (opt-in, default 0; docs/DESIGN.md §4h): soft batches (``logit_bias`` /
+    ``presence_penalty`` / ``frequency_penalty``) of up to N names (at most 64) run as one soft persistent
+    launch instead of the per-char graph, where the shape has a variant (vocab 256, max_len <= 64); a soft
+    batch with constraints needs ``persist_constraints`` to cover it as well."""
 
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
-                 precision: str = "fp32", persist_constraints: int = 0):
+                 precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -74,6 +78,7 @@ class HipGenerator:
         self.g = self.C.Generator(dims, self.flat.data_ptr(), offsets)
         self.g.refresh_weights(self._s())
         self.set_persist_constraints(persist_constraints)
+        self.set_persist_soft(persist_soft)
 
     def set_persist_constraints(self, n: int) -> None:
         """Constrained batches of up to ``n`` names take the constrained persistent launch where the
@@ -82,6 +87,14 @@ class HipGenerator:
         if n < 0:
             raise ValueError(f"persist_constraints must be >= 0, got {n}")
         self.g.set_persist_con_max(n)
+
+    def set_persist_soft(self, n: int) -> None:
+        """Soft batches of up to ``n`` names take the soft persistent launch where the shape has one
+        (``g.uses_persist_soft``); 0 turns it off (the default)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"persist_soft must be >= 0, got {n}")
+        self.g.set_persist_soft_max(n)
 
     def _s(self) -> int:
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -136,8 +149,9 @@ class HipGenerator:
         ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty`` (cpu_ref.make_soft's arguments;
         docs/DESIGN.md §4h): soft preferences -- a per-char additive bias (a dict {chars: value}, V values, or
         one of those per name), a deduction for every char the name already holds and one per earlier
-        occurrence.  Any that is not None takes the controlled per-char graph, whatever the batch size, and
-        combines with every control and constraint above.  Bad values raise ValueError before anything
+        occurrence.  Any that is not None takes the controlled per-char graph, whatever the batch size -- or,
+        batches of up to ``persist_soft`` names, one soft persistent launch -- and combines with every control
+        and constraint above.  Bad values raise ValueError before anything
         is launched."""
         ML = self.cfg.max_len
         ctl = None
@@ -450,7 +464,7 @@ def _slice_constraints(cfg: GRUConfig, constraints, N: int, start: int, count: i
 
 def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperature=None, top_k=None, top_p=None,
             prefix=None, constraints=None, persist_constraints=None, logit_bias=None, presence_penalty=None,
-            frequency_penalty=None) -> None:
+            frequency_penalty=None, persist_soft=None) -> None:
     """namegensf.cu:627-890.  ``output`` (rank 0): uint8 [N*(MAX_LEN+1)] filled in place.
     ``temperature`` / ``top_k`` / ``top_p`` / ``prefix``: sampling controls (HipGenerator.generate_device),
     scalars or one value per name of the job; every rank takes its names' slice.  ``constraints``: a
@@ -458,7 +472,9 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
     (docs/DESIGN.md §4e, §4g: ``regex`` / ``exclude``), sliced by global name index like the prefixes.
     ``persist_constraints``: HipGenerator.set_persist_constraints for this and later calls (None: as it
     is); the CPU path ignores it.  ``logit_bias`` / ``presence_penalty`` / ``frequency_penalty``: the soft
-    controls (docs/DESIGN.md §4h), one value for every name or one per name of the job, sliced likewise."""
+    controls (docs/DESIGN.md §4h), one value for every name or one per name of the job, sliced likewise.
+    ``persist_soft``: HipGenerator.set_persist_soft for this and later calls (None: as it is); the CPU path
+    ignores it."""
     assert _S is not None, "call namegen_initialize first"
     cfg, ctx = _S.cfg, _S.ctx
     ML = cfg.max_len
@@ -476,6 +492,8 @@ def namegen(N: int, random_floats: np.ndarray, output: np.ndarray, *, temperatur
     if _S.gen is not None:
         if persist_constraints is not None:
             _S.gen.set_persist_constraints(persist_constraints)
+        if persist_soft is not None:
+            _S.gen.set_persist_soft(persist_soft)
         _S.gen.g.set_global_names(N)   # bf16 mode: the same arithmetic path at every world size
         mine = _S.gen.generate(random_floats, start, count, **ctl)
         if ctx.world > 1:
