@@ -7,6 +7,7 @@
     python -m gru_mpi_cuda_amd.cli score    --ckpt out/model.bin --names heldout.txt --temperature 0.8 --top-k 40 --pattern '[A-Z]'
     python -m gru_mpi_cuda_amd.cli beam     --ckpt out/model.bin --width 5 --prefix Mar
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 200 --regex '.*son' --exclude-file train.txt --exclude-emitted
+    python -m gru_mpi_cuda_amd.cli distinct --ckpt out/model.bin --width 20 --prefix Mar --seed 1
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
 
@@ -28,11 +29,13 @@ from typing import Optional
 import numpy as np
 
 
-def _add_model_args(ap: argparse.ArgumentParser) -> None:
+def _add_model_args(ap: argparse.ArgumentParser, skip=()) -> None:
     for name, typ in (("vocab", int), ("embed", int), ("hidden", int), ("layers", int), ("batch", int),
                       ("seq", int), ("lr", float), ("max_len", int), ("sos", int), ("eos", int),
                       ("clip_norm", float), ("seed", int), ("bucket_mb", float), ("time_chunks", int),
                       ("warmup_steps", int), ("total_steps", int), ("lr_min", float)):
+        if name in skip:
+            continue
         ap.add_argument("--" + name.replace("_", "-"), dest=name, type=typ, default=None)
     ap.add_argument("--optimizer", choices=["adam", "sgd"], default=None)
     ap.add_argument("--lr-sched", dest="lr_sched", choices=["const", "cosine", "linear"], default=None,
@@ -471,6 +474,45 @@ def cmd_beam(args) -> int:
     return 0
 
 
+def cmd_distinct(args) -> int:
+    """`width` distinct names per prefix, sampled without replacement in draw order with the model's
+    probabilities (stochastic beam search, docs/DESIGN.md §4i): one `prefix<TAB>draw<TAB>name<TAB>logq` line
+    per row (draw from 0, dead slots left out; logq: the name's log-probability under the sampler)."""
+    import torch
+    from .engine import generator as G
+    from .models import cpu_ref
+    from .utils import ckpt
+    fmt = args.fmt
+    if fmt == "auto":
+        fmt = "gen" if os.path.exists(args.ckpt + ".json") else "ref"
+    cfg, params = ckpt.load(args.ckpt, _cfg_from(args) if fmt == "ref" else None, fmt)
+    over = {k: getattr(args, k) for k in ("max_len", "sos", "eos") if getattr(args, k) is not None}
+    cfg = cfg.replace(**over)
+    if args.prefix is not None and args.prefix_file is not None:
+        raise SystemExit("--prefix and --prefix-file exclude each other")
+    if args.prefix_file:
+        prefixes = [b.decode("latin-1") for b in _read_names(args.prefix_file)]
+    else:
+        prefixes = [args.prefix or ""]
+    kw = dict(seed=args.noise_seed, temperature=args.temperature, constraints=_constraints_from(args))
+    if args.cpu or not torch.cuda.is_available():
+        res = cpu_ref.sample_distinct({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width, **kw)
+    else:
+        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)))
+        res = gen.sample_distinct(prefixes, args.width, **kw)
+    lines = []
+    for pre, names, lqs in zip(prefixes, res.names(), res.logq):
+        for k, nm in enumerate(names):
+            lines.append(f"{_escape(pre)}\t{k}\t{_escape(nm)}\t{float(lqs[k]):.6f}")
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    else:
+        sys.stdout.write(text)
+    return 0
+
+
 class _Evaluator:
     """Held-out evaluation for `train --eval-data`: the file is read once; every call scores the
     trainer's current weights on all of it (each rank the whole file: no collective of its own)."""
@@ -595,6 +637,20 @@ def main(argv=None) -> int:
     bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
     bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(bm)
+    ds = sub.add_parser("distinct", help="distinct names per prefix: sampling without replacement (stochastic beam search)")
+    ds.add_argument("--ckpt", required=True)
+    ds.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")
+    ds.add_argument("--width", type=int, default=4, help="distinct names per prefix, 1 .. min(32, vocab)")
+    ds.add_argument("--prefix", default=None, help="the names start with these chars (default: the empty prefix)")
+    ds.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
+    ds.add_argument("--temperature", type=float, default=None, help="softmax temperature, > 0 (default 1)")
+    _constraint_args(ds)
+    ds.add_argument("--out", default=None, help="prefix, draw, name and log-prob per line, tab-separated")
+    ds.add_argument("--cpu", action="store_true", help="cpu_ref.sample_distinct in fp32 instead of the HIP generator")
+    ds.add_argument("--seed", dest="noise_seed", type=int, default=0,
+                    help="the sampler's seed: the same seed gives the same names (default 0)")
+    ds.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
+    _add_model_args(ds, skip=("seed",))      # --seed is the sampler's here, not the config's
     sub.add_parser("info", help="device / build info")
     b = sub.add_parser("bench", help="run bench.py", add_help=False)
     args, rest = ap.parse_known_args(argv)
@@ -605,7 +661,8 @@ def main(argv=None) -> int:
         return bench.main()
     if rest:
         ap.error(f"unrecognized arguments: {rest}")
-    return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "beam": cmd_beam, "info": cmd_info}[args.cmd](args)
+    return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "beam": cmd_beam, "distinct": cmd_distinct,
+            "info": cmd_info}[args.cmd](args)
 
 
 if __name__ == "__main__":

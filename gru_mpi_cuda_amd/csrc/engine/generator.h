@@ -132,6 +132,21 @@ class Generator {
   void beam(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp, int* n_tok,
             int* n_beams, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
             int allow_rows = 0, const unsigned short* allow_next = nullptr, const int* allow_start = nullptr);
+  // Distinct names (docs/DESIGN.md §4i; the rule: cpu_ref.sample_distinct): for each of N prefixes W rows
+  // sampled without replacement, in draw order, from the distribution of inv_t (device [N], 1 / T), the
+  // prefix and the constraints -- stochastic beam search.  rows [N][W][max_len+1], logq [N][W] (the rows'
+  // log-probability under that distribution, -inf for a dead slot), gumbel [N][W] (the final perturbed
+  // values), n_tok [N][W], n_found [N], all device pointers.  Name n draws its noise at the global index
+  // start + n under seed.  It is beam()'s loop on beam()'s arena with sbs_select_f32 as the selection: the
+  // same batches of floor(max_batch / W) names, the batch's first global index written to a device word
+  // (the bytes do not depend on max_batch), recordings of its own per (names, W, constraint lines or
+  // states) that bake in no seed, index or temperature.  Two G buffers and the seed / start / inv_t
+  // staging are plain allocations made by the first call: no arena and no workspace size changes.
+  void distinct(const int* plen, const unsigned char* prefix, int N, int W, unsigned long long seed,
+                unsigned long long start, const float* inv_t, unsigned char* rows, float* logq, float* gumbel, int* n_tok,
+                int* n_found, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
+                int allow_rows = 0, const unsigned short* allow_next = nullptr, const int* allow_start = nullptr);
+  int distinct_graphs() const { return (int)(dgraphs_.size() + adgraphs_.size()); }   // recordings so far
   size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
@@ -186,7 +201,9 @@ class Generator {
   void soft_alloc();
   void score_ctl_alloc();
   void beam_alloc();
-  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false);
+  // distinct: sbs_select_f32 as the selection (G by step parity, step 0 reads the reset scores as G)
+  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false, bool distinct = false);
+  void distinct_alloc();
   // the automaton buffers for `states` states (grown, never shrunk) and the call's tables into them
   void automaton_stage(const unsigned* tab, const unsigned short* next, int states, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
@@ -282,6 +299,12 @@ class Generator {
   unsigned char* bprefix_ = nullptr;            // [Bmax][ML]
   unsigned* btab_ = nullptr;                    // [kAllowRows][V / 32] the call's constraint table
   int* bidx_ = nullptr;                         // [Bmax][ML] the current batch's lines
+  // distinct names (plain allocations, made by the first distinct() call)
+  float* dG_[2] = {nullptr, nullptr};           // [Bmax] x2 the slots' perturbed values, by step parity
+  float* dinv_ = nullptr;                       // [Bmax] the current batch's 1 / T
+  unsigned long long* dwords_ = nullptr;        // [2] the call's seed, the current batch's first global index
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> dgraphs_;    // keyed by (names, W, table lines or 0)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> adgraphs_;   // keyed by (names, W, states)
   // automaton constraints (plain allocations, made by the first automaton call and grown on demand)
   unsigned* atab_ = nullptr;                    // [acap_][V / 32] the call's state sets
   unsigned short* anxt_ = nullptr;              // [acap_][V] the call's successor table

@@ -653,6 +653,44 @@ struct BeamSelectArgs {
   const unsigned short* allow_next = nullptr;    // nullable [allow_rows][V]
 };
 void beam_select_f32(const BeamSelectArgs& a, hipStream_t s);
+// sbs_select_f32 (sbs.hip, docs/DESIGN.md §4i; the rule: cpu_ref.sbs_step): the selection of a stochastic
+// beam search step, one workgroup per name, beam_select_f32's geometry, states, constraints and error
+// word.  A slot carries logq (its row's log-probability under the sampler) and G (its perturbed value).
+// Per live slot b: y = x * inv_t[n], lq = the log-softmax of y over the allowed set, on a forced step the
+// one child prefix[step] with lq = 0; child j = b V + c gets gum = -log(-log u) from word j & 3 of
+// Philox-4x32-10(key = *seed, counter = (j >> 2, step, *start + n)), u = (2 (word >> 9) + 1) 2^-24;
+// psi = logq_b + lq[c], g = psi + gum, Z = the offered children's max, Gt = G_b truncated (sbs.hip).  A
+// finished slot offers its carry j = b V with Gt = G_b.  The first W candidates in the order "Gt
+// descending, then j ascending" become the new slots: logq_out = psi (a carry: logq_in), G_out = Gt.
+struct SbsSelectArgs {
+  const float* logits = nullptr;   // [>= N W][V], row n W + b
+  int splits = 1; long slab = 0;   // split-K slabs of the logits, summed in fixed order
+  const float* bias = nullptr;     // nullable: added after the slab sum
+  const float* logq_in = nullptr; const float* G_in = nullptr; const int* state_in = nullptr;   // [N W]
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][max_len]
+  const unsigned long long* seed = nullptr;    // one word: the Philox key
+  const unsigned long long* start = nullptr;   // one word: the global index of name 0 of this launch
+  const float* inv_t = nullptr;            // [N] 1 / temperature
+  float* logq_out = nullptr; float* G_out = nullptr; int* parent = nullptr; int* chr = nullptr;   // [N W],
+  int* state_out = nullptr; int* next_id = nullptr;                                               // never the inputs
+  float* lq = nullptr;             // nullable [N W][V]: every row's sampler log-probabilities, NaN outside the set (tests)
+  float* gt = nullptr;             // nullable [N W][V]: Gt, NaN where not offered (tests)
+  float* zmax = nullptr;           // nullable [N W]: Z, NaN for a row that offers no child (tests)
+  int* sel = nullptr;              // nullable [N W]: the winners' flat indices j, -1 for a dead slot (tests)
+  unsigned* err = nullptr;         // nullable
+  int N = 0, W = 0, V = 0, step = 0, max_len = 0, sos = 0, eos = 0;   // V % 64 == 0, V <= 512, W <= min(32, V)
+  const unsigned* allow_tab = nullptr;     // as BeamSelectArgs' seven
+  const int* allow_idx = nullptr;
+  int allow_rows = 0;
+  const int* allow_state_in = nullptr;
+  int* allow_state_out = nullptr;
+  const unsigned short* allow_next = nullptr;
+};
+void sbs_select_f32(const SbsSelectArgs& a, hipStream_t s);
+// *seed = seed_v, *start = start_v as one kernel node on the stream (the values travel as kernel arguments)
+void sbs_stage(unsigned long long* seed, unsigned long long seed_v, unsigned long long* start, unsigned long long start_v,
+               hipStream_t s);
 // The winners' state moved into the next step's slots: per layer h_dst[n W + k] = h_src[n W + parent[k]]
 // (zeros for a dead beam), rows_dst likewise with chr appended at the parent's length (len_src ->
 // len_dst), ids = next_id, n_beams[n] = the beams that are not dead.  A gather is never in place: source

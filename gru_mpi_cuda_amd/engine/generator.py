@@ -300,7 +300,50 @@ class HipGenerator:
         return BeamResult(rows.cpu().numpy(), logp.cpu().numpy(), nt.cpu().numpy(), nb.cpu().numpy(), self.cfg.eos)
 
 
+    def sample_distinct(self, prefix=None, width: int = 4, count: Optional[int] = None, *, seed: int = 0, start: int = 0,
+                        temperature=None, constraints=None, **excluded) -> "DistinctResult":
+        """``width`` distinct output rows per prefix, an exact sample without replacement in draw order from
+        the distribution ``generate`` samples from with the same ``temperature`` / ``prefix`` / ``constraints``
+        -- stochastic beam search (the rule: cpu_ref.sample_distinct, docs/DESIGN.md §4i).  ``logq`` is what
+        ``score(rows, temperature=, prefix=, constraints=).name_logp`` returns for the rows; ``gumbel`` the
+        final perturbed values.  Name n of the call draws its noise at the global index ``start + n`` under
+        ``seed``, so the result does not depend on how a job is cut into calls or batches.  Always exact fp32
+        arithmetic; precision "bf16" is refused (ValueError), as are top_k, top_p, temperature 0 and the soft
+        controls, before anything is launched."""
+        if self.precision == "bf16":
+            raise ValueError('sample_distinct needs precision "fp32" or "bf16x3" (it runs exact fp32; the bf16 mode '
+                             "samples from another distribution)")
+        pre, plen, inv, seed, start = cpu_ref.distinct_inputs(self.cfg, prefix, width, count, seed, start, temperature,
+                                                              **excluded)
+        N, W, ML = pre.shape[0], int(width), self.cfg.max_len
+        cons = cpu_ref.as_constraints(self.cfg, N, constraints)
+        cpu_ref.check_prefix_allowed(cons, pre, plen)
+        if N == 0:
+            return DistinctResult(np.zeros((0, W, ML + 1), np.uint8), np.zeros((0, W), np.float32),
+                                  np.zeros((0, W), np.float32), np.zeros((0, W), np.int32), np.zeros(0, np.int32),
+                                  self.cfg.eos)
+        p, l = torch.from_numpy(pre).to(self.dev), torch.from_numpy(plen).to(self.dev)
+        it = torch.from_numpy(inv).to(self.dev)
+        rows = torch.empty(N, W, ML + 1, dtype=torch.uint8, device=self.dev)
+        logq = torch.empty(N, W, dtype=torch.float32, device=self.dev)
+        gum = torch.empty(N, W, dtype=torch.float32, device=self.dev)
+        nt = torch.empty(N, W, dtype=torch.int32, device=self.dev)
+        nf = torch.empty(N, dtype=torch.int32, device=self.dev)
+        extra = ()
+        if cons is not None:
+            held = self._constraint_tensors(cons)
+            extra = self._constraint_args(held)
+        self.g.distinct(l.data_ptr(), p.data_ptr(), N, W, seed, start, it.data_ptr(), rows.data_ptr(), logq.data_ptr(),
+                        gum.data_ptr(), nt.data_ptr(), nf.data_ptr(), self._s(), *extra)
+        err = self.g.read_error()   # synchronises: the input tensors stay alive until the call is done
+        if err:
+            raise RuntimeError(f"HipGenerator.sample_distinct: device error word {err}")
+        return DistinctResult(rows.cpu().numpy(), logq.cpu().numpy(), gum.cpu().numpy(), nt.cpu().numpy(),
+                              nf.cpu().numpy(), self.cfg.eos)
+
+
 BeamResult = cpu_ref.BeamResult
+DistinctResult = cpu_ref.DistinctResult
 
 
 @dataclass

@@ -1699,3 +1699,281 @@ def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.n
             astate = nastate
         cur = torch.from_numpy(nxt)
     return BeamResult(rows, score, ntok, (state != BEAM_DEAD).sum(1).astype(np.int32), cfg.eos)
+
+
+# --------------------------------------------------------------------------- distinct names
+# Sampling without replacement by stochastic beam search (docs/DESIGN.md §4i; Kool, van Hoof and Welling,
+# 2019): the beam loop above, ranked by Gumbel-perturbed log-probabilities.  Per name W ordered slots (live /
+# finished / dead as above), each with logq -- the log-probability of its row so far under the SAMPLER's
+# distribution (temperature, constraint sets renormalised, forced chars 0: what ``score`` returns with the
+# same keywords) -- and G, its perturbed value.  Slot 0 starts live with logq = G = 0.  Per step l:
+#   1. every row takes the model's step;
+#   2. per live slot b: y = x * inv_T, A = the allowed set, lq[c] = (y[c] - max_A y) - log sum_A exp(y - max_A y);
+#      on a forced step the only child is prefix[l] with lq = 0;
+#   3. candidate j = b V + c of the name with global index g = start + n gets the 32-bit word j & 3 of
+#      Philox-4x32-10(key = seed, counter = (j >> 2, l, g)); u = (2 (word >> 9) + 1) 2^-24, gum = -log(-log u);
+#   4. psi = logq_b + lq[c], g = psi + gum, Z = max over the offered c; with d = g - Z
+#         v  = (G_b - g) + log1mexp(d)
+#         Gt = (G_b - max(0, v)) - log1p(exp(-|v|))
+#      i.e. Gt = -log(e^-G_b - e^-Z + e^-g): the children's maximum is moved onto G_b.  A finished slot offers
+#      its carry j = b V with Gt = G_b and logq unchanged, a dead slot nothing;
+#   5. the first W candidates in the order "Gt descending, then j ascending" are the new slots, in that order.
+# The W rows at the end are an exact sample without replacement, in draw order, from the distribution
+# ``generate`` samples from with the same temperature / prefix / constraints.
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(ctr: np.ndarray, key: np.ndarray) -> np.ndarray:
+    """Philox-4x32-10 (Salmon et al., Random123): ctr [..., 4], key [..., 2] (uint32 values) -> uint32 [..., 4]."""
+    c = [np.asarray(ctr)[..., i].astype(np.uint64) for i in range(4)]
+    k = [np.asarray(key)[..., i].astype(np.uint64) for i in range(2)]
+    for _ in range(10):
+        p0, p1 = _PHILOX_M0 * c[0], _PHILOX_M1 * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _U32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _U32]
+        k = [(k[0] + _PHILOX_W0) & _U32, (k[1] + _PHILOX_W1) & _U32]
+    return np.stack(c, -1).astype(np.uint32)
+
+
+def sbs_uniform(seed: int, g: np.ndarray, step: int, W: int, V: int) -> np.ndarray:
+    """Step 3's u, float32 [len(g), W, V] (exact, inside [2^-24, 1 - 2^-24]) for the names with global
+    indices ``g`` at ``step``."""
+    g = np.asarray(g, dtype=np.uint64).reshape(-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    nb = (W * V + 3) // 4
+    ctr = np.zeros((g.shape[0], nb, 4), np.uint64)
+    ctr[:, :, 0] = np.arange(nb, dtype=np.uint64)[None, :]
+    ctr[:, :, 1] = np.uint64(int(step) & 0xFFFFFFFF)
+    ctr[:, :, 2] = (g & _U32)[:, None]
+    ctr[:, :, 3] = (g >> np.uint64(32))[:, None]
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
+    words = philox4x32(ctr, key).reshape(g.shape[0], nb * 4)[:, :W * V]
+    u = (2.0 * (words >> np.uint32(9)).astype(np.float64) + 1.0) * 2.0 ** -24
+    return u.astype(np.float32).reshape(g.shape[0], W, V)
+
+
+def _rounded(f, a: np.ndarray) -> np.ndarray:
+    """f(a) in a's dtype; float32: evaluated in float64 and rounded once, as a correctly rounded expf /
+    logf would (the device's are within an ulp or two of that)."""
+    if a.dtype == np.float32:
+        return f(a.astype(np.float64)).astype(np.float32)
+    return f(a)
+
+
+def _wave_sum(e: np.ndarray) -> np.ndarray:
+    """The sum over the last axis (V entries) in e's dtype, in the device's order when V is a multiple of
+    64: a lane adds its V / 64 consecutive entries in index order, then the 64 lane sums are added as a
+    balanced tree of neighbours (pairs, quads, eights, the 16-lane rows, two rows, the wave)."""
+    V = e.shape[-1]
+    if V % 64:
+        return e.sum(-1, keepdims=True)
+    t = e.reshape(e.shape[:-1] + (64, V // 64))
+    acc = t[..., 0]
+    for k in range(1, V // 64):
+        acc = acc + t[..., k]
+    while acc.shape[-1] > 1:
+        acc = acc[..., 0::2] + acc[..., 1::2]
+    return acc
+
+
+def sbs_step(x: np.ndarray, logq: np.ndarray, G: np.ndarray, state: np.ndarray, forced: np.ndarray, allowed,
+             inv_t: np.ndarray, u: np.ndarray, eos: int, sos: int, mut: Optional[str] = None) -> Dict[str, np.ndarray]:
+    """Steps 2-5 for N names at once, in the dtype of ``x`` (float32: the device's operations in its order,
+    the row sum included, each rounded once; expf / logf / log1pf / expm1f as correctly rounded functions,
+    which the device's are not, so this emulates the kernel, it does not reproduce its bits).  x [N, W, V] logits, logq / G / state [N, W], forced [N] (the forced char, -1 on
+    a free step), allowed None / bool [N, V] / bool [N, W, V], inv_t [N] float32, u [N, W, V] float32.
+    Returns the new slots -- parent (-1: dead), chr (-1: a carry or dead), state, logq, G, next_id, sel (the
+    flat index j, -1) -- and lq / gt [N, W, V] (NaN outside the allowed set / where not offered), zmax [N, W],
+    scale [N, W, V] (max(1, exp(Gt - g)): the conditioning of a candidate's truncation), and top / top_gt /
+    top_scale / top_row_scale [N, W + 1]: the first W + 1 candidates in order (-1 / NaN where there are fewer;
+    row_scale: max(1, exp(G_b - Z)) of the candidate's row, the supremum of its scale).  ``mut``: a planted
+    defect (models/sbs_ref.py)."""
+    N, W, V = x.shape
+    dt = x.dtype.type
+    ninf = dt(-np.inf)
+    with np.errstate(all="ignore"):
+        y = x * inv_t.astype(x.dtype)[:, None, None]
+        if allowed is None:
+            A = np.ones((N, W, V), bool)
+        else:
+            A = np.asarray(allowed, bool)
+            A = np.broadcast_to(A[:, None, :] if A.ndim == 2 else A, (N, W, V))
+        An = np.ones((N, W, V), bool) if mut == "lq_not_renormalised" else A
+        mx = np.where(An, y, ninf).max(-1, keepdims=True)
+        z = y - mx
+        e = np.where(An, _rounded(np.exp, z), dt(0))
+        se = _wave_sum(e)
+        lq = np.where(A, z - _rounded(np.log, se), dt(np.nan)).astype(x.dtype)
+        gum = -_rounded(np.log, -_rounded(np.log, u.astype(x.dtype)))
+        live = state == BEAM_LIVE
+        fin = state == BEAM_FIN
+        isf = (forced >= 0)[:, None, None]
+        off = A & live[:, :, None] & (~isf | (np.arange(V)[None, None, :] == forced[:, None, None]))
+        lqe = lq if mut == "forced_adds_lp" else np.where(isf, dt(0), lq)
+        psi = (logq[:, :, None] + lqe).astype(x.dtype)
+        g = psi + gum
+        if mut == "z_over_masked":      # every char of a live row, in its set or not
+            Z = np.where(live[:, :, None], (logq[:, :, None] + (z - _rounded(np.log, se))) + gum, ninf).max(-1)
+        else:
+            Z = np.where(off, g, ninf).max(-1)
+        d = g - Z[:, :, None]
+        l1 = np.where(d > dt(-0.6931), _rounded(np.log, -_rounded(np.expm1, d)), _rounded(np.log1p, -_rounded(np.exp, d)))
+        Gb = G[:, :, None]
+        v = (Gb - g) + l1
+        gt = (Gb - np.maximum(dt(0), v)) - _rounded(np.log1p, _rounded(np.exp, -np.abs(v)))
+        if mut == "naive_truncation":
+            gt = -_rounded(np.log, (_rounded(np.exp, -Gb) - _rounded(np.exp, -Z[:, :, None])) + _rounded(np.exp, -g))
+        if mut == "g_as_key":
+            gt = g
+        gt = np.where(off, gt, dt(np.nan)).astype(x.dtype)
+        psi = np.where(off, psi, dt(np.nan)).astype(x.dtype)
+        off = off.copy()
+        off[:, :, 0] |= fin
+        gt[:, :, 0] = np.where(fin, (logq + gum[:, :, 0]) if mut == "carry_reperturbed" else G, gt[:, :, 0])
+        psi[:, :, 0] = np.where(fin, logq, psi[:, :, 0])
+        has = off.any(-1) & live
+        zmax = np.where(has, Z, dt(np.nan)).astype(x.dtype)
+        # the conditioning of a candidate's Gt: |dGt/dg| = exp(Gt - g) (dGt/dZ and dGt/dG_b are no larger); a row's
+        # best child (Gt == G_b bitwise) and a carry have none.  Its supremum over a row is exp(G_b - Z).
+        scale = np.where(off & (d != 0) & live[:, :, None],
+                         np.maximum(1.0, np.exp(np.minimum(gt.astype(np.float64) - g.astype(np.float64), 80.0))), 1.0)
+        row_scale = np.where(has, np.maximum(1.0, np.exp(np.minimum(G.astype(np.float64) - Z.astype(np.float64), 80.0))), 1.0)
+        keyv = np.where(off, gt, ninf).reshape(N, W * V)
+        order = np.argsort(-keyv, axis=1, kind="stable")      # Gt descending, then j ascending
+    rows_i = np.arange(N)[:, None]
+    # ... offered candidates first: one whose Gt is -inf still ranks before what was not offered
+    order = order[rows_i, np.argsort(~off.reshape(N, W * V)[rows_i, order], axis=1, kind="stable")][:, :W + 1]
+    cnt = off.reshape(N, -1).sum(1)
+    valid = np.arange(W + 1)[None, :] < cnt[:, None]
+    top = np.where(valid, order, -1)
+    top_gt = np.where(valid, keyv[rows_i, order], np.nan)
+    top_scale = np.where(valid, scale.reshape(N, W * V)[rows_i, order], np.nan)
+    top_row_scale = np.where(valid, row_scale[rows_i, order // V], np.nan)
+    win, wv = order[:, :W], valid[:, :W]
+    pb, pc = win // V, win % V
+    carried = fin[rows_i, pb] & wv
+    parent = np.where(wv, pb, -1).astype(np.int32)
+    chrs = np.where(wv & ~carried, pc, -1).astype(np.int32)
+    nstate = np.where(wv, np.where(carried | (pc == eos), BEAM_FIN, BEAM_LIVE), BEAM_DEAD).astype(np.int32)
+    nlogq = np.where(wv, psi.reshape(N, -1)[rows_i, win], ninf).astype(x.dtype)
+    nG = np.where(wv, keyv[rows_i, win], ninf).astype(x.dtype)
+    if mut == "logq_from_key":
+        nlogq = np.where(wv & ~carried, nG - gum.reshape(N, -1)[rows_i, win], nlogq).astype(x.dtype)
+    nxt = np.where(nstate == BEAM_LIVE, pc, sos).astype(np.int32)
+    sel = np.where(wv, win, -1).astype(np.int32)
+    return dict(parent=parent, chr=chrs, state=nstate, logq=nlogq, G=nG, next_id=nxt, sel=sel, lq=lq, gt=gt, zmax=zmax,
+                scale=scale, top=top, top_gt=top_gt, top_scale=top_scale, top_row_scale=top_row_scale)
+
+
+class DistinctResult:
+    """``HipGenerator.sample_distinct`` / ``cpu_ref.sample_distinct`` output for N prefixes of W draws, in
+    draw order: rows [N, W, MAX_LEN+1] uint8 (the ``generate`` format), logq [N, W] (the rows' log-probability
+    under the sampler, -inf for a dead slot), gumbel [N, W] (the final perturbed values, non-increasing),
+    n_tok [N, W] int32, n_found [N] int32 (the slots that are not dead, always the first ones)."""
+
+    def __init__(self, rows, logq, gumbel, n_tok, n_found, eos: int = 0):
+        self.rows, self.logq, self.gumbel, self.n_tok, self.n_found, self.eos = rows, logq, gumbel, n_tok, n_found, eos
+
+    def names(self) -> List[List[str]]:
+        """Per prefix the draws' names in order (the EOS byte dropped, dead slots left out)."""
+        return BeamResult(self.rows, self.logq, self.n_tok, self.n_found, self.eos).names()
+
+
+def distinct_inputs(cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None, seed: int = 0,
+                    start: int = 0, temperature=None, **excluded):
+    """Validated (prefix rows, plen, inv_t [N] float32, seed, start) of ``sample_distinct``.  ValueError for
+    what ``beam_inputs`` rejects, a temperature that is not finite and > 0, a seed or start outside
+    [0, 2^64), and any of the keywords the rule does not carry (top_k, top_p, the soft controls)."""
+    for k, v in excluded.items():
+        if k not in ("top_k", "top_p", "logit_bias", "presence_penalty", "frequency_penalty", "soft"):
+            raise TypeError(f"sample_distinct: unexpected keyword {k!r}")
+        if v is not None:
+            raise ValueError(f"sample_distinct does not take {k}: the rule samples without replacement from the "
+                             "distribution of temperature, prefix and constraints alone")
+    pre, plen = beam_inputs(cfg, prefix, width, count)
+    N = pre.shape[0]
+    T = _per_name(1.0 if temperature is None else temperature, N, np.float64, "temperature")
+    if not np.isfinite(T).all() or (T <= 0).any():
+        raise ValueError("sample_distinct: temperature must be finite and > 0 (temperature 0 has one name: use beam_search)")
+    with np.errstate(over="ignore", under="ignore"):
+        inv = (1.0 / T).astype(np.float32)
+    if (~np.isfinite(inv)).any() or (inv == 0).any():
+        raise ValueError("temperature: 1/T must be a finite non-zero fp32 value")
+    for what, v in (("seed", seed), ("start", start)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"{what} must be an integer in [0, 2^64), got {v!r}")
+    if int(start) + N > 2 ** 64:
+        raise ValueError("start + count must stay below 2^64")
+    return pre, plen, inv, int(seed), int(start)
+
+
+def sample_distinct(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None, *,
+                    seed: int = 0, start: int = 0, temperature=None, constraints=None, **excluded) -> DistinctResult:
+    """``width`` distinct names per prefix, an exact sample without replacement in draw order (the rule
+    above) in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli distinct``).  Name n
+    of the call has the global index ``start + n``: its noise does not depend on how a job is cut up."""
+    pre, plen, inv, seed, start = distinct_inputs(cfg, prefix, width, count, seed, start, temperature, **excluded)
+    cons = as_constraints(cfg, pre.shape[0], constraints)
+    check_prefix_allowed(cons, pre, plen)
+    return sample_distinct_rule(params, cfg, pre, plen, int(width), seed, start, inv, cons)
+
+
+def sample_distinct_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, seed: int,
+                         start: int, inv_t: np.ndarray, cons=None, mut: Optional[str] = None,
+                         trace: Optional[list] = None) -> DistinctResult:
+    """The rule itself on validated inputs.  ``trace``: a list that receives every step's ``sbs_step``
+    output (models/sbs_ref.py); ``mut``: a planted defect (there too)."""
+    N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
+    dt = params["fc.weight"].dtype
+    npdt = np.float64 if dt == torch.float64 else np.float32
+    rows = np.zeros((N, W, ML + 1), np.uint8)
+    logq = np.full((N, W), -np.inf, npdt)
+    G = np.full((N, W), -np.inf, npdt)
+    state = np.full((N, W), BEAM_DEAD, np.int32)
+    ntok = np.zeros((N, W), np.int32)
+    if N == 0:
+        return DistinctResult(rows, logq, G, ntok, np.zeros(0, np.int32), cfg.eos)
+    logq[:, 0] = G[:, 0] = 0
+    state[:, 0] = BEAM_LIVE
+    hs = [torch.zeros(N * W, H, dtype=dt) for _ in range(cfg.layers)]
+    cur = torch.full((N * W,), cfg.sos, dtype=torch.int64)
+    aut = cons if isinstance(cons, Automaton) else None
+    if aut is not None:
+        alines, astate = aut.lines(), np.zeros((N, W), np.int64)
+        astate[:, 0] = aut.start
+    gidx = np.arange(N, dtype=np.uint64) + np.uint64(0 if mut == "counter_local_index" else start)
+    ni = np.arange(N)[:, None]
+    for l in range(ML):
+        inp = params["embedding"][cur]
+        new = []
+        for k in range(cfg.layers):
+            gi = inp @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
+            gh = hs[k] @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
+            hk, _ = _gates(gi, gh, hs[k])
+            new.append(hk)
+            inp = hk
+        logits = inp @ params["fc.weight"].T + params["fc.bias"]
+        if dt != torch.float64:
+            logits = logits.to(torch.float32)
+        x = logits.numpy().reshape(N, W, V)
+        allowed = None if cons is None else (alines[astate] if aut is not None else cons.allowed(l))
+        forced = np.where(plen > l, pre[:, l].astype(np.int64), -1)
+        u = sbs_uniform(seed, gidx, 0 if mut == "counter_without_step" else l, W, V)
+        s = sbs_step(x, logq, G, state, forced, allowed, inv_t, u, cfg.eos, cfg.sos, mut)
+        if trace is not None:
+            trace.append(s)
+        par = np.maximum(s["parent"], 0)
+        alive = s["parent"] >= 0
+        app = s["chr"] >= 0
+        nrows = np.where(alive[:, :, None], rows[ni, par], 0).astype(np.uint8)
+        nrows[:, :, l] = np.where(app, s["chr"], nrows[:, :, l])
+        ntok = np.where(alive, np.where(app, l + 1, ntok[ni, par]), 0).astype(np.int32)
+        if aut is not None:   # (a carried or dead slot sits in state 0)
+            astate = np.where(app, aut.nxt[astate[ni, par], np.maximum(s["chr"], 0)].astype(np.int64), 0)
+        gather = torch.from_numpy((ni * W + par).reshape(-1).astype(np.int64))
+        dead = torch.from_numpy(~alive.reshape(-1))
+        hs = [h[gather].masked_fill(dead[:, None], 0) for h in new]
+        rows, logq, G, state = nrows, s["logq"], s["G"], s["state"]
+        cur = torch.from_numpy(s["next_id"].reshape(-1).astype(np.int64))
+    return DistinctResult(rows, logq, G, ntok, (state != BEAM_DEAD).sum(1).astype(np.int32), cfg.eos)
