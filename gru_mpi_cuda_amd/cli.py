@@ -8,6 +8,7 @@
     python -m gru_mpi_cuda_amd.cli beam     --ckpt out/model.bin --width 5 --prefix Mar
     python -m gru_mpi_cuda_amd.cli generate --ckpt out/model.bin -n 200 --regex '.*son' --exclude-file train.txt --exclude-emitted
     python -m gru_mpi_cuda_amd.cli distinct --ckpt out/model.bin --width 20 --prefix Mar --seed 1
+    python -m gru_mpi_cuda_amd.cli conditional --ckpt out/model.bin --regex '.*son' --width 16 --runs 8
     python -m gru_mpi_cuda_amd.cli info
     python -m gru_mpi_cuda_amd.cli bench    [bench.py args]
 
@@ -513,6 +514,64 @@ def cmd_distinct(args) -> int:
     return 0
 
 
+def cmd_conditional(args) -> int:
+    """Weighted names from the model's own distribution over the names that satisfy the constraints, and the
+    probability of the constraints under the model (sequential Monte Carlo, docs/DESIGN.md §4j): one
+    `prefix<TAB>i<TAB>name<TAB>weight` line per particle (weights normalised per prefix), or per draw with
+    --draw; one JSON summary per prefix on stderr (log_z, probability, z_stderr, ess, resamples)."""
+    import json
+    import torch
+    from .engine import generator as G
+    from .models import cpu_ref
+    from .utils import ckpt
+    fmt = args.fmt
+    if fmt == "auto":
+        fmt = "gen" if os.path.exists(args.ckpt + ".json") else "ref"
+    cfg, params = ckpt.load(args.ckpt, _cfg_from(args) if fmt == "ref" else None, fmt)
+    over = {k: getattr(args, k) for k in ("max_len", "sos", "eos") if getattr(args, k) is not None}
+    cfg = cfg.replace(**over)
+    if args.prefix is not None and args.prefix_file is not None:
+        raise SystemExit("--prefix and --prefix-file exclude each other")
+    if args.prefix_file:
+        prefixes = [b.decode("latin-1") for b in _read_names(args.prefix_file)]
+    else:
+        prefixes = [args.prefix or ""]
+    if args.draw is not None and args.draw < 1:
+        raise SystemExit("--draw needs a count >= 1")
+    kw = dict(runs=args.runs, seed=args.noise_seed, temperature=args.temperature, constraints=_constraints_from(args),
+              ess_threshold=args.ess_threshold, top_k=args.top_k, top_p=args.top_p, logit_bias=args.logit_bias,
+              presence_penalty=args.presence_penalty, frequency_penalty=args.frequency_penalty)
+    try:
+        if args.cpu or not torch.cuda.is_available():
+            res = cpu_ref.sample_conditional({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width, **kw)
+        else:
+            gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.runs * args.width)))
+            res = gen.sample_conditional(prefixes, args.width, **kw)
+    except ValueError as e:
+        raise SystemExit(f"conditional: {e}")
+    lines = []
+    names, w = res.names(), res.weights()
+    drawn = res.draw(args.draw, args.noise_seed) if args.draw is not None else None
+    for n, pre in enumerate(prefixes):
+        if drawn is not None:
+            for k, nm in enumerate(drawn[n]):
+                lines.append(f"{_escape(pre)}\t{k}\t{_escape(nm)}\t{1.0 / len(drawn[n]):.6f}")
+        else:
+            for k, nm in enumerate(names[n]):
+                lines.append(f"{_escape(pre)}\t{k}\t{_escape(nm)}\t{float(w[n, k]):.6f}")
+        se = float(res.z_stderr[n])
+        sys.stderr.write(json.dumps(dict(prefix=pre, log_z=float(res.log_z[n]), probability=float(np.exp(res.log_z[n])),
+                                         z_stderr=None if se != se else se, ess=float(res.ess[n]),
+                                         resamples=[int(v) for v in res.n_resampled[n]])) + "\n")
+    text = "\n".join(lines) + ("\n" if lines else "")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    else:
+        sys.stdout.write(text)
+    return 0
+
+
 class _Evaluator:
     """Held-out evaluation for `train --eval-data`: the file is read once; every call scores the
     trainer's current weights on all of it (each rank the whole file: no collective of its own)."""
@@ -651,6 +710,31 @@ def main(argv=None) -> int:
                     help="the sampler's seed: the same seed gives the same names (default 0)")
     ds.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(ds, skip=("seed",))      # --seed is the sampler's here, not the config's
+    cd = sub.add_parser("conditional", help="weighted names from the model's distribution given the constraints, and "
+                                            "the constraints' probability (sequential Monte Carlo)")
+    cd.add_argument("--ckpt", required=True)
+    cd.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")
+    cd.add_argument("--width", type=int, default=16, help="particles per system, 1 .. min(32, vocab)")
+    cd.add_argument("--runs", type=int, default=1, help="independent systems per prefix, pooled (default 1)")
+    cd.add_argument("--prefix", default=None, help="the names start with these chars (default: the empty prefix)")
+    cd.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
+    cd.add_argument("--temperature", type=float, default=None, help="softmax temperature, > 0 (default 1)")
+    cd.add_argument("--ess-threshold", dest="ess_threshold", type=float, default=0.5,
+                    help="resample when the effective sample size falls below this fraction of the width (0: never)")
+    _constraint_args(cd)
+    cd.add_argument("--draw", type=int, default=None, help="print K names per prefix drawn from the weighted pool instead")
+    cd.add_argument("--out", default=None, help="prefix, index, name and weight per line, tab-separated")
+    cd.add_argument("--cpu", action="store_true", help="cpu_ref.sample_conditional in fp32 instead of the HIP generator")
+    cd.add_argument("--seed", dest="noise_seed", type=int, default=0,
+                    help="the sampler's seed: the same seed gives the same particles (default 0)")
+    # not carried by the rule: given, they are an error before anything runs
+    cd.add_argument("--top-k", dest="top_k", type=int, default=None, help=argparse.SUPPRESS)
+    cd.add_argument("--top-p", dest="top_p", type=float, default=None, help=argparse.SUPPRESS)
+    cd.add_argument("--logit-bias", dest="logit_bias", default=None, help=argparse.SUPPRESS)
+    cd.add_argument("--presence-penalty", dest="presence_penalty", type=float, default=None, help=argparse.SUPPRESS)
+    cd.add_argument("--frequency-penalty", dest="frequency_penalty", type=float, default=None, help=argparse.SUPPRESS)
+    cd.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
+    _add_model_args(cd, skip=("seed",))      # --seed is the sampler's here, not the config's
     sub.add_parser("info", help="device / build info")
     b = sub.add_parser("bench", help="run bench.py", add_help=False)
     args, rest = ap.parse_known_args(argv)
@@ -662,7 +746,7 @@ def main(argv=None) -> int:
     if rest:
         ap.error(f"unrecognized arguments: {rest}")
     return {"train": cmd_train, "generate": cmd_generate, "score": cmd_score, "beam": cmd_beam, "distinct": cmd_distinct,
-            "info": cmd_info}[args.cmd](args)
+            "conditional": cmd_conditional, "info": cmd_info}[args.cmd](args)
 
 
 if __name__ == "__main__":

@@ -276,6 +276,19 @@ PYBIND11_MODULE(_C, m) {
          py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
          py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0, py::arg("allow_start") = (uintptr_t)0)
       .def("distinct_graphs", &Generator::distinct_graphs)
+      .def("conditional", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, unsigned long long seed,
+                             unsigned long long start, float thr, uintptr_t inv_t, uintptr_t rows, uintptr_t logw,
+                             uintptr_t logq, uintptr_t n_tok, uintptr_t n_res, uintptr_t s, uintptr_t allow_tab,
+                             uintptr_t allow_idx, int allow_rows, uintptr_t allow_next, uintptr_t allow_start) {
+        g.conditional(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, seed, start, thr, Pp<const float>(inv_t),
+                      Pp<unsigned char>(rows), Pp<float>(logw), Pp<float>(logq), Pp<int>(n_tok), Pp<int>(n_res), S(s),
+                      Pp<const unsigned>(allow_tab), Pp<const int>(allow_idx), allow_rows,
+                      Pp<const unsigned short>(allow_next), Pp<const int>(allow_start));
+      }, py::arg("plen"), py::arg("prefix"), py::arg("N"), py::arg("W"), py::arg("seed"), py::arg("start"),
+         py::arg("thr"), py::arg("inv_t"), py::arg("rows"), py::arg("logw"), py::arg("logq"), py::arg("n_tok"),
+         py::arg("n_res"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
+         py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0, py::arg("allow_start") = (uintptr_t)0)
+      .def("conditional_graphs", &Generator::conditional_graphs)
       .def("beam_workspace_bytes", &Generator::beam_workspace_bytes)
       .def("beam_graphs", &Generator::beam_graphs)
       .def("set_use_graph", &Generator::set_use_graph)
@@ -999,6 +1012,28 @@ PYBIND11_MODULE(_C, m) {
     a.allow_state_in = GP(const int, d, "allow_state_in"); a.allow_state_out = GP(int, d, "allow_state_out");
     a.allow_next = GP(const unsigned short, d, "allow_next");
     sbs_select_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the sequential Monte Carlo selection on caller-owned buffers (tests/test_smc_gpu.py)
+  m.def("smc_select", [](py::dict d, uintptr_t s) {
+    SmcSelectArgs a;
+    a.logits = GP(const float, d, "logits"); a.splits = get<int>(d, "splits", 1); a.slab = get<long>(d, "slab", 0);
+    a.bias = GP(const float, d, "bias"); a.logw_in = GP(const float, d, "logw_in"); a.logq_in = GP(const float, d, "logq_in");
+    a.state_in = GP(const int, d, "state_in"); a.plen = GP(const int, d, "plen");
+    a.prefix = GP(const unsigned char, d, "prefix");
+    a.seed = GP(const unsigned long long, d, "seed"); a.start = GP(const unsigned long long, d, "start");
+    a.thr = GP(const float, d, "thr"); a.inv_t = GP(const float, d, "inv_t");
+    a.logw_out = GP(float, d, "logw_out"); a.logq_out = GP(float, d, "logq_out"); a.parent = GP(int, d, "parent");
+    a.chr = GP(int, d, "chr"); a.state_out = GP(int, d, "state_out"); a.next_id = GP(int, d, "next_id");
+    a.n_res = GP(int, d, "n_res"); a.logm = GP(float, d, "logm"); a.lq = GP(float, d, "lq"); a.ess = GP(float, d, "ess");
+    a.err = GP(unsigned, d, "err");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0);
+    a.max_len = get<int>(d, "max_len", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
+    a.allow_rows = get<int>(d, "allow_rows", 0);
+    a.allow_state_in = GP(const int, d, "allow_state_in"); a.allow_state_out = GP(int, d, "allow_state_out");
+    a.allow_next = GP(const unsigned short, d, "allow_next");
+    smc_select_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("beam_reorder", [](py::dict d, uintptr_t s) {

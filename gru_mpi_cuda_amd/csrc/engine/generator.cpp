@@ -105,6 +105,8 @@ Generator::~Generator() {
   bgraphs_.clear();
   dgraphs_.clear();
   adgraphs_.clear();
+  qgraphs_.clear();
+  aqgraphs_.clear();
   agraphs_.clear();
   csgraphs_.clear();
   asgraphs_.clear();
@@ -116,6 +118,8 @@ Generator::~Generator() {
                   (void*)abstate_[1]})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)dG_[0], (void*)dG_[1], (void*)dinv_, (void*)dwords_})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)qw_[0], (void*)qw_[1], (void*)qinv_, (void*)qres_, (void*)qwords_})
     if (p) (void)hipFree(p);
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
@@ -458,6 +462,7 @@ void Generator::automaton_stage(const unsigned* tab, const unsigned short* next,
     asgraphs_.clear();
     abgraphs_.clear();
     adgraphs_.clear();
+    aqgraphs_.clear();
     if (atab_) HIP_CHECK(hipFree(atab_));
     if (anxt_) HIP_CHECK(hipFree(anxt_));
     atab_ = nullptr; anxt_ = nullptr; acap_ = 0;
@@ -855,7 +860,7 @@ void Generator::beam_alloc() {
 // exact-fp32 step (the master weights, f32_splits slabs summed in order by the consumer), but on
 // fixed slots: the gates read bhA_ and write bhB_, the reorder gathers bhB_ -> bhA_.  Scores, states,
 // lengths and output rows alternate between two sets by step parity; the result is in set ML & 1.
-void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows, bool automaton, bool distinct) {
+void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows, bool automaton, BeamSelect sel) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = rup(n * W, 64);
   const int cap = std::max(Bmax_, kF32SlabRows);
@@ -890,14 +895,12 @@ void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows, bool au
       gru_gates_f32(a, s);
     }
     const int splits = product(bhB_[L - 1], P("fc.weight"), P("fc.bias"), V, blogits_);
-    if (distinct) {   // §4i: the same loop, ranked by truncated Gumbel-perturbed log-probabilities
-      SbsSelectArgs q;
+    // what the three selections share: the logits, the states, the prefix, the outputs beam_reorder reads, the
+    // shape and the constraint (an automaton's state buffers by step parity, or the per-position table)
+    auto common = [&](auto& q) {
       q.logits = blogits_; q.splits = splits; q.slab = (long)Bp * V;
-      q.logq_in = bscore_[cur]; q.G_in = st == 0 ? bscore_[0] : dG_[cur];   // before step 0: G = logq = 0 / -inf
       q.state_in = bstate_[cur]; q.plen = bplen_; q.prefix = bprefix_;
-      q.seed = dwords_; q.start = dwords_ + 1; q.inv_t = dinv_;
-      q.logq_out = bscore_[nxt]; q.G_out = dG_[nxt]; q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_;
-      q.next_id = bnext_;
+      q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_; q.next_id = bnext_;
       q.err = err_; q.N = n; q.W = W; q.V = V; q.step = st; q.max_len = ML; q.sos = d_.sos; q.eos = d_.eos;
       if (automaton) {
         q.allow_tab = atab_; q.allow_next = anxt_; q.allow_rows = allow_rows;
@@ -905,19 +908,25 @@ void Generator::record_beam(int n, int W, hipStream_t s, int allow_rows, bool au
       } else if (allow_rows > 0) {
         q.allow_tab = btab_; q.allow_idx = bidx_; q.allow_rows = allow_rows;
       }
+    };
+    if (sel == BeamSelect::kConditional) {   // §4j: the same loop, W weighted particles with resampling
+      SmcSelectArgs q;
+      common(q);
+      q.logq_in = bscore_[cur]; q.logw_in = st == 0 ? bscore_[0] : qw_[cur];   // before step 0: logw = logq = 0 / -inf
+      q.seed = qwords_; q.start = qwords_ + 1; q.thr = reinterpret_cast<const float*>(qwords_ + 2); q.inv_t = qinv_;
+      q.logq_out = bscore_[nxt]; q.logw_out = qw_[nxt]; q.n_res = qres_;
+      smc_select_f32(q, s);
+    } else if (sel == BeamSelect::kDistinct) {   // §4i: the same loop, ranked by truncated Gumbel-perturbed log-probabilities
+      SbsSelectArgs q;
+      common(q);
+      q.logq_in = bscore_[cur]; q.G_in = st == 0 ? bscore_[0] : dG_[cur];   // before step 0: G = logq = 0 / -inf
+      q.seed = dwords_; q.start = dwords_ + 1; q.inv_t = dinv_;
+      q.logq_out = bscore_[nxt]; q.G_out = dG_[nxt];
       sbs_select_f32(q, s);
     } else {
       BeamSelectArgs q;
-      q.logits = blogits_; q.splits = splits; q.slab = (long)Bp * V;
-      q.score_in = bscore_[cur]; q.state_in = bstate_[cur]; q.plen = bplen_; q.prefix = bprefix_;
-      q.score_out = bscore_[nxt]; q.state_out = bstate_[nxt]; q.parent = bparent_; q.chr = bchr_; q.next_id = bnext_;
-      q.err = err_; q.N = n; q.W = W; q.V = V; q.step = st; q.max_len = ML; q.sos = d_.sos; q.eos = d_.eos;
-      if (automaton) {
-        q.allow_tab = atab_; q.allow_next = anxt_; q.allow_rows = allow_rows;
-        q.allow_state_in = abstate_[cur]; q.allow_state_out = abstate_[nxt];
-      } else if (allow_rows > 0) {
-        q.allow_tab = btab_; q.allow_idx = bidx_; q.allow_rows = allow_rows;
-      }
+      common(q);
+      q.score_in = bscore_[cur]; q.score_out = bscore_[nxt];
       beam_select_f32(q, s);
     }
     BeamReorderArgs o;
@@ -1054,12 +1063,12 @@ void Generator::distinct(const int* plen, const unsigned char* prefix, int N, in
       if (!g) {
         g.reset(new Graph());
         g->begin(cap_);
-        record_beam(n, W, cap_, ar, aut, true);
+        record_beam(n, W, cap_, ar, aut, BeamSelect::kDistinct);
         g->end(cap_);
       }
       g->launch(s);
     } else {
-      record_beam(n, W, s, ar, aut, true);
+      record_beam(n, W, s, ar, aut, BeamSelect::kDistinct);
     }
     const size_t r0 = (size_t)b0 * W, nr = (size_t)n * W;
     HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), brows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));
@@ -1067,6 +1076,87 @@ void Generator::distinct(const int* plen, const unsigned char* prefix, int N, in
     HIP_CHECK(hipMemcpyAsync(gumbel + r0, dG_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + r0, blen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_found + b0, bnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ------------------------------------------------------------------------------ conditional names
+void Generator::conditional_alloc() {
+  if (qwords_) return;
+  const size_t B = Bmax_;
+  for (float** p : {&qw_[0], &qw_[1], &qinv_}) {
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), B * 4));
+    HIP_CHECK(hipMemset(*p, 0, B * 4));
+  }
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&qres_), B * 4));
+  HIP_CHECK(hipMemset(qres_, 0, B * 4));
+  HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&qwords_), 32));
+  HIP_CHECK(hipMemset(qwords_, 0, 32));
+}
+
+void Generator::conditional(const int* plen, const unsigned char* prefix, int N, int W, unsigned long long seed,
+                            unsigned long long start, float thr, const float* inv_t, unsigned char* rows, float* logw,
+                            float* logq, int* n_tok, int* n_res, hipStream_t s, const unsigned* allow_tab,
+                            const int* allow_idx, int allow_rows, const unsigned short* allow_next, const int* allow_start) {
+  GK_TRACE("gk.conditional");
+  const int ML = d_.max_len;
+  if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::conditional needs 1 <= width <= min(32, vocab)");
+  if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::conditional needs max_len <= 64 and vocab <= 512");
+  if (d_.max_batch < W) throw std::runtime_error("Generator::conditional needs max_batch >= width");
+  if (d_.L > 4) throw std::runtime_error("Generator::conditional needs at most 4 layers");
+  if (!(thr >= 0.f && thr <= 1.f)) throw std::runtime_error("Generator::conditional needs 0 <= ess threshold <= 1");
+  if (!plen || !prefix || !inv_t || !rows || !logw || !logq || !n_tok || !n_res)
+    throw std::runtime_error("Generator::conditional: plen, prefix, inv_t, rows, logw, logq, n_tok and n_res are required");
+  const bool aut = allow_next != nullptr || allow_start != nullptr;
+  if (aut && (!allow_next || !allow_start || !allow_tab || allow_idx || allow_rows < 1 || allow_rows > kAutoStates ||
+              (d_.V != 256 && d_.V != 512)))
+    throw std::runtime_error("Generator::conditional: an automaton needs allow_tab, allow_next and allow_start, no "
+                             "allow_idx, 1 <= allow_rows <= 65535 and a vocabulary of 256 or 512");
+  const bool masked = allow_tab != nullptr;
+  if (!aut && (masked != (allow_idx != nullptr) || (masked && (allow_rows < 1 || allow_rows > kAllowRows))))
+    throw std::runtime_error("Generator::conditional: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
+  if (N <= 0) return;
+  beam_alloc();       // first call: allocates (and synchronises) before anything is captured
+  conditional_alloc();
+  if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);   // the tables once per call
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));
+  err_clean_ = false;
+  const int nb = d_.max_batch / W, fin = ML & 1;
+  const int ar = masked ? allow_rows : 0;
+  if (masked && !aut)   // the table once per call
+    HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+  for (int b0 = 0; b0 < N; b0 += nb) {
+    const int n = std::min(nb, N - b0);
+    HIP_CHECK(hipMemcpyAsync(bplen_, plen + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)b0 * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(qinv_, inv_t + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    smc_stage(qwords_, seed, start + (unsigned long long)b0, thr, s);
+    HIP_LAUNCH_CHECK();
+    if (aut)
+      HIP_CHECK(hipMemcpyAsync(abstart_, allow_start + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    else if (masked)
+      HIP_CHECK(hipMemcpyAsync(bidx_, allow_idx + (size_t)b0 * ML, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      if (aut && aqgraphs_.size() >= kAutoGraphs && !aqgraphs_.count(std::make_tuple(n, W, ar))) {   // as in beam()
+        HIP_CHECK(hipStreamSynchronize(s));
+        aqgraphs_.clear();
+      }
+      auto& g = aut ? aqgraphs_[std::make_tuple(n, W, ar)] : qgraphs_[std::make_tuple(n, W, ar)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_beam(n, W, cap_, ar, aut, BeamSelect::kConditional);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_beam(n, W, s, ar, aut, BeamSelect::kConditional);
+    }
+    const size_t r0 = (size_t)b0 * W, nr = (size_t)n * W;
+    HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), brows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(logq + r0, bscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(logw + r0, qw_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + r0, blen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_res + b0, qres_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

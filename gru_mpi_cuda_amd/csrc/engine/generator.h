@@ -147,6 +147,20 @@ class Generator {
                 int* n_found, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
                 int allow_rows = 0, const unsigned short* allow_next = nullptr, const int* allow_start = nullptr);
   int distinct_graphs() const { return (int)(dgraphs_.size() + adgraphs_.size()); }   // recordings so far
+  // Conditional names (docs/DESIGN.md §4j; the rule: cpu_ref.sample_conditional): for each of N names W
+  // weighted particles of a sequential Monte Carlo run over the constrained sampler.  rows [N][W][max_len+1],
+  // logw [N][W] (the unnormalised log importance weights: their mean of exp is an unbiased estimate of the
+  // rule's probability under the model), logq [N][W] (the rows' log-probability under the sampler), n_tok
+  // [N][W], n_res [N] (the resampling steps), all device pointers.  thr: resample when ESS < thr W.  It is
+  // distinct()'s loop with smc_select_f32 as the selection: the same batches, the batch's first global index,
+  // the seed and thr in device words, recordings of its own per (names, W, constraint lines or states) that
+  // bake in none of them.  Its buffers are plain allocations made by the first call.
+  void conditional(const int* plen, const unsigned char* prefix, int N, int W, unsigned long long seed,
+                   unsigned long long start, float thr, const float* inv_t, unsigned char* rows, float* logw, float* logq,
+                   int* n_tok, int* n_res, hipStream_t s, const unsigned* allow_tab = nullptr,
+                   const int* allow_idx = nullptr, int allow_rows = 0, const unsigned short* allow_next = nullptr,
+                   const int* allow_start = nullptr);
+  int conditional_graphs() const { return (int)(qgraphs_.size() + aqgraphs_.size()); }   // recordings so far
   size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
@@ -201,9 +215,13 @@ class Generator {
   void soft_alloc();
   void score_ctl_alloc();
   void beam_alloc();
-  // distinct: sbs_select_f32 as the selection (G by step parity, step 0 reads the reset scores as G)
-  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false, bool distinct = false);
+  // the beam loop's selection: beam_select_f32; sbs_select_f32 (G by step parity, step 0 reads the reset scores
+  // as G); smc_select_f32 (logw by step parity, step 0 reads the reset scores as logw)
+  enum class BeamSelect { kBeam, kDistinct, kConditional };
+  void record_beam(int n, int W, hipStream_t s, int allow_rows = 0, bool automaton = false,
+                   BeamSelect sel = BeamSelect::kBeam);
   void distinct_alloc();
+  void conditional_alloc();
   // the automaton buffers for `states` states (grown, never shrunk) and the call's tables into them
   void automaton_stage(const unsigned* tab, const unsigned short* next, int states, hipStream_t s);
   const float* P(const std::string& n) const { return params_ + off_.at(n); }
@@ -305,6 +323,13 @@ class Generator {
   unsigned long long* dwords_ = nullptr;        // [2] the call's seed, the current batch's first global index
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> dgraphs_;    // keyed by (names, W, table lines or 0)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> adgraphs_;   // keyed by (names, W, states)
+  // conditional names (plain allocations, made by the first conditional() call)
+  float* qw_[2] = {nullptr, nullptr};           // [Bmax] x2 the slots' log importance weights, by step parity
+  float* qinv_ = nullptr;                       // [Bmax] the current batch's 1 / T
+  int* qres_ = nullptr;                         // [Bmax] the current batch's resampling steps per name
+  unsigned long long* qwords_ = nullptr;        // [4] the call's seed, the batch's first global index, the ESS threshold
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> qgraphs_;    // keyed by (names, W, table lines or 0)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> aqgraphs_;   // keyed by (names, W, states)
   // automaton constraints (plain allocations, made by the first automaton call and grown on demand)
   unsigned* atab_ = nullptr;                    // [acap_][V / 32] the call's state sets
   unsigned short* anxt_ = nullptr;              // [acap_][V] the call's successor table

@@ -691,6 +691,47 @@ void sbs_select_f32(const SbsSelectArgs& a, hipStream_t s);
 // *seed = seed_v, *start = start_v as one kernel node on the stream (the values travel as kernel arguments)
 void sbs_stage(unsigned long long* seed, unsigned long long seed_v, unsigned long long* start, unsigned long long start_v,
                hipStream_t s);
+// smc_select_f32 (smc.hip, docs/DESIGN.md §4j; the rule: cpu_ref.smc_step): the selection of a sequential
+// Monte Carlo step over the constrained sampler, one workgroup per name, sbs_select_f32's geometry, states,
+// constraints and error word.  A slot carries logw (its unnormalised log importance weight) and logq (its
+// row's log-probability under the sampler).  Per live slot b: y = x * inv_t[n], lse_all over the vocabulary,
+// lse_A over the allowed set, logm = lse_A - lse_all (0 on a forced step and for a finished slot),
+// u = logw + logm.  Over the slots that are not dead: e = expf(u - max u), S = sum e, ESS = S S / sum e e.
+// Step 0 fans slot 0 out into every slot; otherwise, iff ESS < *thr W, systematic resampling with the step's
+// one uniform and logw = max u + logf(S / W) for every new slot; otherwise slot i keeps ancestor i and
+// logw = u_i.  New slot i carries a finished ancestor or draws one char of a live one by the inverse CDF over
+// the allowed set (the forced char on a forced step) and adds its y[c] - lse_A (0 when forced) to logq.
+// Noise: Philox-4x32-10(key = *seed, counter = (i, step, *start + n)), word 0 slot i's uniform, word 1 of slot
+// 0's block the resampling uniform, both (2 (word >> 9) + 1) 2^-24.
+struct SmcSelectArgs {
+  const float* logits = nullptr;   // [>= N W][V], row n W + b
+  int splits = 1; long slab = 0;   // split-K slabs of the logits, summed in fixed order
+  const float* bias = nullptr;     // nullable: added after the slab sum
+  const float* logw_in = nullptr; const float* logq_in = nullptr; const int* state_in = nullptr;   // [N W]
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][max_len]
+  const unsigned long long* seed = nullptr;    // one word: the Philox key
+  const unsigned long long* start = nullptr;   // one word: the global index of name 0 of this launch
+  const float* thr = nullptr;              // one word: the ESS threshold, as a fraction of W
+  const float* inv_t = nullptr;            // [N] 1 / temperature
+  float* logw_out = nullptr; float* logq_out = nullptr; int* parent = nullptr; int* chr = nullptr;   // [N W],
+  int* state_out = nullptr; int* next_id = nullptr;                                                  // never the inputs
+  int* n_res = nullptr;            // nullable [N]: the resampling steps so far (step 0 writes 0, a later step adds)
+  float* logm = nullptr;           // nullable [N W]: logm, NaN for a dead slot (tests)
+  float* lq = nullptr;             // nullable [N W][V]: a live row's y - lse_A, NaN outside the set (tests)
+  float* ess = nullptr;            // nullable [N]: ESS (tests)
+  unsigned* err = nullptr;         // nullable
+  int N = 0, W = 0, V = 0, step = 0, max_len = 0, sos = 0, eos = 0;   // V % 64 == 0, V <= 512, W <= min(32, V)
+  const unsigned* allow_tab = nullptr;     // as BeamSelectArgs' seven
+  const int* allow_idx = nullptr;
+  int allow_rows = 0;
+  const int* allow_state_in = nullptr;
+  int* allow_state_out = nullptr;
+  const unsigned short* allow_next = nullptr;
+};
+void smc_select_f32(const SmcSelectArgs& a, hipStream_t s);
+// words[0] = seed_v, words[1] = start_v, the float at words + 2 = thr_v, as one kernel node on the stream
+void smc_stage(unsigned long long* words, unsigned long long seed_v, unsigned long long start_v, float thr_v, hipStream_t s);
 // The winners' state moved into the next step's slots: per layer h_dst[n W + k] = h_src[n W + parent[k]]
 // (zeros for a dead beam), rows_dst likewise with chr appended at the parent's length (len_src ->
 // len_dst), ids = next_id, n_beams[n] = the beams that are not dead.  A gather is never in place: source

@@ -341,9 +341,57 @@ class HipGenerator:
         return DistinctResult(rows.cpu().numpy(), logq.cpu().numpy(), gum.cpu().numpy(), nt.cpu().numpy(),
                               nf.cpu().numpy(), self.cfg.eos)
 
+    def sample_conditional(self, prefix=None, width: int = 16, count: Optional[int] = None, *, runs: int = 1, seed: int = 0,
+                           start: int = 0, temperature=None, constraints=None, ess_threshold: float = 0.5,
+                           **excluded) -> "ConditionalResult":
+        """Weighted names from the MODEL's distribution conditioned on ``constraints`` (and ``prefix``), and the
+        probability of the rule under the model -- sequential Monte Carlo over the constrained sampler (the
+        rule: cpu_ref.sample_conditional, docs/DESIGN.md §4j).  ``generate(constraints=...)`` renormalises the
+        allowed chars at every step, so each of its names satisfies the rule but a name is favoured by the
+        mass that was forbidden along its way; here every particle carries that mass as its importance weight
+        and the particles are resampled when ESS < ``ess_threshold`` x width (0: plain importance sampling).
+
+        ``runs`` independent systems of ``width`` <= 32 particles per prefix are pooled (run r of prefix n draws
+        its noise at the global index ``start + n * runs + r`` under ``seed``: the result does not depend on
+        how a job is cut into calls or batches).  ``exp(result.log_z)`` is an unbiased estimate of P(rule |
+        prefix) at any width; ``weights`` / ``expectation`` / ``draw`` are self-normalised: consistent, with a
+        bias of order 1 / particles.  Always exact fp32 arithmetic; precision "bf16" is refused (ValueError),
+        as are top_k, top_p, temperature 0 and the soft controls, before anything is launched."""
+        if self.precision == "bf16":
+            raise ValueError('sample_conditional needs precision "fp32" or "bf16x3" (it runs exact fp32; the bf16 mode '
+                             "samples from another distribution)")
+        pre, plen, inv, seed, start, thr, N, R = cpu_ref.conditional_inputs(self.cfg, prefix, width, count, runs, seed, start,
+                                                                            temperature, ess_threshold, **excluded)
+        M, W, ML = N * R, int(width), self.cfg.max_len
+        cons = cpu_ref.conditional_constraints(self.cfg, N, R, constraints)
+        cpu_ref.check_prefix_allowed(cons, pre, plen)
+        if M == 0:
+            return cpu_ref.pool_conditional(np.zeros((0, W, ML + 1), np.uint8), np.zeros((0, W), np.float32),
+                                            np.zeros((0, W), np.float32), np.zeros((0, W), np.int32), np.zeros(0, np.int32),
+                                            N, R, W, self.cfg.eos)
+        p, l = torch.from_numpy(pre).to(self.dev), torch.from_numpy(plen).to(self.dev)
+        it = torch.from_numpy(inv).to(self.dev)
+        rows = torch.empty(M, W, ML + 1, dtype=torch.uint8, device=self.dev)
+        logw = torch.empty(M, W, dtype=torch.float32, device=self.dev)
+        logq = torch.empty(M, W, dtype=torch.float32, device=self.dev)
+        nt = torch.empty(M, W, dtype=torch.int32, device=self.dev)
+        nr = torch.empty(M, dtype=torch.int32, device=self.dev)
+        extra = ()
+        if cons is not None:
+            held = self._constraint_tensors(cons)
+            extra = self._constraint_args(held)
+        self.g.conditional(l.data_ptr(), p.data_ptr(), M, W, seed, start, thr, it.data_ptr(), rows.data_ptr(),
+                           logw.data_ptr(), logq.data_ptr(), nt.data_ptr(), nr.data_ptr(), self._s(), *extra)
+        err = self.g.read_error()   # synchronises: the input tensors stay alive until the call is done
+        if err:
+            raise RuntimeError(f"HipGenerator.sample_conditional: device error word {err}")
+        return cpu_ref.pool_conditional(rows.cpu().numpy(), logw.cpu().numpy(), logq.cpu().numpy(), nt.cpu().numpy(),
+                                        nr.cpu().numpy(), N, R, W, self.cfg.eos)
+
 
 BeamResult = cpu_ref.BeamResult
 DistinctResult = cpu_ref.DistinctResult
+ConditionalResult = cpu_ref.ConditionalResult
 
 
 @dataclass

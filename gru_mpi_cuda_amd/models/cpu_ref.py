@@ -1977,3 +1977,358 @@ def sample_distinct_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: 
         rows, logq, G, state = nrows, s["logq"], s["G"], s["state"]
         cur = torch.from_numpy(s["next_id"].reshape(-1).astype(np.int64))
     return DistinctResult(rows, logq, G, ntok, (state != BEAM_DEAD).sum(1).astype(np.int32), cfg.eos)
+
+
+# --------------------------------------------------------------------------- conditional names
+# Sequential Monte Carlo over the constrained sampler (docs/DESIGN.md §4j).  The constrained sampler masks
+# the forbidden chars at every step and renormalises, so its law is q(row) = prod_l p(c_l | ...) / m_l with
+# m_l the model mass of the allowed set; the model's conditional is p(row | row in L) = p(row) / Z,
+# Z = P(row in L).  They differ by the per-row factor prod_l m_l, which the particles below carry as their
+# importance weight.  Per name W ordered slots (live / finished / dead as above), each with logw -- its
+# unnormalised log importance weight -- and logq, the log-probability of its row under the sampler along its
+# own lineage.  Slot 0 starts live with logw = logq = 0, the others dead.  Per step l:
+#   1. every row takes the model's step;
+#   2. per live slot b: y = x * inv_T, lse_all = max y + log sum exp(y - max y) over the vocabulary, lse_A the
+#      same over the allowed set A, logm_b = lse_A - lse_all, lq[c] = y[c] - lse_A.  Forced step: logm_b = 0,
+#      lq[prefix[l]] = 0.  Finished slot: logm_b = 0.  No constraint: lse_A is lse_all itself, logm_b == 0;
+#   3. the look-ahead weight u_b = logw_b + logm_b (known before the draw);
+#   4. over the slots that are not dead, in slot order: e_b = exp(u_b - max u), S = sum e, ESS = S S / sum e e.
+#      l == 0: fan-out, a_i = 0, logw_i = u_0.  Else iff ESS < thr W: systematic resampling with the step's
+#      uniform U, t_i = (i + U) / W * S, a_i = the first b whose inclusive running sum of e exceeds t_i (none:
+#      the last slot), logw_i = max u + log(S / W).  Else a_i = i, logw_i = u_i;
+#   5. new slot i carries a finished ancestor (row, length, logq unchanged) or draws one char of a live one:
+#      the first allowed c in index order whose running sum of exp(y - max_A y) exceeds r_i times the total
+#      (none: the last allowed c; forced: prefix[l]); logq_i = logq_a + lq_a[c]; finished iff c == eos;
+#   6. noise: Philox-4x32-10, key = seed, counter = (i, l, g lo, g hi), g = start + n: word 0 is r_i, word 1 of
+#      slot 0's block is U, both (2 (word >> 9) + 1) 2^-24.
+# Zhat = mean_i exp(logw_i) is an unbiased estimate of Z = P_T(row in L | prefix) at any W, and
+# mean_i exp(logw_i) f(row_i) of sum_{row in L} p_T(row | prefix) f(row).
+def smc_uniform(seed: int, g: np.ndarray, step: int, W: int) -> np.ndarray:
+    """Step 6's uniforms, float32 [len(g), W, 2] (exact, inside [2^-24, 1 - 2^-24]): [:, i, 0] is r_i,
+    [:, 0, 1] the step's U, for the names with global indices ``g`` at ``step``."""
+    g = np.asarray(g, dtype=np.uint64).reshape(-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.zeros((g.shape[0], W, 4), np.uint64)
+    ctr[:, :, 0] = np.arange(W, dtype=np.uint64)[None, :]
+    ctr[:, :, 1] = np.uint64(int(step) & 0xFFFFFFFF)
+    ctr[:, :, 2] = (g & _U32)[:, None]
+    ctr[:, :, 3] = (g >> np.uint64(32))[:, None]
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
+    words = philox4x32(ctr, key)[..., :2]
+    return ((2.0 * (words >> np.uint32(9)).astype(np.float64) + 1.0) * 2.0 ** -24).astype(np.float32)
+
+
+def _slot_cumsum(e: np.ndarray) -> np.ndarray:
+    """Inclusive running sums along the last axis in e's dtype, one addition at a time in index order."""
+    return np.cumsum(e, axis=-1, dtype=e.dtype)
+
+
+def smc_step(x: np.ndarray, logw: np.ndarray, logq: np.ndarray, state: np.ndarray, forced: np.ndarray, allowed,
+             inv_t: np.ndarray, noise: np.ndarray, thr: float, step: int, eos: int, sos: int,
+             mut: Optional[str] = None) -> Dict[str, np.ndarray]:
+    """Steps 2-5 for N names at once, in the dtype of ``x`` (float32: the device's operations in its order,
+    each rounded once, expf / logf as correctly rounded functions; the running sums one addition at a time
+    where the device scans, so this emulates the kernel, it does not reproduce its bits).  x [N, W, V]
+    logits, logw / logq / state [N, W], forced [N] (the forced char, -1 on a free step), allowed None / bool
+    [N, V] / bool [N, W, V], inv_t [N] float32, noise [N, W, 2] (``smc_uniform``).  Returns the new slots --
+    parent (-1: dead), chr (-1: a carry or dead), state, logw, logq, next_id -- resampled [N] bool, ess [N],
+    logm [N, W] (NaN: dead), lq [N, W, V] (a live row's y - lse_A, NaN outside the set), and what
+    models/smc_ref.py measures: q_ess (ESS / W), q_t [N, W, W] ((running sum_b - t_i) / S, NaN where no
+    resampling), q_r [N, W, 2] ((running sum - r_i total) / total at the chosen char and before it, NaN where
+    nothing is drawn), clear [N] (the smallest of |ESS - thr W| / W -- not counted where every weight is bitwise
+    equal -- |q_t| and |q_r|).  ``mut``: a planted defect
+    (models/smc_ref.py)."""
+    N, W, V = x.shape
+    dt = x.dtype.type
+    ninf = dt(-np.inf)
+    ni = np.arange(N)[:, None]
+    with np.errstate(all="ignore"):
+        y = x * inv_t.astype(x.dtype)[:, None, None]
+        mx = y.max(-1, keepdims=True)
+        se = _wave_sum(_rounded(np.exp, y - mx))
+        lse_all = (mx + _rounded(np.log, se))[..., 0]
+        if allowed is None:
+            A = np.ones((N, W, V), bool)
+            mxa, sea, lse_a = mx[..., 0], se[..., 0], lse_all
+        else:
+            A = np.asarray(allowed, bool)
+            A = np.broadcast_to(A[:, None, :] if A.ndim == 2 else A, (N, W, V))
+            mxa_k = np.where(A, y, ninf).max(-1, keepdims=True)
+            sea_k = _wave_sum(np.where(A, _rounded(np.exp, y - mxa_k), dt(0)))
+            mxa, sea = mxa_k[..., 0], sea_k[..., 0]
+            lse_a = mxa + _rounded(np.log, sea)
+        live, fin, dead = state == BEAM_LIVE, state == BEAM_FIN, state == BEAM_DEAD
+        isf = forced >= 0
+        credit = live & ~isf[:, None]
+        if mut == "forced_adds_logm":
+            credit = live
+        if mut == "finished_reweighted":
+            credit = credit | (fin & ~isf[:, None])
+        logm = np.where(credit, lse_a - lse_all, dt(0)).astype(x.dtype)
+        u = (logw + logm).astype(x.dtype)
+        lq = np.where(A & live[:, :, None], y - lse_a[:, :, None], dt(np.nan)).astype(x.dtype)
+        nd = ~dead
+        base = logw.astype(x.dtype) if mut == "resample_on_logw" else u   # what ESS and the ancestors are taken from
+        mu = np.where(nd, u, ninf).max(1)
+        mub = np.where(nd, base, ninf).max(1)
+        e = np.where(nd, _rounded(np.exp, base - mub[:, None]), dt(0)).astype(x.dtype)
+        cum = _slot_cumsum(e)
+        S = cum[:, -1]
+        Q = _slot_cumsum(e * e)[:, -1]
+        ess = (S * S) / Q
+        eu = np.where(nd, _rounded(np.exp, u - mu[:, None]), dt(0)).astype(x.dtype)
+        Su = _slot_cumsum(eu)[:, -1]
+        fan = step == 0
+        res = np.zeros(N, bool) if fan else (ess < dt(thr) * dt(W))
+        Uw = noise[:, :, 1].astype(x.dtype)
+        Ui = Uw if mut == "u_per_slot" else np.broadcast_to(Uw[:, :1], (N, W))
+        t = ((np.arange(W, dtype=x.dtype)[None, :] + Ui) / dt(W) * S[:, None]).astype(x.dtype)
+        over = (cum[:, None, :] > t[:, :, None]) & nd[:, None, :]       # [N, i, b]
+        last = (W - 1 - np.argmax(nd[:, ::-1], 1))
+        a_res = np.where(over.any(-1), np.argmax(over, -1), last[:, None])
+        ident = np.broadcast_to(np.arange(W)[None, :], (N, W))
+        if fan:
+            anc = np.zeros((N, W), np.int64)
+            nlogw = np.broadcast_to(u[:, :1], (N, W)).astype(x.dtype)
+        else:
+            anc = np.where(res[:, None], a_res, ident)
+            eq = (mu + _rounded(np.log, Su / dt(W)))[:, None]
+            if mut == "weights_not_equalised":
+                eq = u[ni, anc]
+            nlogw = np.where(res[:, None], eq, u).astype(x.dtype)
+        a_live, a_fin = live[ni, anc], fin[ni, anc]
+        ya, Aa = y[ni, anc], A[ni, anc]                                  # [N, W, V]
+        ex = np.where(Aa, _rounded(np.exp, ya - mxa[ni, anc][:, :, None]), dt(0)).astype(x.dtype)
+        run = _slot_cumsum(ex)
+        tot = sea[ni, anc]
+        target = (noise[:, :, 0].astype(x.dtype) * tot).astype(x.dtype)
+        hit = (run > target[:, :, None]) & Aa
+        lastc = V - 1 - np.argmax(Aa[:, :, ::-1], -1)
+        c = np.where(hit.any(-1), np.argmax(hit, -1), lastc)
+        c = np.where(isf[:, None], np.maximum(forced, 0)[:, None], c)
+        draws = a_live & ~isf[:, None]
+        dl = np.where(draws, np.take_along_axis(ya, c[:, :, None], -1)[..., 0] - lse_a[ni, anc], dt(0)).astype(x.dtype)
+        nlogq = np.where(a_live | a_fin, logq[ni, anc] + np.where(a_live, dl, dt(0)), ninf).astype(x.dtype)
+        nlogw = np.where(a_live | a_fin, nlogw, ninf).astype(x.dtype)
+        parent = np.where(a_live | a_fin, anc, -1).astype(np.int32)
+        chrs = np.where(a_live, c, -1).astype(np.int32)
+        nstate = np.where(a_fin | (a_live & (c == eos)), BEAM_FIN, np.where(a_live, BEAM_LIVE, BEAM_DEAD)).astype(np.int32)
+        nxt = np.where(nstate == BEAM_LIVE, c, sos).astype(np.int32)
+        # what the guard is made of (float64 quotients of this precision's values)
+        f8 = np.float64
+        q_ess = ess.astype(f8) / W
+        q_t = np.where(res[:, None, None] & nd[:, None, :], (cum[:, None, :].astype(f8) - t[:, :, None].astype(f8)) /
+                       S.astype(f8)[:, None, None], np.nan)
+        run_c = np.take_along_axis(run, c[:, :, None], -1)[..., 0].astype(f8)
+        ex_c = np.take_along_axis(ex, c[:, :, None], -1)[..., 0].astype(f8)
+        q_r = np.stack([(run_c - target.astype(f8)) / tot.astype(f8), (run_c - ex_c - target.astype(f8)) / tot.astype(f8)], -1)
+        q_r = np.where(draws[:, :, None], q_r, np.nan)
+        # (weights that are all bitwise equal give e = 1, S = Q = the slot count and ESS exactly, in any precision:
+        # that decision carries no rounding)
+        flat = (np.where(nd, base, mub[:, None]) == mub[:, None]).all(1)
+        c_ess = np.full(N, np.inf) if fan else np.where(flat, np.inf, np.abs(ess.astype(f8) - f8(dt(thr)) * W) / W)
+        c_t = np.where(np.isnan(q_t), np.inf, np.abs(q_t)).reshape(N, -1).min(1)
+        c_r = np.where(np.isnan(q_r), np.inf, np.abs(q_r)).reshape(N, -1).min(1)
+        clear = np.minimum(np.minimum(np.where(np.isnan(c_ess), np.inf, c_ess), c_t), c_r)
+    counted = res | (np.ones(N, bool) if (mut == "fanout_counted" and fan) else np.zeros(N, bool))
+    return dict(parent=parent, chr=chrs, state=nstate, logw=nlogw, logq=nlogq, next_id=nxt, resampled=counted,
+                ess=ess.astype(x.dtype), logm=np.where(dead, dt(np.nan), logm).astype(x.dtype), lq=lq, q_ess=q_ess, q_t=q_t,
+                q_r=q_r, clear=clear)
+
+
+class ConditionalResult:
+    """``HipGenerator.sample_conditional`` / ``cpu_ref.sample_conditional`` output for N prefixes of R runs
+    of W particles, pooled per prefix (P = R W, run r in columns r W .. r W + W - 1):
+    rows [N, P, MAX_LEN+1] uint8 (the ``generate`` format), log_weight [N, P] (the unnormalised log
+    importance weights), logq [N, P] (the rows' log-probability under the constrained sampler), n_tok [N, P]
+    int32, n_resampled [N, R] int32, log_z [N] float64 (the log-mean-exp of the pooled log_weight: the log of
+    the estimate of Z = P(the rule | prefix) under the model at the temperature), z_stderr [N] (the standard
+    error of exp(log_z) over the runs, NaN at R = 1; like exp(log_z) it is 0 where Z lies below the smallest
+    double -- compare z_stderr / exp(log_z) through log_z then), ess [N] (the pool's effective sample size).
+
+    ``exp(log_z)`` is an UNBIASED estimate of Z at any width and any number of runs.  ``weights``,
+    ``expectation`` and ``draw`` normalise the weights by their own sum: they are consistent, with a bias of
+    order 1 / particles -- use more runs, not a single row, when that matters."""
+
+    def __init__(self, rows, log_weight, logq, n_tok, n_resampled, eos: int = 0):
+        self.rows, self.log_weight, self.logq, self.n_tok, self.n_resampled, self.eos = rows, log_weight, logq, n_tok, n_resampled, eos
+        N, P = log_weight.shape
+        R = max(n_resampled.shape[1], 1) if n_resampled.ndim == 2 else 1
+        lw = np.asarray(log_weight, np.float64)
+        with np.errstate(all="ignore"):
+            m = lw.max(1, keepdims=True) if P else np.zeros((N, 1))
+            m = np.where(np.isfinite(m), m, 0.0)
+            w = np.exp(lw - m)
+            s = w.sum(1)
+            self.log_z = (m[:, 0] + np.log(s / max(P, 1)))
+            self.ess = np.where(s > 0, s * s / np.maximum((w * w).sum(1), 1e-300), 0.0)
+            # the runs' means relative to the pooled maximum, rescaled last: a rule of probability far below the
+            # smallest double still has the spread of its runs taken from non-zero numbers (the product underflows
+            # only where exp(log_z) itself does)
+            zr = w.reshape(N, R, P // R).mean(2) if P else np.zeros((N, R))
+            self.z_stderr = np.exp(m[:, 0]) * zr.std(1, ddof=1) / math.sqrt(R) if R > 1 else np.full(N, np.nan)
+
+    def names(self) -> List[List[str]]:
+        """Per prefix the particles' names in pool order (the EOS byte dropped)."""
+        full = np.full(self.rows.shape[0], self.rows.shape[1], np.int32)
+        return BeamResult(self.rows, self.logq, self.n_tok, full, self.eos).names()
+
+    def weights(self) -> np.ndarray:
+        """[N, P] float64, the weights normalised per prefix (zeros where every weight is zero)."""
+        lw = np.asarray(self.log_weight, np.float64)
+        with np.errstate(all="ignore"):
+            m = lw.max(1, keepdims=True)
+            w = np.exp(lw - np.where(np.isfinite(m), m, 0.0))
+            s = w.sum(1, keepdims=True)
+            return np.where(s > 0, w / np.where(s > 0, s, 1.0), 0.0)
+
+    def expectation(self, f) -> np.ndarray:
+        """[N] self-normalised estimates of E[f(name) | the rule, prefix]; ``f`` maps a name (str) to a number.
+        Consistent, bias O(1 / particles)."""
+        w = self.weights()
+        return np.array([sum(wk * float(f(nm)) for wk, nm in zip(w[n], names)) for n, names in enumerate(self.names())])
+
+    def draw(self, k: int, seed: int = 0) -> List[List[str]]:
+        """Per prefix k names drawn from the pool with probability proportional to the weights (multinomial
+        resampling on the host): approximate draws from the model's conditional, bias O(1 / particles)."""
+        rng = np.random.default_rng(seed)
+        w = self.weights()
+        out = []
+        for n, names in enumerate(self.names()):
+            if not w[n].sum() > 0:
+                out.append([])
+                continue
+            out.append([names[j] for j in rng.choice(len(names), size=int(k), p=w[n] / w[n].sum())])
+        return out
+
+
+def conditional_inputs(cfg: GRUConfig, prefix=None, width: int = 16, count: Optional[int] = None, runs: int = 1,
+                       seed: int = 0, start: int = 0, temperature=None, ess_threshold: float = 0.5, **excluded):
+    """Validated (prefix rows [N R], plen [N R], inv_t [N R] float32, seed, start, thr, N, R) of
+    ``sample_conditional``: every prefix repeated ``runs`` times, run r of prefix n at the global index
+    start + n R + r; thr is ess_threshold rounded to float32.  ValueError for what ``distinct_inputs`` rejects, runs < 1, a threshold outside [0, 1]."""
+    for k, v in excluded.items():
+        if k not in ("top_k", "top_p", "logit_bias", "presence_penalty", "frequency_penalty", "soft"):
+            raise TypeError(f"sample_conditional: unexpected keyword {k!r}")
+        if v is not None:
+            raise ValueError(f"sample_conditional does not take {k}: the target is the model's distribution at the "
+                             "temperature, conditioned on prefix and constraints alone")
+    if isinstance(runs, bool) or int(runs) != runs or runs < 1:
+        raise ValueError(f"runs must be an integer >= 1, got {runs!r}")
+    thr = float(ess_threshold)
+    if not 0.0 <= thr <= 1.0:
+        raise ValueError(f"ess_threshold must lie in [0, 1], got {ess_threshold!r}")
+    thr = float(np.float32(thr))      # the value the device reads: the rule in any precision compares against it
+    try:
+        pre, plen, inv, seed, start = distinct_inputs(cfg, prefix, width, count, seed, start, temperature)
+    except ValueError as e:
+        raise ValueError(str(e).replace("sample_distinct", "sample_conditional")) from None
+    N, R = pre.shape[0], int(runs)
+    if start + N * R > 2 ** 64:
+        raise ValueError("start + count * runs must stay below 2^64")
+    return np.repeat(pre, R, 0), np.repeat(plen, R, 0), np.repeat(inv, R, 0), seed, start, thr, N, R
+
+
+def conditional_constraints(cfg: GRUConfig, N: int, R: int, constraints):
+    """``as_constraints`` for the N R names of a call.  A dict's values are one for every name or one per PREFIX
+    (N of them, as in ``generate``): per-prefix values are repeated for the prefix's R runs.  A built
+    Constraints / Automaton object holds one entry per name and serves R = 1 only."""
+    if constraints is None:
+        return None
+    if not isinstance(constraints, dict):
+        if R > 1:
+            raise ValueError("sample_conditional with runs > 1 takes constraints as a dict of keywords")
+        return as_constraints(cfg, N, constraints)
+    kw = dict(constraints)
+    if R > 1:
+        for k, v in kw.items():
+            if v is None or isinstance(v, (str, bytes)) or np.ndim(v) == 0:
+                continue
+            if k == "exclude" and all(isinstance(x, (str, bytes)) for x in v):      # one list of names for everybody
+                continue
+            if len(v) != N:
+                raise ValueError(f"constraints[{k!r}]: one value or {N} values (one per prefix) expected, got {len(v)}")
+            kw[k] = [x for x in v for _ in range(R)]
+    return as_constraints(cfg, N * R, kw)
+
+
+def pool_conditional(rows, logw, logq, ntok, nres, N: int, R: int, W: int, eos: int) -> ConditionalResult:
+    """The device's / the rule's [N R, W] outputs pooled per prefix."""
+    return ConditionalResult(rows.reshape(N, R * W, rows.shape[-1]), logw.reshape(N, R * W), logq.reshape(N, R * W),
+                             ntok.reshape(N, R * W), nres.reshape(N, R), eos)
+
+
+def sample_conditional(params: Params, cfg: GRUConfig, prefix=None, width: int = 16, count: Optional[int] = None, *,
+                       runs: int = 1, seed: int = 0, start: int = 0, temperature=None, constraints=None,
+                       ess_threshold: float = 0.5, **excluded) -> ConditionalResult:
+    """``runs`` independent systems of ``width`` weighted particles per prefix (the rule above), in the dtype
+    of ``params`` (fp64 params: the oracle; the CPU path of ``cli conditional``)."""
+    pre, plen, inv, seed, start, thr, N, R = conditional_inputs(cfg, prefix, width, count, runs, seed, start, temperature,
+                                                                ess_threshold, **excluded)
+    cons = conditional_constraints(cfg, N, R, constraints)
+    check_prefix_allowed(cons, pre, plen)
+    rows, logw, logq, ntok, nres = sample_conditional_rule(params, cfg, pre, plen, int(width), seed, start, inv, thr, cons)
+    return pool_conditional(rows, logw, logq, ntok, nres, N, R, int(width), cfg.eos)
+
+
+def sample_conditional_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, seed: int,
+                            start: int, inv_t: np.ndarray, thr: float, cons=None, mut: Optional[str] = None,
+                            trace: Optional[list] = None):
+    """The rule itself on validated inputs: (rows [M, W, ML+1], logw, logq [M, W], n_tok [M, W], n_resampled
+    [M]) for the M names given.  ``trace``: a list that receives every step's ``smc_step`` output
+    (models/smc_ref.py); ``mut``: a planted defect (there too)."""
+    N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
+    dt = params["fc.weight"].dtype
+    npdt = np.float64 if dt == torch.float64 else np.float32
+    rows = np.zeros((N, W, ML + 1), np.uint8)
+    logw = np.full((N, W), -np.inf, npdt)
+    logq = np.full((N, W), -np.inf, npdt)
+    state = np.full((N, W), BEAM_DEAD, np.int32)
+    ntok = np.zeros((N, W), np.int32)
+    nres = np.zeros(N, np.int32)
+    if N == 0:
+        return rows, logw, logq, ntok, nres
+    logw[:, 0] = logq[:, 0] = 0
+    state[:, 0] = BEAM_LIVE
+    hs = [torch.zeros(N * W, H, dtype=dt) for _ in range(cfg.layers)]
+    cur = torch.full((N * W,), cfg.sos, dtype=torch.int64)
+    aut = cons if isinstance(cons, Automaton) else None
+    if aut is not None:
+        alines, astate = aut.lines(), np.zeros((N, W), np.int64)
+        astate[:, 0] = aut.start
+    gidx = np.arange(N, dtype=np.uint64) + np.uint64(0 if mut == "counter_local_index" else start)
+    ni = np.arange(N)[:, None]
+    for l in range(ML):
+        inp = params["embedding"][cur]
+        new = []
+        for k in range(cfg.layers):
+            gi = inp @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
+            gh = hs[k] @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
+            hk, _ = _gates(gi, gh, hs[k])
+            new.append(hk)
+            inp = hk
+        logits = inp @ params["fc.weight"].T + params["fc.bias"]
+        if dt != torch.float64:
+            logits = logits.to(torch.float32)
+        x = logits.numpy().reshape(N, W, V)
+        allowed = None if cons is None else (alines[astate] if aut is not None else cons.allowed(l))
+        forced = np.where(plen > l, pre[:, l].astype(np.int64), -1)
+        noise = smc_uniform(seed, gidx, 0 if mut == "counter_without_step" else l, W)
+        s = smc_step(x, logw, logq, state, forced, allowed, inv_t, noise, thr, l, cfg.eos, cfg.sos, mut)
+        if trace is not None:
+            trace.append(s)
+        par = np.maximum(s["parent"], 0)
+        alive = s["parent"] >= 0
+        app = s["chr"] >= 0
+        nrows = np.where(alive[:, :, None], rows[ni, par], 0).astype(np.uint8)
+        nrows[:, :, l] = np.where(app, s["chr"], nrows[:, :, l])
+        ntok = np.where(alive, np.where(app, l + 1, ntok[ni, par]), 0).astype(np.int32)
+        if aut is not None:   # (a carried or dead slot sits in state 0)
+            astate = np.where(app, aut.nxt[astate[ni, par], np.maximum(s["chr"], 0)].astype(np.int64), 0)
+        gather = torch.from_numpy((ni * W + par).reshape(-1).astype(np.int64))
+        dead = torch.from_numpy(~alive.reshape(-1))
+        hs = [h[gather].masked_fill(dead[:, None], 0) for h in new]
+        rows, logw, logq, state = nrows, s["logw"], s["logq"], s["state"]
+        nres = nres + s["resampled"].astype(np.int32)
+        cur = torch.from_numpy(s["next_id"].reshape(-1).astype(np.int64))
+    return rows, logw, logq, ntok, nres
