@@ -128,6 +128,10 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
     }
   }
   size_t o_pP = seq_[0].fuse_p ? R((size_t)seq_[0].nrb * V * 3 * H * 4) : 0;
+  // the one-launch forward + backward (gru_fb_one): two flag sets, the launch counter, the forward's ring
+  const bool fb_mem = L == 1 && persist_fwd_ && seq_[0].bwd;
+  size_t o_fbf = fb_mem ? R((size_t)4 * seq_flag_words(H, B) * 4) : 0, o_fbl = fb_mem ? R(64) : 0;
+  size_t o_xf = fb_mem ? R((size_t)T * B * H * 2) : 0;
   // per-step backward on the split-K LDS kernel: partial tiles + monotonic arrival counters
   // (shared by all layers: their step kernels run one after another on one stream)
   int sk = 0;
@@ -153,6 +157,9 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
     seq_[l].dbih_part = (seq_[l].bwd || seq_[l].big) ? arena_.get<float>(o_pbi[l]) : nullptr;
   }
   dP_part_ = seq_[0].fuse_p ? arena_.get<float>(o_pP) : nullptr;
+  fb_flags_ = fb_mem ? arena_.get<unsigned>(o_fbf) : nullptr;
+  fb_launches_ = fb_mem ? arena_.get<unsigned>(o_fbl) : nullptr;
+  xbuf_fwd_ = fb_mem ? arena_.get<u16>(o_xf) : nullptr;
   bpart_ = any_big ? arena_.get<float>(o_bp) : nullptr;
   sk_part_ = sk ? arena_.get<float>(o_skp) : nullptr;
   sk_cnt_ = sk ? arena_.get<unsigned>(o_skc) : nullptr;
@@ -236,6 +243,9 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
                  seq_[0].s16 && seq_[0].HF && step_lds_variants().bwd_tail && d_.V % seq_[0].nrb == 0 &&
                  (d_.V / seq_[0].nrb) % 8 == 0 && gru_bwd_seq_tail_supported(d_.H, Bp_, d_.V);
   bwd_tail_ = bwd_tail_ok_ && use_graph_ && o_.clip <= 0.f;   // what a single-GPU step() will take (record_fb_seq)
+  fb_one_ok_ = fc_tail_ && bwd_tail_ok_ && fb_flags_ && d_.T >= 2 && step_lds_variants().fb_one &&
+               gru_fb_one_supported(d_.H, Bp_, d_.V);
+  fb_one_ = fb_one_ok_ && bwd_tail_;
 }
 
 Trainer::~Trainer() {
@@ -769,7 +779,7 @@ void Trainer::optimizer_step(hipStream_t s) {
 void Trainer::set_comm(RcclComm* c, const std::vector<std::pair<long, long>>& buckets, long min_bucket_floats) {
   comm_ = c;
   if (!c) shard_opt_ = false;
-  if (c) bwd_tail_ = false;   // data-parallel steps keep the reduce launch (record_fb_seq)
+  if (c) bwd_tail_ = fb_one_ = false;   // data-parallel steps keep the reduce launch (record_fb_seq)
   buckets_ = buckets;
   min_bucket_ = std::max(1L, min_bucket_floats);
   // the overlapped path relies on the readiness order of the flat layout (models/params.py)

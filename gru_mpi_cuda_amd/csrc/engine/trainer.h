@@ -50,7 +50,7 @@ class Trainer {
   int get_step();                                       // optimiser step counter (device)
   void set_step(int v);                                 // for resume
   void set_lr(float lr);
-  void set_use_graph(bool g) { use_graph_ = g; if (!g) bwd_tail_ = false; }   // (eager steps keep the reduce launch)
+  void set_use_graph(bool g) { use_graph_ = g; if (!g) bwd_tail_ = fb_one_ = false; }   // (eager steps keep the reduce launch)
   // Truncated BPTT over a continuous stream: with carry on, each step starts from
   // the previous step's final hidden state (HS[T] -> HS[0] copies at the head of the step graph;
   // no gradient flows into it).  reset_hidden zeroes the carried state.
@@ -255,6 +255,16 @@ class Trainer {
   // exactly these three jobs).  bwd_tail_: what step() takes -- predicted from the options at construction,
   // then what the last recorded step did (plan()).
   bool bwd_tail_ok_ = false, bwd_tail_ = false;
+  // that step with fc_tail_ and bwd_tail_ both taken, T >= 2, no carried state: the persistent forward and
+  // backward as ONE launch (gru_fb_one, StepLdsVariants::fb_one).  fb_one_ok_: shape, plan and co-residency
+  // allow it (constructor); record_fb_seq decides per recording; fb_one_: predicted at construction, then
+  // what the last recorded step did (plan()).  The launch has two flag sets of its own (a forward and a
+  // backward block each; the parity of the device counter fb_launches_ picks one, the launch zeroes the
+  // other) and the forward ring a region of its own (xbuf_fwd_): inside one launch the two rings are live
+  // at the same time.
+  bool fb_one_ok_ = false, fb_one_ = false;
+  unsigned *fb_flags_ = nullptr, *fb_launches_ = nullptr;
+  u16* xbuf_fwd_ = nullptr;
   bool in_step_ = false;       // record_fb_seq is recording a step (record_step_body), not forward_backward()
   bool dy_in_bwd_ = false;     // the top layer's large-H backward computes dy = dl · W_fc itself (big_dy)
   bool fwd_wave_ = false;      // layer pairs (0,1), (2,3).. forward as one wavefront launch (gru_fwd_seq2)

@@ -188,6 +188,24 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
   auto fc_fuse_dh = [&](FcXentArgs& f) {   // dy_top = dlogits · W_fc inside the head (dlogits never leave LDS)
     f.dl = nullptr; f.WT = WfcT; f.dy = Ls_[L - 1].dy; f.Wf = WfcF; f.WTf = WfcTF;
   };
+  // The one-launch forward + backward (gru_fb_one): where the step is a candidate the forward is not
+  // recorded at its place but held, and with it the dW_fc product where that is a launch of its own between
+  // the two (it reads only what the forward wrote and nothing before Adam reads its slabs).  A backward
+  // that takes its tail then goes out with the forward as one launch, the dW_fc product behind it; any
+  // other backward is preceded by what was held, in order: such a step records exactly the launches it
+  // always did.
+  const bool fb_cand = fb_one_ok_ && in_step_ && !dp && !carry_ && L == 1 && T >= 2 && step_lds_variants().fb_one;
+  bool fwd_held = false;
+  SeqFwdArgs held_a;
+  FcXentArgs held_f;
+  bool wfc_held = false;
+  GemmArgs held_w;
+  auto flush_held_fwd = [&]() {
+    if (fwd_held) gru_fwd_seq_tail(held_a, held_f, s);
+    if (wfc_held) gemm_nt(held_w, s);
+    fwd_held = wfc_held = false;
+  };
+  bool fb_one = false;
   for (int l = 0; l < L; ++l) {
     Layer& y = Ls_[l];
     if (l > 0) {
@@ -220,7 +238,8 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       // the fused FC head's blocks as the tail of this launch (no fc_xent node below)
       FcXentArgs f = fc_args();
       fc_fuse_dh(f);
-      gru_fwd_seq_tail(fwd_args(l), f, s);
+      if (fb_cand) { held_a = fwd_args(l); held_f = f; fwd_held = true; }
+      else gru_fwd_seq_tail(fwd_args(l), f, s);
     } else if (persist_fwd_) {
       gru_fwd_seq(fwd_args(l), s);
     } else {
@@ -303,6 +322,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     fc_held_on_ = (dp && dp_pipe_on()) ||
                   (!dp && defer_slabs_ && sp <= 8 && w.algo == 3 && step_lds_variants().dwfc_group);
     if (fc_held_on_) fc_held_ = w;
+    else if (fwd_held) { held_w = w; wfc_held = true; }
     else gemm_nt(w, s);
     tail.add(slab_fc2_, sp, (long)V * H, G("fc.weight"));
     tail.add(rs_fc2_, sp, V, G("fc.bias"));
@@ -314,6 +334,9 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
   bool bwd_tail = bwd_tail_ok_ && !dp && defer_slabs_ && seq_[0].nrb <= kDeferMaxSplits;
   for (int k2 = 0; k2 < tail.n; ++k2) bwd_tail = bwd_tail && tail.job[k2].splits <= kDeferMaxSplits;
   if (in_step_) bwd_tail_ = bwd_tail;
+  if (!bwd_tail || !seq_[0].bwd) flush_held_fwd();
+  fb_one = fwd_held;
+  if (in_step_) fb_one_ = fb_one;
   // ------------------------------------------------------------------ backward (BPTT)
   for (int l = L - 1; l >= 0; --l) {
     Layer& y = Ls_[l];
@@ -338,7 +361,17 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       if (bwd_tail && l == 0) {
         BwdTailArgs t;
         t.dP_bf = dP_bf_; t.dPT_bf = dPT_bf_; t.loss_part = loss_part_; t.nloss = nloss_; t.loss = loss_; t.step = step_;
-        gru_bwd_seq_tail(a, t, s);
+        if (fb_one) {
+          // both phases on the launch's own flag sets (forward block, then backward block, per set) and
+          // the forward's ring in its own region; neither phase zeroes the stand-alone kernels' blocks
+          FbOneX x;
+          x.set_words = 2 * fw; x.launches = fb_launches_;
+          held_a.cnt = fb_flags_; held_a.zero_next = nullptr; held_a.zero_words = 0; held_a.xch = xbuf_fwd_;
+          a.cnt = fb_flags_ + fw; a.zero_next = nullptr; a.zero_words = 0;
+          gru_fb_one(held_a, held_f, a, t, x, s);
+          if (wfc_held) gemm_nt(held_w, s);
+          fwd_held = wfc_held = false;
+        } else gru_bwd_seq_tail(a, t, s);
       } else if (q.rows16) gru_bwd_seq16(a, s);
       else gru_bwd_seq(a, s);
     } else if (q.big) {
@@ -618,6 +651,7 @@ std::string Trainer::plan() const {
   if (fc_tail_) p += " head=fwd-tail";
   p += overlap_ ? " overlap(chunks=" + std::to_string(C_) + ")" : " serial";
   if (bwd_tail_) p += " dP=bwd-tail";
+  if (fb_one_ && fc_tail_ && bwd_tail_) p += " fb=one-launch";
   return p;
 }
 

@@ -56,6 +56,7 @@ struct FcXPlain {
   DEV bool sc1() const { return false; }
   DEV void ready() const {}
   DEV int tid() const { return (int)threadIdx.x; }
+  DEV void store_loss(float* p, float v) const { *p = v; }
 };
 
 // Policy XP:
@@ -65,7 +66,9 @@ struct FcXPlain {
 //   sc1()          X with L1-bypassing sc1 loads (X handed off by other workgroups inside the same
 //                  launch: the tail) or plain ones (X complete before the launch);
 //   tid()          the thread index (the tail hands it over opaque, so that nothing of the block is
-//                  computed ahead of the step loop it follows).
+//                  computed ahead of the step loop it follows);
+//   store_loss()   the block's loss partial: a plain store where its reader is a later launch, write-through
+//                  where workgroup 0 of the same launch sums the partials (gru_fb_one_kernel).
 // DH = true (every default plan): dH = dl · W_fc fused, the dlogits never leave LDS.  DH = false
 // writes the row-major bf16 dl instead and leaves dH to a GEMM (a round-2 plan computed dy inside
 // the backward sequence kernel from it: fc_xent 16.3 -> 11.4 us but the backward +7-10 us,
@@ -269,7 +272,7 @@ DEV void fc_xent_v256_block(const FcXentArgs& a, float* smem, int block, const X
   if (tid == 0) {
     float t = 0.f;
     for (int i = 0; i < FROWS; ++i) t += lrow[i];
-    a.loss_part[block] = t;
+    xp.store_loss(a.loss_part + block, t);
   }
   STAMP();
 }

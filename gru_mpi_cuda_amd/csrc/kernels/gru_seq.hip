@@ -386,6 +386,7 @@ struct FcXTail {
   unsigned epoch;
   unsigned* err;
   DEV bool sc1() const { return true; }
+  DEV void store_loss(float* p, float v) const { *p = v; }
   DEV void ready() const { wait_flags_keep(fl, nunit, epoch, err); }
   // opaque: every per-thread address of the block is a function of the thread index alone, and the
   // compiler computed them ahead of the step loop, where their registers pushed scalars into VGPR lanes
@@ -410,7 +411,15 @@ struct FcXTail {
 // want checking again (-Rpass-analysis=kernel-resource-usage, the loop's ISA) at a compiler upgrade.
 static_assert(std::is_trivially_copyable<SeqFwdArgs>::value && std::is_trivially_copyable<FcXentArgs>::value,
               "the tail reads both argument structs back from the kernel-argument segment byte for byte");
-DEV void fwd_fc_tail(bool loc, unsigned char* smem) {
+// The same policy inside gru_fb_one_kernel: the loss partials reach workgroup 0 -- any XCD -- at the end
+// of the same launch, so they leave write-through (an agent-scope store: sc1) and are read back sc1.
+struct FcXTailOne : FcXTail {
+  DEV void store_loss(float* p, float v) const { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+};
+
+// ONE (gru_fb_one_kernel): the flag lines are those of the launch's flag set, foff words behind a.cnt.
+template <bool ONE>
+DEV void fwd_fc_tail(bool loc, unsigned char* smem, unsigned foff) {
   typedef const __attribute__((address_space(4))) char* kptr_t;
   kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(kp));
@@ -418,8 +427,9 @@ DEV void fwd_fc_tail(bool loc, unsigned char* smem) {
   constexpr size_t fc_off = (sizeof(SeqFwdArgs) + alignof(FcXentArgs) - 1) / alignof(FcXentArgs) * alignof(FcXentArgs);
   const int T = a.T, nrb = a.Bp / 32, nunit = a.H / 16;
   const int ut = seq_unit_tile(nrb), rbk = seq_row_block(nrb);
-  unsigned* const fl = a.cnt + (size_t)rbk * nunit * kFlagStride;   // the row block's producer lines
-  const FcXTail xp{fl, nunit, (unsigned)(T + 1), a.err};
+  unsigned* const fl = a.cnt + (ONE ? (size_t)foff : (size_t)0) + (size_t)rbk * nunit * kFlagStride;   // the row block's producer lines
+  const FcXTail xb{fl, nunit, (unsigned)(T + 1), a.err};
+  const typename std::conditional<ONE, FcXTailOne, FcXTail>::type xp{xb};
   const int tid = xp.tid();
   // h of the last step in HSb -> epoch T + 1.  Only wave 0 wrote HSb, and each of its publish drains
   // covered the step before, so its own drain is the only one needed; the other waves go on to their
@@ -460,221 +470,8 @@ __global__ void __launch_bounds__(512, WPE) gru_fwd_seq_kernel(SeqFwdArgs a, typ
                              void (*)(SeqFwdArgs, typename FwdFcArg<TAIL>::type)>::value,
                 "gru_fwd_seq_kernel takes (SeqFwdArgs, FC arguments) and nothing else");
   __shared__ __attribute__((aligned(16))) unsigned char smem[TAIL ? kFwdTailLds : FC ? (kFwdFcLds > kFwdRecLds ? kFwdFcLds : kFwdRecLds) : kFwdRecLds];
-  auto& part = *reinterpret_cast<float(*)[8][6][256]>(smem);
-  // padded rows (48 B / 80 B, still 16-B aligned for the vector reads): the epilogue's per-item
-  // u16 writes -- rows 4 apart within a wave -- land in distinct banks (unpadded: 2-way / 4-way)
-  auto& stg = *reinterpret_cast<u16(*)[32][24]>(smem + sizeof(float) * 8 * 6 * 256);
-  auto& stgT = *reinterpret_cast<u16(*)[16][40]>(smem + sizeof(float) * 8 * 6 * 256 + sizeof(u16) * 32 * 24);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int H = a.H, Bp = a.Bp, T = a.T;
-  const int nrb = Bp / 32;
-  const unsigned nunit = (unsigned)(H / 16);
-  if constexpr (FC) {
-    const int nrec = (int)nunit * nrb;
-    if ((int)blockIdx.x >= nrec) {
-      zero_next_flags(a.zero_next, a.zero_words);
-      if constexpr (NKW * 128 == 512 && RS == 2) fwd_fc_consumer<512>(a, fc, smem, (int)blockIdx.x - nrec);
-      return;
-    }
-  }
-  // flag lines per row block: its H/16 producers (+ its FC consumers)
-  const size_t rb_lines = nunit + (FC ? kFcCons : 0);
-  // (FC: the grid also holds the consumers, so the block -> tile map takes the recurrence's own count)
-  const int ut = FC ? seq_unit_tile_n(nrb, (int)nunit * nrb) : seq_unit_tile(nrb);
-  const int j0 = ut * 16, rbk = FC ? seq_row_block_n(nrb, (int)nunit * nrb) : seq_row_block(nrb), b0 = rbk * 32;
-  const int lr = lane & 15, lk = 8 * (lane >> 4);
-  constexpr int NR = RS == 2 ? 1 : 2;           // row tiles per wave
-  const int rt = RS == 2 ? (w >> 2) : 0;        // first row tile of this wave
-  const int k0 = (RS == 2 ? (w & 3) : w) * NKW * 32;
-
-  bf16x8 bw[NKW][3];   // this wave's K-slice of W_h{r,z,n} for the 16 units, resident all sequence
-#pragma unroll
-  for (int kk = 0; kk < NKW; ++kk)
-#pragma unroll
-    for (int g = 0; g < 3; ++g) bw[kk][g] = ld8(a.Whh + (size_t)(g * H + j0 + lr) * H + k0 + kk * 32 + lk);
-
-  // this thread's epilogue item (row, unit) -- one per thread with 512 threads
-  const int rb = tid >> 8, reg = (tid >> 6) & 3, ln = tid & 63;
-  const int row = rb * 16 + (ln >> 4) * 4 + reg, col = ln & 15;
-  const int b = b0 + row, j = j0 + col;
-  float bh[3];
-#pragma unroll
-  for (int g = 0; g < 3; ++g) bh[g] = a.bhh[g * H + j];
-  float hp = a.h0 ? a.h0[(size_t)b * H + j] : 0.f;
-  const rsrc_t rH = make_rsrc(a.HSb, (unsigned)((size_t)(T + 1) * Bp * H * 2));
-  const rsrc_t rX = make_rsrc(a.xch, (unsigned)((size_t)T * Bp * H * 2));
-  // exchange ring: the slot of step t is reused at step t + xr.  Safe for xr >= 2: a producer writes
-  // step t only after every producer of its row block published step t - 1, i.e. finished reading
-  // the tiles of step t - 2 -- the ones the write replaces when xr = 2.
-  const int xr = a.xring >= 2 ? a.xring : T;
-  const unsigned sv_bytes = (unsigned)((size_t)T * Bp * H * 4);   // < 4 GB: checked on the host
-  const rsrc_t rHSf = make_rsrc(a.HSf, sv_bytes + (unsigned)(Bp * H * 4));
-  const rsrc_t rSr = make_rsrc(a.sr, a.sr ? sv_bytes : 0u), rSz = make_rsrc(a.sz, a.sz ? sv_bytes : 0u);
-  const rsrc_t rSn = make_rsrc(a.sn, a.sn ? sv_bytes : 0u), rSg = make_rsrc(a.sghn, a.sghn ? sv_bytes : 0u);
-  const rsrc_t rS16 = make_rsrc(a.s16, a.s16 ? 2u * sv_bytes : 0u);   // < 4 GB: checked on the host
-  const unsigned sv_lane = (unsigned)((b * H + j) * 4);
-  stamp(a.dbg, T + 1, 0);   // prologue stamps in the (unused) step slot T + 1
-  zero_next_flags(a.zero_next, a.zero_words);
-  // (probe 3: consumers leave before the census, which then covers the producers only)
-  int cens = (int)rb_lines;
-  if constexpr (FC) {
-    if ((fc.probe & 7) == 3) cens = (int)nunit;
-    if (fc.probe & 8) __builtin_amdgcn_s_setprio(2);
-  }
-  const bool loc = a.allow_local && row_block_local(a.cnt + (size_t)rbk * rb_lines * kFlagStride, ut, cens, a.err);
-  stamp(a.dbg, T + 1, 4);
-
-  // the input projection of step t, gathered one step ahead, after the publish (its latency off
-  // the critical path; issued before wave 0's drain it would be part of it: vmcnt retires in order).
-  // The char id it needs is loaded one step earlier still, so the gather never waits on an id load.
-  int idn = a.ids ? a.ids[b] : 0;   // id of the step whose row load_gi gathers next
-  auto load_gi = [&](int t, float (&gi)[3]) {
-    if (t >= T) return;
-    const float* src = a.ids ? a.P + (size_t)idn * 3 * H : a.Gi + ((size_t)t * Bp + b) * 3 * H;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) gi[g] = src[g * H + j];
-    if (a.ids && t + 1 < T) idn = a.ids[(size_t)(t + 1) * Bp + b];
-  };
-  float gin[3] = {0.f, 0.f, 0.f};
-  load_gi(0, gin);
-  for (int t = 0; t < T; ++t) {
-    stamp(a.dbg, t, 0);
-    const float gi[3] = {gin[0], gin[1], gin[2]};
-    f32x4 acc[NR][3];
-    zero_acc(acc);
-    if (t > 0 || a.h0) {
-      // wave w's K-slice [k0, k0 + 32*NKW) is produced by unit tiles k0/16 .. k0/16 + 2*NKW - 1
-      bf16x8 af[NKW][NR];
-      if (t > 0) {
-        // h_t from the producers' exchange tiles (written at step t-1); unit u = k0 + 32kk + lk
-        // lives in tile u/16 at column u%16
-        const size_t slot = ((size_t)((t - 1) % xr) * nrb + rbk) * nunit;
-        wave_wait_load<NKW>(a.cnt + (size_t)rbk * rb_lines * kFlagStride, lane < 2 * NKW, k0 / 16 + lane,
-                            (unsigned)t, a.err, [&](int kk) {
-          const int u = k0 + kk * 32 + lk;
-          const unsigned tb = (unsigned)(((slot + u / 16) * 32 + lr) * 16 + (u & 15)) * 2;
-#pragma unroll
-          for (int r = 0; r < NR; ++r) af[kk][r] = ld8_sc1(rX, tb + (unsigned)((rt + r) * 16 * 16 * 2));
-        });
-      } else {   // h_init, row-major HS[0] (written before the launch)
-        const unsigned base = (unsigned)((((size_t)b0 + rt * 16 + lr) * H + k0 + lk) * 2);
-#pragma unroll
-        for (int kk = 0; kk < NKW; ++kk)
-#pragma unroll
-          for (int r = 0; r < NR; ++r) af[kk][r] = ld8_sc1(rH, base + (unsigned)(r * 16 * H * 2 + kk * 64));
-      }
-      stamp(a.dbg, t, 1);
-#pragma unroll
-      for (int kk = 0; kk < NKW; ++kk)
-#pragma unroll
-        for (int r = 0; r < NR; ++r)
-#pragma unroll
-          for (int g = 0; g < 3; ++g) acc[r][g] = mfma16(af[kk][r], bw[kk][g], acc[r][g]);
-    }
-#pragma unroll
-    for (int r = 0; r < NR; ++r)
-#pragma unroll
-      for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) part[w][r * 3 + g][i * 64 + lane] = acc[r][g][i];
-    // FC consumers read wave 2's HF block of step t - 1 once wave 0 signals t + 1: drain it before
-    // the barrier wave 0 passes first (its exchange loads retired, so this waits on nothing else)
-    if constexpr (FC) {
-      if (w == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    stamp(a.dbg, t, 2);
-    float gh[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      float s = 0.f;
-      if constexpr (RS == 2) {
-#pragma unroll
-        for (int ww = 0; ww < 4; ++ww) s += part[rb * 4 + ww][g][reg * 64 + ln];
-      } else {
-#pragma unroll
-        for (int ww = 0; ww < 8; ++ww) s += part[ww][rb * 3 + g][reg * 64 + ln];
-      }
-      gh[g] = s + bh[g];
-    }
-    const float r = sigmoidf_(gi[0] + gh[0]);
-    const float z = sigmoidf_(gi[1] + gh[1]);
-    const float n = tanhf_(gi[2] + r * gh[2]);
-    const float h = n + z * (hp - n);
-    hp = h;
-    const u16 hb = f2bf(h);
-    stg[row][col] = hb;
-    stgT[col][row] = hb;
-    __syncthreads();
-    stamp(a.dbg, t, 3);
-    if (w == 0) {
-      // publish: the 32x16 bf16 tile (1 KB, whole lines of its own), 16 B per lane, write-through;
-      // drain; one signal.  Then the row-major copy for the GEMMs that read HS later.
-      const u32x4 v = *reinterpret_cast<const u32x4*>(&stg[lane >> 1][(lane & 1) * 8]);
-      const unsigned xo = (unsigned)((((size_t)(t % xr) * nrb + rbk) * nunit + ut) * 512 + lane * 8) * 2;
-      unsigned* fl = a.cnt + ((size_t)rbk * rb_lines + ut) * kFlagStride;
-      if (loc) {
-        st16_plain(rX, xo, v);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) signal_flag_local(fl, (unsigned)(t + 1));
-      } else {
-        st16_sc1(rX, xo, v);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) signal_flag(fl, (unsigned)(t + 1));
-      }
-      stamp(a.dbg, t, 4);
-      const size_t hs = ((size_t)(t + 1) * Bp + b0 + (lane >> 1)) * H + j0 + (lane & 1) * 8;
-      if (FC && !loc) st16_sc1(rH, (unsigned)(hs * 2), v);   // write-through: FC consumers on other XCDs
-      else if (TAIL && !loc) {
-        // write-through for tail blocks on other XCDs: four agent-scope dword stores (sc1) at the plain
-        // store's address.  (As one sc1 buffer store through rH the branch cost the step loop ~80
-        // v_readlane / v_writelane per step -- scalars parked in VGPR lanes -- against the plain kernel's 17.)
-        unsigned* hp = reinterpret_cast<unsigned*>(a.HSb + hs);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) __hip_atomic_store(hp + i, v[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else *reinterpret_cast<u32x4*>(a.HSb + hs) = v;
-      stamp(a.dbg, t, 5);
-    } else if (w == 1 && a.HT) {
-      const u32x4 v = *reinterpret_cast<const u32x4*>(&stgT[lane >> 2][(lane & 3) * 8]);
-      *reinterpret_cast<u32x4*>(a.HT + (size_t)(j0 + (lane >> 2)) * a.ldT + (size_t)(t + 1) * Bp + b0 + (lane & 3) * 8) = v;
-    } else if (w == 2 && a.HF) {   // the backward's dW_hh operand: one whole 1-KB block
-      const u32x4 v = *reinterpret_cast<const u32x4*>(&stgT[lane & 15][8 * (lane >> 4)]);
-      const size_t hf = (((size_t)(t + 1) * nunit + ut) * nrb + rbk) * 512 + lane * 8;
-      if (FC && !loc) st16_sc1(make_rsrc(a.HF, (unsigned)((size_t)(T + 1) * Bp * H * 2)), (unsigned)(hf * 2), v);
-      else *reinterpret_cast<u32x4*>(a.HF + hf) = v;
-    }
-    // the next gather, then the saves for the backward pass, AFTER the publish (not part of wave
-    // 0's drain).  Saves as buffer stores: one per-lane offset for the launch, the step in the
-    // scalar offset -- with 64-bit VGPR address math the compiler reused the in-flight gather's
-    // destination as a temporary and waited for it (+0.3 us per step at H = 512).
-    load_gi(t + 1, gin);
-    const int sstep = __builtin_amdgcn_readfirstlane(t * Bp * H * 4);   // uniform: no waterfall loop
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(h), rHSf, sv_lane, sstep + Bp * H * 4, 0);
-    // (TAIL: built for the packed saves only -- without the four fp32 save descriptors the step loop
-    // keeps every scalar in SGPRs: no v_readlane / v_writelane at all, 381 instructions per step against
-    // the plain kernel's 414 with 17 of them)
-    if (TAIL || a.s16) {   // packed bf16 (r, z, n, gh_n): one 8-B store at twice the fp32 offsets
-      typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-      const u32x2_ pv = {(unsigned)f2bf(r) | ((unsigned)f2bf(z) << 16), (unsigned)f2bf(n) | ((unsigned)f2bf(gh[2]) << 16)};
-      __builtin_amdgcn_raw_buffer_store_b64(pv, rS16, sv_lane * 2u, sstep * 2, 0);
-    } else if (a.sr) {
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(r), rSr, sv_lane, sstep, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(z), rSz, sv_lane, sstep, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(n), rSn, sv_lane, sstep, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gh[2]), rSg, sv_lane, sstep, 0);
-    }
-    stamp(a.dbg, t, 6);
-  }
-  if constexpr (FC) {   // h of the last step complete in HSb / HF -> epoch T + 1 for the consumers
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      unsigned* fl = a.cnt + ((size_t)rbk * rb_lines + ut) * kFlagStride;
-      if (loc) signal_flag_local(fl, (unsigned)(T + 1));
-      else signal_flag(fl, (unsigned)(T + 1));
-    }
-  }
-  if constexpr (TAIL) fwd_fc_tail(loc, smem);
+#include "gru_seq_fwd_body.h"
+  if constexpr (TAIL) fwd_fc_tail<false>(loc, smem, 0u);
 }
 
 // ==================================================================== two-layer wavefront forward
@@ -970,6 +767,16 @@ __global__ void __launch_bounds__(512, 1) gru_fwd_seq2_kernel(SeqFwd2Args a) {
 struct SeqBwdTailK : SeqBwdArgs { BwdTailArgs t; };
 template <bool TAIL> struct BwdKArg { typedef SeqBwdArgs type; };
 template <> struct BwdKArg<true> { typedef SeqBwdTailK type; };
+// gru_fb_one_kernel's single argument: the three launches' arguments in order, then its own.  Every phase
+// reads its part back from the kernel-argument segment at these offsets.
+struct FbOneArgs { SeqFwdArgs f; FcXentArgs fc; SeqBwdTailK b; FbOneX x; };
+static_assert(std::is_trivially_copyable<FbOneArgs>::value, "the phases read their arguments back byte for byte");
+constexpr size_t karg_align(size_t off, size_t al) { return (off + al - 1) / al * al; }
+static constexpr size_t kFbOneFcOff = karg_align(sizeof(SeqFwdArgs), alignof(FcXentArgs));
+static constexpr size_t kFbOneBOff = karg_align(kFbOneFcOff + sizeof(FcXentArgs), alignof(SeqBwdTailK));
+static constexpr size_t kFbOneXOff = karg_align(kFbOneBOff + sizeof(SeqBwdTailK), alignof(FbOneX));
+static_assert(sizeof(FbOneArgs) == karg_align(kFbOneXOff + sizeof(FbOneX), alignof(FbOneArgs)),
+              "members in declaration order at their natural alignment");
 
 // The end of the TAIL kernel, in this order (with 2. behind 4. the step measured the same, docs/DESIGN.md §6.9):
 //  1. every wave's dP partials to slab rbk as 16-B write-through stores (accP[g][nt] is 4 consecutive
@@ -988,14 +795,18 @@ template <> struct BwdKArg<true> { typedef SeqBwdTailK type; };
 // workgroups run.  Like fwd_fc_tail it takes nothing from the step loop but the accumulators: arguments
 // re-read from the kernel-argument segment through an opaque pointer, the thread index opaque.
 static_assert(std::is_trivially_copyable<SeqBwdTailK>::value, "the tail reads its arguments back from the kernel-argument segment");
-template <int NTW, int NTP>
+// ONE (gru_fb_one_kernel): the arguments lie at kFbOneBOff, the flag lines foff words behind a.cnt (the
+// launch's flag set); the loss partials were written inside this launch and are read sc1; workgroup 0 also
+// bumps the launch counter whose parity picks the next launch's flag set.
+template <int NTW, int NTP, bool ONE = false>
 DEV void bwd_dp_tail(const f32x4 (&accW)[3][NTW], const f32x4 (&accP)[3][NTP], const float (&dbh)[3], float dbi,
-                     float (*red)[16][33], unsigned char* stage /* >= 32 * 56 u16 */) {
+                     float (*red)[16][33], unsigned char* stage /* >= 32 * 56 u16 */, unsigned foff = 0u) {
   typedef const __attribute__((address_space(4))) char* kptr_t;
   kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(kp));
-  const SeqBwdTailK& k = *(const SeqBwdTailK*)kp;
+  const SeqBwdTailK& k = *(const SeqBwdTailK*)(kp + (ONE ? kFbOneBOff : 0));
   const SeqBwdArgs& a = k;
+  unsigned* const cnt = a.cnt + (ONE ? (size_t)foff : (size_t)0);
   int tid = (int)threadIdx.x;
   asm volatile("" : "+v"(tid));
   const int lane = tid & 63, w = tid >> 6, lr = lane & 15, lq = lane >> 4;
@@ -1021,7 +832,7 @@ DEV void bwd_dp_tail(const f32x4 (&accW)[3][NTW], const f32x4 (&accP)[3][NTP], c
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   lds_barrier();
-  if (tid == 0) signal_flag(a.cnt + ((size_t)rbk * nunit + ut) * kFlagStride, (unsigned)(T + 1));
+  if (tid == 0) signal_flag(cnt + ((size_t)rbk * nunit + ut) * kFlagStride, (unsigned)(T + 1));
   stamp(a.dbg, T + 1, 1);
   // ---- 2. bias and dW_hh partials of this row block (plain)
   if (tid < 96) {
@@ -1047,7 +858,7 @@ DEV void bwd_dp_tail(const f32x4 (&accW)[3][NTW], const f32x4 (&accP)[3][NTP], c
     for (;;) {
       bool ok = true;
       if (lane < nrb)
-        ok = __hip_atomic_load(a.cnt + ((size_t)lane * nunit + ut) * kFlagStride, __ATOMIC_RELAXED,
+        ok = __hip_atomic_load(cnt + ((size_t)lane * nunit + ut) * kFlagStride, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)(T + 1);
       if (__all(ok)) break;
       __builtin_amdgcn_s_sleep(GK_POLL_SLEEP);
@@ -1104,10 +915,21 @@ DEV void bwd_dp_tail(const f32x4 (&accW)[3][NTW], const f32x4 (&accP)[3][NTP], c
   }
   // ---- 5. the loss and the step counter
   if (blockIdx.x == 0 && tid < 64) {
-    const float l = wave_strided_sum(k.t.loss_part, k.t.nloss, 1, 0, lane);
+    float l;
+    if constexpr (ONE) {   // wave_strided_sum's order over sc1 loads
+      float acc = 0.f;
+      for (int s = lane; s < k.t.nloss; s += 64)
+        acc += __hip_atomic_load(k.t.loss_part + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      l = wave_sum(acc);
+    } else l = wave_strided_sum(k.t.loss_part, k.t.nloss, 1, 0, lane);
     if (tid == 0) {
       k.t.loss[0] = l;
       *k.t.step += 1;
+      if constexpr (ONE) {
+        kptr_t kx = kp + kFbOneXOff;
+        asm volatile("" : "+s"(kx));
+        *((const FbOneX*)kx)->launches += 1u;
+      }
     }
   }
   stamp(a.dbg, T + 1, 3);
@@ -1126,213 +948,11 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(typename BwdKArg<TA
   __shared__ __attribute__((aligned(16))) u16 srow[3][32][24];        // dGh tile, gate-major (exchange; 48-B rows)
   __shared__ __attribute__((aligned(16))) u16 sgT[4][16][40];         // dGh^T gates r,z,n + dGi_n^T (padded rows)
   __shared__ __attribute__((aligned(16))) float red[6][16][33];
-  // H = 1024 (NKW3 = 12): scalar wave index and scalar-offset exchange loads (below); the smaller
-  // variants measured slower with them (h512 step 0.2257 -> 0.2327 ms, profiles/r2_bwd_soffset_ab.json)
-  constexpr bool kScalarX = NKW3 >= 12;
-  const int tid = threadIdx.x, lane = tid & 63, w = kScalarX ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
-  const int H = a.H, H3 = 3 * a.H, Bp = a.Bp, T = a.T;
-  const int nrb = Bp / 32, ut = seq_unit_tile(nrb);
-  const int j0 = ut * 16, rbk = seq_row_block(nrb), b0 = rbk * 32;
-  const int lr = lane & 15, lk = 8 * (lane >> 4);
-  const int k0 = w * NKW3 * 32;
-  const unsigned nunit = (unsigned)(H / 16);
-
-  // this wave's K-slice of W_hh^T rows j0..j0+15 (dh = dGh · W_hh), resident all sequence: in
-  // VGPRs, or -- for the variants with fused weight gradients, whose accumulators take the
-  // register file -- lane-linear in LDS (each lane re-reads only its own 16-B slots: conflict-free,
-  // and program order suffices, no barrier)
-  // (also at H = 1024, NKW3 = 12, where the 48-VGPR slice measured 342 -> 327 us per layer in LDS)
-  constexpr bool kBwLds = NTW > 0 || NTP > 0 || NKW3 >= 12;
-  __shared__ __attribute__((aligned(16))) bf16x8 bwL[kBwLds ? NKW3 : 1][kBwLds ? 512 : 1];
-  bf16x8 bw[kBwLds ? 1 : NKW3];
-#pragma unroll
-  for (int kk = 0; kk < NKW3; ++kk) {
-    const bf16x8 v = ld8(a.WhhT + (size_t)(j0 + lr) * H3 + k0 + kk * 32 + lk);
-    if constexpr (kBwLds) bwL[kk][tid] = v; else bw[kk] = v;
-  }
-
-  const int rb = tid >> 8, reg = (tid >> 6) & 3, ln = tid & 63;
-  const int row = rb * 16 + (ln >> 4) * 4 + reg, col = ln & 15;
-  const int b = b0 + row, j = j0 + col;
-  float carry = 0.f;
-  float dbh[3] = {0.f, 0.f, 0.f}, dbi = 0.f;   // dbi: only the n gate differs from dbh
-  f32x4 accW[3][NTW > 0 ? NTW : 1];
-  f32x4 accP[3][NTP > 0 ? NTP : 1];
-  zero_acc(accW);
-  zero_acc(accP);
-  // exchange ring (SeqBwdArgs::xring, gru_seq16.hip): the slot of step t is reused at step t - xr
-  const int xr = a.xring >= 2 ? a.xring : T;
-  const rsrc_t rX = make_rsrc(a.xbuf, (unsigned)((size_t)T * Bp * H3 * 2));
-  const unsigned xlane = (unsigned)(((lk >> 4) * 3 * 512 + lr * 16 + (lk & 15)) * 2);   // exchange lane offset
-  zero_next_flags(a.zero_next, a.zero_words);
-  const bool loc = a.allow_local && row_block_local(a.cnt + (size_t)rbk * nunit * kFlagStride, ut, (int)nunit, a.err);
-  // the saves of step t-1 are loaded during step t, right after its hand-off: in front of the
-  // next poll they would delay it (vmcnt retires in order), and they have a whole step to land
-  float sv[6];
-  int svid = 0;
-  // the step's 32 row ids for the fused dP one-hot: staged through LDS by the epilogue threads of
-  // unit column 0 and read back right before use (8 ids held in registers across the barriers and
-  // the publish pushed the register file over the limit)
+  // the resident W_hh^T K-slice of the variants that keep it in LDS, lane-linear; the step's 32 row ids
+  constexpr bool kBwL = NTW > 0 || NTP > 0 || NKW3 >= 12;
+  __shared__ __attribute__((aligned(16))) bf16x8 bwL[kBwL ? NKW3 : 1][kBwL ? 512 : 1];
   __shared__ __attribute__((aligned(16))) int idsL[NTP > 0 ? 32 : 1];
-  auto load_saves = [&](int t) {
-    const size_t o = ((size_t)t * Bp + b) * H + j;
-    sv[0] = a.dy[o];
-    if (TAIL || a.s16) ld_save16_raw(a.s16 + o * 4, sv[1], sv[2]);   // unpacked at use
-    else { sv[1] = a.sr[o]; sv[2] = a.sz[o]; sv[3] = a.sn[o]; sv[4] = a.sghn[o]; }
-    sv[5] = a.HSf[o];   // HS[t] = h_{t-1}
-    if constexpr (NTP > 0) svid = a.ids[(size_t)t * Bp + b];   // this thread's row id (fused dP)
-  };
-  load_saves(T - 1);
-
-  for (int t = T - 1; t >= 0; --t) {
-    const int s = T - 1 - t;
-    stamp(a.dbg, s, 0);
-    f32x4 acc[2];
-    acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    acc[1] = acc[0];
-    if (s > 0) {
-      // wave w's columns [k0, k0 + 32*NKW3) of dGh (3 gates x H) come from unit tiles ((k0+16p) mod H)/16
-      bf16x8 af[NKW3][2];
-      // dGh_{t+1} column c = k0 + 32kk + lk (gate c/H, unit c%H) lives in producer tile (c%H)/16 of
-      // slot t+1 at column (c/H)*16 + c%16
-      // 32-column k-steps never straddle a gate (H % 32 == 0): gate c0 / H and producer tile
-      // (c0 % H) / 16 are wave-uniform (scalar offset); the lane part is fixed for the launch
-      const size_t slot = ((size_t)((t + 1) % xr) * nrb + rbk) * nunit;
-      wave_wait_load<NKW3>(a.cnt + (size_t)rbk * nunit * kFlagStride, lane < 2 * NKW3,
-                           ((k0 + 16 * lane) % H) / 16, (unsigned)s, a.err, [&](int kk) {
-        if constexpr (kScalarX) {
-          const int c0 = k0 + kk * 32;
-          const int so = (int)((((slot + (size_t)((c0 % H) / 16)) * 3 + (size_t)(c0 / H)) * 512) * 2);
-#pragma unroll
-          for (int r = 0; r < 2; ++r) af[kk][r] = ld8_sc1s(rX, xlane + (unsigned)(r * 16 * 16 * 2), so);
-        } else {
-          const int c = k0 + kk * 32 + lk, u = c % H;
-          const unsigned tb = (unsigned)(((slot + u / 16) * 3 + c / H) * 512 + lr * 16 + (u & 15)) * 2;
-#pragma unroll
-          for (int r = 0; r < 2; ++r) af[kk][r] = ld8_sc1(rX, tb + (unsigned)(r * 16 * 16 * 2));
-        }
-      });
-      stamp(a.dbg, s, 1);
-#pragma unroll
-      for (int kk = 0; kk < NKW3; ++kk) {
-        bf16x8 bk;
-        if constexpr (kBwLds) bk = bwL[kk][tid]; else bk = bw[kk];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) acc[r] = mfma16(af[kk][r], bk, acc[r]);
-      }
-    }
-    const int idc = svid;
-    float sr = sv[1], sz = sv[2], sn = sv[3], sghn = sv[4];
-    const float dy = sv[0], hprev = sv[5];
-    if (t > 0) load_saves(t - 1);
-    if (TAIL || a.s16) unpack_save16(sr, sz, sr, sz, sn, sghn);
-    // operands of the fused weight-gradient MFMAs (independent of other workgroups): issued after
-    // the hand-off so the poll above does not wait behind them; first used after the publish
-    bf16x8 hB[NTW > 0 ? NTW : 1];
-    if constexpr (NTW > 0) {
-      if (TAIL || a.HF) {   // whole 1-KB fragment blocks (8 lines each) instead of 16 rows x 64 B
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-          hB[nt] = ld8(a.HF + (((size_t)t * nunit + w * NTW + nt) * nrb + rbk) * 512 + lane * 8);
-      } else {
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-          hB[nt] = ld8(a.HT + (size_t)(w * NTW * 16 + nt * 16 + lr) * a.ldT + (size_t)t * Bp + b0 + lk);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) part[w][r][i * 64 + lane] = acc[r][i];
-    __syncthreads();
-    stamp(a.dbg, s, 2);
-    float dh = dy + carry;
-#pragma unroll
-    for (int ww = 0; ww < 8; ++ww) dh += part[ww][rb][reg * 64 + ln];
-    const float dn = dh * (1.f - sz);
-    const float dz = dh * (hprev - sn);
-    const float dan = dn * (1.f - sn * sn);
-    const float dar = dan * sghn * sr * (1.f - sr);
-    const float daz = dz * sz * (1.f - sz);
-    const float dhn = dan * sr;
-    carry = sz * dh;
-    dbh[0] += dar; dbh[1] += daz; dbh[2] += dhn; dbi += dan;
-    const u16 br = f2bf(dar), bz = f2bf(daz), bn = f2bf(dhn), bi = f2bf(dan);
-    srow[0][row][col] = br; srow[1][row][col] = bz; srow[2][row][col] = bn;
-    sgT[0][col][row] = br; sgT[1][col][row] = bz; sgT[2][col][row] = bn; sgT[3][col][row] = bi;
-    if constexpr (NTP > 0) {
-      if (col == 0) idsL[row] = idc;
-    }
-    __syncthreads();
-    stamp(a.dbg, s, 3);
-    // fused weight-gradient MFMAs (A = this step's dG^T tile from LDS), off the exchange: every wave
-    // runs them after the publish / transposed copies.  (Deferred into the next step's exchange-load window they delayed its
-    // recurrent MFMAs: 0.2199 -> 0.2291 ms, profiles/r2_rejected_ab.jsonl)
-    auto fused_mma = [&]() {
-      if constexpr (NTW > 0 || NTP > 0) {
-        bf16x8 ga[3];
-#pragma unroll
-        for (int g = 0; g < 3; ++g) ga[g] = *reinterpret_cast<const bf16x8*>(&sgT[g][lr][lk]);
-        if constexpr (NTW > 0) {
-#pragma unroll
-          for (int g = 0; g < 3; ++g)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) accW[g][nt] = mfma16(ga[g], hB[nt], accW[g][nt]);
-        }
-        if constexpr (NTP > 0) {
-          ga[2] = *reinterpret_cast<const bf16x8*>(&sgT[3][lr][lk]);   // dGi: n gate without r
-          int idv[8];
-          const int4 i0 = *reinterpret_cast<const int4*>(&idsL[lk]), i1 = *reinterpret_cast<const int4*>(&idsL[lk + 4]);
-          idv[0] = i0.x; idv[1] = i0.y; idv[2] = i0.z; idv[3] = i0.w;
-          idv[4] = i1.x; idv[5] = i1.y; idv[6] = i1.z; idv[7] = i1.w;
-#pragma unroll
-          for (int nt = 0; nt < NTP; ++nt) {
-            const int v = (w * NTP + nt) * 16 + lr;
-            bf16x8 oh;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) oh[e] = (__bf16)(idv[e] == v ? 1.0f : 0.0f);
-#pragma unroll
-            for (int g = 0; g < 3; ++g) accP[g][nt] = mfma16(ga[g], oh, accP[g][nt]);
-          }
-        }
-      }
-    };
-    if (w == 0) {
-      // publish the dGh_t tile as 3 gate blocks of [32 rows][16 units] (1 KB each, whole lines of its
-      // own): a consumer's 16-row fragment of one gate is then 512 contiguous bytes per producer
-      // (8 full lines per load instruction instead of 16-row x 96-B strided pieces)
-      const size_t tile = (((size_t)(t % xr) * nrb + rbk) * nunit + ut) * (3 * 32 * 16);
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(&srow[g][lane >> 1][(lane & 1) * 8]);
-        if (loc) st16_plain(rX, (unsigned)((tile + g * 512 + lane * 8) * 2), v);
-        else st16_sc1(rX, (unsigned)((tile + g * 512 + lane * 8) * 2), v);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      unsigned* fl = a.cnt + ((size_t)rbk * nunit + ut) * kFlagStride;
-      if (lane == 0) {
-        if (loc) signal_flag_local(fl, (unsigned)(s + 1));
-        else signal_flag(fl, (unsigned)(s + 1));
-      }
-      stamp(a.dbg, s, 4);
-    } else if (!TAIL && w <= 4 && a.dghT) {
-      // transposed copies for the (non-fused) weight-gradient GEMMs: 16 units x 32 rows per gate
-      const int g = w - 1;          // 0..3 : dGh r, z, n and dGi n
-      const u32x4 v = *reinterpret_cast<const u32x4*>(&sgT[g][lane >> 2][(lane & 3) * 8]);
-      const size_t c0 = (size_t)t * Bp + b0 + (lane & 3) * 8;
-      const int gg = g < 3 ? g : 2;
-      const size_t rowsel = (size_t)(gg * H + j0 + (lane >> 2)) * a.ldG + c0;
-      if (g < 3) *reinterpret_cast<u32x4*>(a.dghT + rowsel) = v;
-      if (g != 2) *reinterpret_cast<u32x4*>(a.dgiT + rowsel) = v;
-    }
-    if (!TAIL && a.dgi) {   // row-major dGi for the layer below, after the publish (not in wave 0's drain)
-      const size_t og = ((size_t)t * Bp + b) * H3 + j;
-      a.dgi[og] = br; a.dgi[og + H] = bz; a.dgi[og + 2 * H] = bi;
-    }
-    stamp(a.dbg, s, 5);
-    fused_mma();
-    stamp(a.dbg, s, 6);
-  }
+#include "gru_seq_bwd_body.h"
 
   if constexpr (TAIL) {   // the partials, their dP sum, the loss and the step counter
     bwd_dp_tail<NTW, NTP>(accW, accP, dbh, dbi, red, reinterpret_cast<unsigned char*>(&part[0][0][0]));
@@ -1370,6 +990,123 @@ __global__ void __launch_bounds__(512, 1) gru_bwd_seq_kernel(typename BwdKArg<TA
     float* dst = (k < 3 ? a.dbhh_part : a.dbih_part);
     if (dst) dst[(size_t)rbk * H3 + (k % 3) * H + j0 + c] = sum;
   }
+}
+
+// ==================================================================== forward + backward in one launch
+// gru_fb_one_kernel: the one-layer H = 512, V = 256 single-GPU step's two persistent launches as one, on
+// their common grid (H/16 x Bp/32 workgroups, the same block -> (unit tile, row block) map and the same
+// per-thread item): forward loop, FC head tail, a hand-over per ROW BLOCK, backward loop, dP tail.  The
+// backward of a row block needs nothing of another row block's forward, so a workgroup waits only for
+// the nunit workgroups of its own row block -- not for the slowest FC tail of the chip -- keeps `loc`
+// (no second placement census) and has its W_hh^T slice in flight across the wait.
+//
+// Hand-over (docs/DESIGN.md section 6.11).  Bytes that cross workgroups: dy (every FC tail of the row block ->
+// every backward workgroup of it), HF (forward wave 2 -> the backward's fused dW_hh operand loads).  Both
+// are plain stores and plain loads, so the hand-over is the release / acquire form of MI355X_MICROARCH.md
+// 'Valid forms': producer = every wave's s_waitcnt vmcnt(0), workgroup barrier, lane 0's agent release,
+// vmcnt(0), relaxed agent flag store of epoch T + 2 on the workgroup's own forward line; consumer = wave 0's
+// poll of the row block's nunit lines, ONE agent acquire, vmcnt(0), workgroup barrier, plain loads.  An
+// XCD-local row block leaves out the release (the bytes stay in the L2 all its workgroups share, as in the
+// recurrence's local form) and signals with the plain flag store; its consumers still invalidate their L1.
+// HSf and the packed saves are written and read by the same thread.  The loss partials: FcXTailOne.
+//
+// Flags: two sets of (forward block, backward block); the parity of a device launch counter, read at
+// kernel start, picks this launch's set, the prologue zeroes the other set for the next launch (the
+// kernel boundary orders that), workgroup 0 bumps the counter as its last act (every workgroup read it
+// at its start, long before any row block can have finished).  The two exchange rings have regions of
+// their own: row block A may be in its backward while row block B is still in its forward.
+// LDS: the forward's union and the backward's arrays overlaid (together they would not fit 160 KB).
+struct FbOneBwdLds {
+  float part[8][2][256];
+  u16 srow[3][32][24];
+  u16 sgT[4][16][40];
+  float red[6][16][33];
+  bf16x8 bwL[6][512];
+  int idsL[32];
+};
+static constexpr size_t kFbOneLds = sizeof(FbOneBwdLds) > kFwdTailLds ? sizeof(FbOneBwdLds) : kFwdTailLds;
+
+// (a template only so that the bodies' discarded `if constexpr` branches stay unchecked, as in their own kernels)
+template <int NKW, int RS, int NKW3, int NTW, int NTP, bool FC = false>
+__global__ void __launch_bounds__(512, 1) gru_fb_one_kernel(FbOneArgs k) {
+  static_assert(NKW == 4 && RS == 2 && NKW3 == 6 && NTW == 4 && NTP == 2 && !FC, "built for H = 512, V = 256");
+  static_assert(std::is_same<decltype(&gru_fb_one_kernel<NKW, RS, NKW3, NTW, NTP, FC>), void (*)(FbOneArgs)>::value,
+                "one argument struct and nothing else");
+  static_assert(kFbOneFcOff == (sizeof(SeqFwdArgs) + alignof(FcXentArgs) - 1) / alignof(FcXentArgs) * alignof(FcXentArgs),
+                "fwd_fc_tail finds the head's arguments where the two-argument forward has them");
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kFbOneLds];
+  typedef const __attribute__((address_space(4))) char* kptr_t;
+  constexpr bool TAIL = true;
+  // ---- the launch's flag set; the other one zeroed for the next launch
+  unsigned foff;
+  {
+    const unsigned par = __builtin_amdgcn_readfirstlane(__hip_atomic_load(k.x.launches, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & 1u;
+    foff = par * (unsigned)k.x.set_words;
+    zero_next_flags(k.f.cnt + (size_t)(par ^ 1u) * k.x.set_words, k.x.set_words);
+  }
+#define GK_FB_ONE 1
+  // ---- forward loop, FC head tail
+  bool loc_f;
+  {
+    const SeqFwdArgs& a = k.f;
+    const typename FwdFcArg<!FC>::type& fc = k.fc;   // (the FC consumers' arguments: unused, FC is false)
+    (void)fc;
+#include "gru_seq_fwd_body.h"
+    loc_f = loc;
+  }
+  fwd_fc_tail<true>(loc_f, smem, foff);
+  // ---- hand-over: this workgroup's FC blocks are done
+  bf16x8 wpre[NKW3];
+  {
+    kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const SeqFwdArgs& a = *(const SeqFwdArgs*)kp;
+    const SeqBwdArgs& b = *(const SeqBwdTailK*)(kp + kFbOneBOff);
+    int tid = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, w = tid >> 6, lr = lane & 15, lk = 8 * (lane >> 4);
+    const int T = a.T, nrb = a.Bp / 32, nunit = a.H / 16;
+    const int ut = seq_unit_tile(nrb), rbk = seq_row_block(nrb);
+    // the backward's W_hh^T slice depends only on the launch before: in flight across the wait
+#pragma unroll
+    for (int kk = 0; kk < NKW3; ++kk)
+      wpre[kk] = ld8(b.WhhT + (size_t)(ut * 16 + lr) * (3 * 512) + w * NKW3 * 32 + kk * 32 + lk);
+    unsigned* const fl = a.cnt + (size_t)foff + (size_t)rbk * nunit * kFlagStride;
+    stamp(a.dbg, T + 1, 7);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave: its dy / HF / HSf / save stores (and wpre)
+    __syncthreads();
+    if (tid == 0) {
+      if (loc_f) signal_flag_local(fl + (size_t)ut * kFlagStride, (unsigned)(T + 2));
+      else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        signal_flag(fl + (size_t)ut * kFlagStride, (unsigned)(T + 2));
+      }
+    }
+    sweep_flags(fl, nunit, (unsigned)(T + 2), a.err);
+    if (tid < 64) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();   // also: the forward's use of the LDS union is over
+    stamp(a.dbg, T + 2, 0);
+  }
+  // ---- backward loop, dP tail
+  {
+    kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    const SeqBwdTailK& a = *(const SeqBwdTailK*)(kp + kFbOneBOff);
+    FbOneBwdLds& L = *reinterpret_cast<FbOneBwdLds*>(smem);
+    auto& part = L.part;
+    auto& srow = L.srow;
+    auto& sgT = L.sgT;
+    auto& red = L.red;
+    auto& bwL = L.bwL;
+    auto& idsL = L.idsL;
+#include "gru_seq_bwd_body.h"
+    bwd_dp_tail<NTW, NTP, true>(accW, accP, dbh, dbi, red, reinterpret_cast<unsigned char*>(&part[0][0][0]), foff);
+  }
+#undef GK_FB_ONE
 }
 
 // ==================================================================== host side
@@ -1446,13 +1183,17 @@ bool gru_fwd_seq_tail_supported(int H, int Bp, int V) {
   return cap >= (H / 16) * (Bp / 32);
 }
 
-void gru_fwd_seq_tail(const SeqFwdArgs& a, const FcXentArgs& f, hipStream_t s) {
+static void check_fwd_tail_args(const SeqFwdArgs& a, const FcXentArgs& f) {
   if (a.H != 512 || f.H != 512 || f.V != 256 || f.M != a.T * a.Bp || f.X != a.HSb + (size_t)a.Bp * a.H || !f.Wf || !f.WTf ||
       !f.dy || f.dl || !f.dlT || !f.loss_part || !f.labels || !f.inv_count || !f.b || !a.s16)
     throw std::runtime_error("gru_fwd_seq_tail: needs H = 512, V = 256, the packed saves (s16), X = HSb + Bp * H and the "
                              "fused-dH FC arguments");
   if ((size_t)(a.T + 1) * a.Bp * a.H * (a.s16 ? 8 : 4) >= (1ull << 31))
     throw std::runtime_error("gru_fwd_seq_tail: saves exceed the 2 GB buffer-offset range");
+}
+
+void gru_fwd_seq_tail(const SeqFwdArgs& a, const FcXentArgs& f, hipStream_t s) {
+  check_fwd_tail_args(a, f);
   dim3 grid((a.H / 16) * (a.Bp / 32)), block(512);
   hipLaunchKernelGGL((gru_fwd_seq_kernel<4, 2, false, 1, true>), grid, block, 0, s, a, f);
 }
@@ -1526,16 +1267,42 @@ bool gru_bwd_seq_tail_supported(int H, int Bp, int V) {
   return cap >= (H / 16) * nrb;
 }
 
-void gru_bwd_seq_tail(const SeqBwdArgs& a, const BwdTailArgs& t, hipStream_t s) {
+static void check_bwd_tail_args(const SeqBwdArgs& a, const BwdTailArgs& t) {
   const int nrb = a.Bp / 32;
   if (a.H != 512 || a.V != 256 || a.Bp < 32 || a.Bp % 32 || nrb > 8 || a.V % nrb || (a.V / nrb) % 8 || !a.dWhh_part || !a.dP_part ||
       !a.s16 || !a.HF || a.dghT || a.dgiT || a.dgi || !a.ids || !a.cnt || !a.err || !t.dP_bf || !t.dPT_bf || !t.loss_part || !t.loss || !t.step || t.nloss <= 0)
     throw std::runtime_error("gru_bwd_seq_tail: needs H = 512, V = 256, at most 8 row blocks dividing V into multiples "
                              "of 8 rows, the packed saves (s16), the HF copy, no dG copies, the fused dW_hh / dP "
                              "partials and every tail buffer");
-  dim3 grid((a.H / 16) * nrb), block(512);
+}
+
+void gru_bwd_seq_tail(const SeqBwdArgs& a, const BwdTailArgs& t, hipStream_t s) {
+  check_bwd_tail_args(a, t);
+  dim3 grid((a.H / 16) * (a.Bp / 32)), block(512);
   SeqBwdTailK k{a, t};
   hipLaunchKernelGGL((gru_bwd_seq_kernel<6, 4, 2, true>), grid, block, 0, s, k);
+}
+
+// Both of the above as one launch (gru_fb_one_kernel): the shapes of both, T >= 2, and all H/16 x Bp/32
+// workgroups of the merged kernel co-resident.
+bool gru_fb_one_supported(int H, int Bp, int V) {
+  if (!gru_fwd_seq_tail_supported(H, Bp, V) || !gru_bwd_seq_tail_supported(H, Bp, V)) return false;
+  return resident_blocks(gru_fb_one_kernel<4, 2, 6, 4, 2>) >= (H / 16) * (Bp / 32);
+}
+
+void gru_fb_one(const SeqFwdArgs& a, const FcXentArgs& f, const SeqBwdArgs& b, const BwdTailArgs& t, const FbOneX& x, hipStream_t s) {
+  check_fwd_tail_args(a, f);
+  check_bwd_tail_args(b, t);
+  const long fw = (long)(a.Bp / 32) * (a.H / 16) * kFlagStride;
+  if (a.T < 2 || b.T != a.T || b.Bp != a.Bp || a.h0 || !x.launches || x.set_words < 2 * fw || b.cnt < a.cnt + fw ||
+      b.cnt + fw > a.cnt + x.set_words || (const void*)b.xbuf == (const void*)a.xch || b.dy != f.dy || b.HF != a.HF ||
+      b.HSf != a.HSf || b.s16 != a.s16 || t.loss_part != f.loss_part)
+    throw std::runtime_error("gru_fb_one: needs T >= 2, no carried state, one set of buffers for both phases, the "
+                             "backward's flag block behind the forward's inside each of the two flag sets, an "
+                             "exchange region per phase and the launch counter");
+  dim3 grid((a.H / 16) * (a.Bp / 32)), block(512);
+  FbOneArgs k{a, f, SeqBwdTailK{b, t}, x};
+  hipLaunchKernelGGL((gru_fb_one_kernel<4, 2, 6, 4, 2>), grid, block, 0, s, k);
 }
 
 }  // namespace gk

@@ -101,6 +101,9 @@ struct StepLdsVariants {
   int bwd_tail = 1;      // one-layer H = 512, V = 256 single-GPU one-graph step: the dP row-block partials, the
                          // loss partials and the step counter summed as the tail of the persistent backward
                          // launch (gru_bwd_seq_tail); 0: the reduce_multi launch after it
+  int fb_one = 1;        // that step (fc_tail and bwd_tail both taken, T >= 2, no carried state): the persistent
+                         // forward and backward as ONE launch with a hand-over per row block (gru_fb_one);
+                         // 0: two launches
   int big_dy = 1;        // top layer on the persistent large-H backward, V = 256: dy = dl · W_fc inside it
                          // (SeqBwdArgs::dl) instead of the dH GEMM + an fp32 dy in memory
   int ld_pad = -1;       // padding of the dGh^T / dGi^T / dl^T leading dimension: -1 = 64 elements where
@@ -281,6 +284,20 @@ struct BwdTailArgs {
 };
 bool gru_bwd_seq_tail_supported(int H, int Bp, int V);
 void gru_bwd_seq_tail(const SeqBwdArgs& a, const BwdTailArgs& t, hipStream_t s);
+// gru_fwd_seq_tail and gru_bwd_seq_tail as ONE launch on their common grid (gru_seq.hip
+// gru_fb_one_kernel): forward loop, FC head tail, a hand-over per row block (a workgroup waits for the
+// H/16 workgroups of its own row block only), backward loop, dP tail.  a / f / b / t are what the two
+// launches would take, except: a.cnt is the base of TWO flag sets of x.set_words words each, a set holding
+// the forward's block (at its start) and the backward's (b.cnt, inside set 0); x.launches is a device
+// counter, zero at first, that the kernel bumps once per launch and whose parity picks the launch's set
+// (the other set is zeroed for the next launch; both zero before the first); a.zero_next / b.zero_next are
+// unused; a.xch and b.xbuf must be regions of their own (row blocks are in different phases at one time).
+struct FbOneX {
+  long set_words = 0;
+  unsigned* launches = nullptr;
+};
+bool gru_fb_one_supported(int H, int Bp, int V);
+void gru_fb_one(const SeqFwdArgs& a, const FcXentArgs& f, const SeqBwdArgs& b, const BwdTailArgs& t, const FbOneX& x, hipStream_t s);
 // The same backward on 16-row row blocks x 32 units (gru_seq16.hip): 8 XCD-local row blocks at
 // Bp = 128, half the streamed dGh per workgroup; H = 1024, no fused dW_hh.  Bias / dP partials are
 // per 16-row block: dbhh_part / dbih_part [Bp/16][3H], dP_part [Bp/16][V][3H].
