@@ -29,7 +29,7 @@ KERNELS = ["kernels/gru_step.hip", "kernels/gru_seq.hip", "kernels/fc.hip", "ker
            "kernels/gen_f32.hip", "kernels/gemm256.hip", "kernels/gen_persist.hip", "kernels/gru_seq_big.hip",
            "kernels/gru_seq16.hip", "kernels/onehot.hip", "kernels/score.hip", "kernels/gen_ctl.hip",
            "kernels/gen_persist_ctl.hip", "kernels/beam.hip", "kernels/score_ctl.hip", "kernels/gen_persist_con.hip",
-           "kernels/gen_persist_soft.hip", "kernels/sbs.hip", "kernels/smc.hip"]
+           "kernels/gen_persist_soft.hip", "kernels/sbs.hip", "kernels/smc.hip", "kernels/dropout.hip"]
 ENGINE = ["runtime/blaslt.cpp", "engine/trainer.cpp", "engine/trainer_seq.cpp", "engine/generator.cpp", "comm/rccl_comm.cpp",
           "comm/watchdog.cpp", "comm/bootstrap.cpp", "data/name_loader.cpp"]
 PYBIND = ["bindings.cpp"]

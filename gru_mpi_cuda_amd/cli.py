@@ -628,6 +628,8 @@ def main(argv=None) -> int:
                         "(eval_nll / eval_ppl / eval_top1 in the log line and the metrics record)")
     t.add_argument("--eval-every", dest="eval_every", type=int, default=0)
     _add_model_args(t)
+    t.add_argument("--dropout", type=float, default=None, metavar="P",
+                   help="training dropout on the non-recurrent connections, 0 <= P < 1 (default 0: off)")
     sc = sub.add_parser("score", help="teacher-forced log-likelihood of names under a checkpoint")
     sc.add_argument("--ckpt", required=True)
     sc.add_argument("--fmt", choices=["auto", "gen", "ref"], default="auto")

@@ -35,6 +35,10 @@ class GRUConfig:
     eps: float = 1e-8
     weight_decay: float = 0.0
     clip_norm: float = 0.0      # 0 = off; global-norm gradient clipping otherwise
+    dropout: float = 0.0        # training dropout on the non-recurrent connections (every layer's output as
+                                # its consumer above sees it; layer 0's input and the recurrent path are
+                                # never masked): masks from Philox keyed by ``seed`` and the step counter
+                                # (models/cpu_ref.dropout_mask, docs/DESIGN.md §3.5).  Inference is untouched.
     # learning-rate schedule (applied on the device from the step counter, so graph replay keeps
     # it): linear warm-up over warmup_steps, then "const", "cosine" or "linear" decay to lr_min at
     # total_steps (models/cpu_ref.lr_at)
@@ -77,6 +81,8 @@ class GRUConfig:
         for name in ("vocab", "embed", "hidden", "batch", "seq", "max_len"):
             if getattr(self, name) <= 0:
                 raise ValueError(f"{name} must be positive")
+        if not (0.0 <= float(self.dropout) < 1.0):   # (NaN fails both comparisons)
+            raise ValueError(f"dropout must be in [0, 1), got {self.dropout!r}")
 
     # -- sizes -------------------------------------------------------------------
     def layer_in(self, l: int) -> int:

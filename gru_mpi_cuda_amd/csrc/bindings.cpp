@@ -130,6 +130,7 @@ PYBIND11_MODULE(_C, m) {
         d.V = get<int>(dims, "V", 256); d.E = get<int>(dims, "E", 512); d.H = get<int>(dims, "H", 512);
         d.L = get<int>(dims, "L", 1); d.B = get<int>(dims, "B", 256); d.T = get<int>(dims, "T", 32);
         d.chunks = get<int>(dims, "chunks", 4); d.overlap = get<int>(dims, "overlap", 1);
+        d.seed = get<uint64_t>(dims, "seed", 0);
         OptCfg o;
         o.lr = get<float>(opt, "lr", 1e-3f); o.b1 = get<float>(opt, "beta1", 0.9f); o.b2 = get<float>(opt, "beta2", 0.999f);
         o.eps = get<float>(opt, "eps", 1e-8f); o.wd = get<float>(opt, "weight_decay", 0.f);
@@ -137,6 +138,7 @@ PYBIND11_MODULE(_C, m) {
         o.sched = get<int>(opt, "lr_sched", 0); o.warmup = get<int>(opt, "warmup_steps", 0);
         o.total = get<int>(opt, "total_steps", 0); o.lr_min = get<float>(opt, "lr_min", 0.f);
         o.keep_grads = get<int>(opt, "keep_grads", 1);
+        o.dropout = get<double>(opt, "dropout", 0.0);
         return new Trainer(d, o, Pp<float>(params), Pp<float>(grads), Pp<float>(mm), Pp<float>(vv), nflat, offsets);
       }))
       .def("refresh_weights", [](Trainer& t, uintptr_t s) { t.refresh_weights(S(s)); })
@@ -360,6 +362,25 @@ PYBIND11_MODULE(_C, m) {
   m.def("prep_batch", [](py::dict p, uintptr_t s) {
     const PrepJob j = prep_from(p, "prep_batch");
     prep_batch(j.in, j.Bmax, j.T, j.Bp, j.ids, j.labels, j.inv_count, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // training dropout (dropout.hip): the two mask kernels on raw buffers.  d: hsb / xd / xdT / ldT (forward)
+  // or dy (backward), step (one device int), seed, thr, scale, layer, b0, T, Bp, H
+  auto dropout_from = [](py::dict d) {
+    DropoutArgs a;
+    a.hsb = GP(const u16, d, "hsb"); a.xd = GP(u16, d, "xd"); a.xdT = GP(u16, d, "xdT");
+    a.ldT = get<long>(d, "ldT", 0); a.dy = GP(float, d, "dy"); a.step = GP(const int, d, "step");
+    a.seed = get<uint64_t>(d, "seed", 0); a.thr = get<uint32_t>(d, "thr", 0); a.scale = get<float>(d, "scale", 1.f);
+    a.layer = get<int>(d, "layer", 0); a.b0 = get<int>(d, "b0", 0);
+    a.T = get<int>(d, "T", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
+    return a;
+  };
+  m.def("dropout_fwd_seq", [dropout_from](py::dict d, uintptr_t s) {
+    dropout_fwd_seq(dropout_from(d), S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("dropout_bwd_seq", [dropout_from](py::dict d, uintptr_t s) {
+    dropout_bwd_seq(dropout_from(d), S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("colsum", [](uintptr_t in, int R, int C, uintptr_t out, uintptr_t s) {

@@ -15,6 +15,13 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
     : d_(d), o_(o), params_(params), grads_(grads), m_(m), v_(v), nflat_(nflat), off_(offsets) {
   if (d_.V % 64 || d_.E % 64 || d_.H % 64)
     throw std::runtime_error("HIP engine needs vocab, embed and hidden to be multiples of 64");
+  if (!(o_.dropout >= 0.0 && o_.dropout < 1.0))   // (NaN fails both comparisons)
+    throw std::runtime_error("dropout must be in [0, 1)");
+  if (o_.dropout > 0.0 && d_.overlap)
+    throw std::runtime_error("dropout > 0 is not supported with overlap = True (the chunked side-stream schedule "
+                             "stays undropped); use the single-stream step");
+  if (o_.dropout > 0.0 && (d_.L > 256 || d_.T >= (1 << 24)))
+    throw std::runtime_error("dropout: the mask counter holds layers <= 256 and seq < 2^24");
   Bp_ = round_up(std::max(d_.B, 1), 64);
   // library handle + workspace now, never inside the step-graph capture (also where the weight-
   // gradient engine will route dW_hh to the library)
@@ -145,6 +152,11 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
   sk_cnt_words_ = sk ? (long)(H / 128) * (B / 64) * 16 : 0;   // 64-row tiles (gru_bwd_step_sk64) need twice the 128-row count
   size_t o_skp = sk ? R((size_t)sk_part_floats_ * 4) : 0, o_skc = sk ? R((size_t)sk_cnt_words_ * 4) : 0;
   (void)any_bwd;
+  // training dropout: the masked copies of every layer's output sequence, reserved last and only when on
+  // (every other offset is what it is without dropout)
+  std::vector<size_t> o_xd(L, 0), o_xdT(L, 0);
+  if (dropout_on())
+    for (int l = 0; l < L; ++l) { o_xd[l] = R(tok * H * 2); o_xdT[l] = R((tok + B) * H * 2); }
   arena_.commit();   // zero-filled: HS[0] = h_init = 0, HT columns [0,Bp) = 0
   d_stage_ = arena_.get<int>(o_dst);
   cnt_ = arena_.get<unsigned>(o_cnt); err_ = arena_.get<unsigned>(o_err); xbuf_ = arena_.get<u16>(o_x);
@@ -173,6 +185,8 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
   WfcF = arena_.get<u16>(o_WfcF); WfcTF = arena_.get<u16>(o_WfcTF);
   logits_ = fc_split_ ? arena_.get<float>(o_lg) : nullptr;
   dl_ = arena_.get<u16>(o_dl); dlT_ = arena_.get<u16>(o_dlT); dP_bf_ = arena_.get<u16>(o_dPb); dPT_bf_ = arena_.get<u16>(o_dPTb);
+  if (dropout_on())
+    for (int l = 0; l < L; ++l) { Xd_.push_back(arena_.get<u16>(o_xd[l])); XdT_.push_back(arena_.get<u16>(o_xdT[l])); }
   Ls_.resize(L);
   for (int l = 0; l < L; ++l) {
     const LO& x = los[l];
@@ -226,15 +240,18 @@ Trainer::Trainer(const Dims& d, const OptCfg& o, float* params, float* grads, fl
   const char* ng = std::getenv("GK_NO_GRAPH");
   if (ng && ng[0] == '1') use_graph_ = false;
   overlap_ = d_.overlap != 0;
-  dy_in_bwd_ = fc_split_ && !overlap_ && !seq_.empty() && seq_.back().big && seq_.back().s16 && d_.V == 256 &&
+  // dropout: the head and the layer hand-offs stay launches of their own, between which the mask kernels
+  // run -- the plans of the variants' 0 settings (fwd_fc, fc_tail, fb_one, GK_FWD_WAVE, big_dy)
+  if (dropout_on()) fwd_wave_ = false;
+  dy_in_bwd_ = !dropout_on() && fc_split_ && !overlap_ && !seq_.empty() && seq_.back().big && seq_.back().s16 && d_.V == 256 &&
                step_lds_variants().big_dy;
-  fc_in_fwd_ = persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !seq_.empty() &&
+  fc_in_fwd_ = !dropout_on() && persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !seq_.empty() &&
                seq_[0].bwd && seq_[0].fuse_w && seq_[0].HF && step_lds_variants().fwd_fc &&
                Bp_ / 32 <= kFcSplitsMax && gru_fwd_seq_fc_supported(d_.H, Bp_, d_.V);
   // (the shape test is the one record_fb_seq launches the fused V = 256 head under)
   // (and the packed saves: the tail kernel is built for them alone, which is what keeps its step loop free
   // of scalar spills)
-  fc_tail_ = persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !fc_in_fwd_ && seq_[0].s16 &&
+  fc_tail_ = !dropout_on() && persist_fwd_ && !fwd_wave_ && d_.L == 1 && !overlap_ && !fc_split_ && !fc_in_fwd_ && seq_[0].s16 &&
              d_.V % 128 == 0 && d_.H % (16 * (d_.V / 64)) == 0 && step_lds_variants().fc_tail &&
              step_lds_variants().fc_flash == 0 && gru_fwd_seq_tail_supported(d_.H, Bp_, d_.V);
   // (the tail kernel is built for the packed saves, the HF copy and no transposed dG copies: the fused
@@ -778,6 +795,7 @@ void Trainer::optimizer_step(hipStream_t s) {
 
 void Trainer::set_comm(RcclComm* c, const std::vector<std::pair<long, long>>& buckets, long min_bucket_floats) {
   comm_ = c;
+  b0_ = c ? c->rank() * d_.B : 0;   // dropout: a rank draws the masks of its slice of the global batch
   if (!c) shard_opt_ = false;
   if (c) bwd_tail_ = fb_one_ = false;   // data-parallel steps keep the reduce launch (record_fb_seq)
   buckets_ = buckets;

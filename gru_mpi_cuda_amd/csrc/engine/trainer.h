@@ -26,6 +26,7 @@ namespace gk {
 struct Dims {
   int V = 256, E = 512, H = 512, L = 1, B = 256, T = 32, chunks = 4;
   int overlap = 1;   // side stream for chunk-consumers (0 = everything on one stream)
+  unsigned long long seed = 0;   // GRUConfig.seed: the Philox key of the dropout masks
 };
 struct OptCfg {
   float lr = 1e-3f, b1 = 0.9f, b2 = 0.999f, eps = 1e-8f, wd = 0.f, clip = 0.f;
@@ -33,6 +34,7 @@ struct OptCfg {
   int sched = 0, warmup = 0, total = 0;   // OptimArgs::sched / warmup / total
   float lr_min = 0.f;
   int keep_grads = 1;   // OptimArgs::keep_g
+  double dropout = 0.0; // training dropout on the non-recurrent connections (docs/DESIGN.md §3.5); 0 = off
 };
 
 class Trainer {
@@ -302,6 +304,15 @@ class Trainer {
   int* step_;
   u16 *Emb, *EmbT, *Wfc, *WfcT, *dl_, *dlT_, *dP_bf_, *dPT_bf_;
   bool fc_split_ = false;        // FC as LDS GEMM (logits) + softmax_xent + LDS GEMM (dH)
+  // Training dropout (OptCfg::dropout > 0, docs/DESIGN.md §3.5): every layer's output sequence reaches its
+  // consumer above (the FC head / the next layer's input projection, and their weight-gradient products)
+  // through the masked copies Xd [tok][H] and XdT (Layer::HT's layout), written by dropout_fwd_seq after the
+  // layer's forward; the gradient coming back is masked in place by dropout_bwd_seq.  The head then runs
+  // unfused (no fc_tail / fb_one / wavefront forward / big_dy: the plans of those variants' 0 settings).
+  bool dropout_on() const { return o_.dropout > 0.0; }
+  DropoutArgs drop_args(int l) const;
+  std::vector<u16*> Xd_, XdT_;
+  int b0_ = 0;                   // global index of this rank's first sequence (set_comm)
   float* logits_ = nullptr;
   u16 *WfcF, *WfcTF;   // fragment-tiled (kernels.h ft_offset) copies of W_fc and W_fc^T for fc_xent
 };

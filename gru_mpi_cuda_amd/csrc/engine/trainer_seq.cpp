@@ -12,6 +12,7 @@
 // co-resident (gru_*_seq_supported), so any config still runs -- just slower.
 #include "trainer.h"
 #include <algorithm>
+#include <cstdio>
 #include <string>
 
 namespace gk {
@@ -132,6 +133,17 @@ void Trainer::slab_job(SlabJobs& j, const float* src, int splits, long n, float*
   t.add(src, splits, n, dst);
 }
 
+// the mask kernels' arguments for layer l's output sequence (the unit index j is the padded model's, which is
+// the user's for every unit the user has: a padded unit's h and dy are exactly 0 under any mask)
+DropoutArgs Trainer::drop_args(int l) const {
+  DropoutArgs a;
+  a.step = step_; a.seed = d_.seed;
+  a.thr = (unsigned)(unsigned long long)(o_.dropout * 4294967296.0);   // floor(p 2^32), p < 1
+  a.scale = (float)(1.0 / (1.0 - o_.dropout));
+  a.layer = l; a.b0 = b0_; a.T = d_.T; a.Bp = Bp_; a.H = d_.H;
+  return a;
+}
+
 void Trainer::record_fb_seq(hipStream_t s, bool dp) {
   const int V = d_.V, E = d_.E, H = d_.H, T = d_.T, L = d_.L, B = Bp_;
   const int H3 = 3 * H;
@@ -146,6 +158,24 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
   // next step's forward(l)), so no memset node is needed; a block whose partner runs per-step
   // is zeroed by a memset instead.  The arena starts zeroed for the first step.
   nloss_ = (int)(tok / 32);
+  const bool drop = dropout_on();
+  if (drop && (fc_in_fwd_ || fc_tail_ || fwd_wave_ || dy_in_bwd_))
+    throw std::runtime_error("record_fb_seq: dropout needs the head and the layer hand-offs as launches of their own");
+  // layer l's output sequence as its consumer above reads it: the saved states, or their masked copies
+  auto x_of = [&](int l) -> const u16* { return drop ? Xd_[l] : Ls_[l].HSb + (size_t)B * H; };
+  auto xT_of = [&](int l) -> const u16* { return (drop ? XdT_[l] : Ls_[l].HT) + B; };
+  auto drop_fwd = [&](int l) {
+    if (!drop) return;
+    DropoutArgs a = drop_args(l);
+    a.hsb = Ls_[l].HSb; a.xd = Xd_[l]; a.xdT = XdT_[l]; a.ldT = (long)(T + 1) * B;
+    dropout_fwd_seq(a, s);
+  };
+  auto drop_bwd = [&](int l) {   // the gradient arriving at layer l's output from above, before its BPTT
+    if (!drop) return;
+    DropoutArgs a = drop_args(l);
+    a.dy = Ls_[l].dy;
+    dropout_bwd_seq(a, s);
+  };
   {
     // layer-0 input projection folded into a [V][3H] table: Gi(t,b) = P[x(t,b)], launched together
     // with the batch preparation (independent work, one graph node)
@@ -179,7 +209,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
   // the FC head's arguments: fc_xent's after the forward, or the forward's own with the head as its tail
   auto fc_args = [&]() {
     FcXentArgs f;
-    f.X = Ls_[L - 1].HSb + (size_t)B * H; f.W = Wfc; f.b = P("fc.bias");
+    f.X = x_of(L - 1); f.W = Wfc; f.b = P("fc.bias");
     f.labels = labels_; f.inv_count = inv_count_;
     f.dl = dl_; f.dlT = dlT_; f.ldT = (int)ldG_; f.colT = 0;
     f.loss_part = loss_part_; f.M = (int)tok; f.H = H; f.V = V;
@@ -210,7 +240,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     Layer& y = Ls_[l];
     if (l > 0) {
       GemmArgs g;   // hoisted input projection over all B*T tokens
-      g.A = Ls_[l - 1].HSb + (size_t)B * H; g.lda = H; g.B = y.Wih; g.ldb = H;
+      g.A = x_of(l - 1); g.lda = H; g.B = y.Wih; g.ldb = H;
       g.C = y.Gi; g.ldc = H3; g.bias = P("bias_ih_l" + std::to_string(l));
       g.M = (int)tok; g.N = H3; g.K = H;
       gemm_nt(g, s);
@@ -245,6 +275,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     } else {
       for (int t = 0; t < T; ++t) fwd_step(l, t, s);
     }
+    drop_fwd(l);
   }
   // ------------------------------------------------------------------ FC + loss + dH
   Layer& top = Ls_[L - 1];
@@ -282,6 +313,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       g.M = (int)tok; g.N = H; g.K = V;
       gemm_nt(g, s);
     }
+    drop_bwd(L - 1);   // (fc_tail_ / dy_in_bwd_ are off under dropout: top.dy is complete here)
     // dW_fc = dlogits^T · H_top, db_fc = row sums of dlogits^T: split-K into dedicated slabs whose
     // reduce joins the multi-tensor reduce after the backward sweep (one launch fewer)
     // few output tiles (V x H): split K until ~256 workgroups fill the chip
@@ -294,7 +326,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     // profiles/r6_gemm_dwfc.jsonl)
     if (sp * 2 <= kFcSplitsMax && tiles * sp < 512 && tok % (sp * 2) == 0 && tok / (sp * 2) >= 4096) sp *= 2;
     GemmArgs w;
-    w.A = dlT_; w.lda = (int)ldG_; w.B = top.HT + B; w.ldb = (T + 1) * B;
+    w.A = dlT_; w.lda = (int)ldG_; w.B = xT_of(L - 1); w.ldb = (T + 1) * B;
     w.C = slab_fc2_; w.ldc = H; w.rowsumA = rs_fc2_;
     w.M = V; w.N = H; w.K = (int)tok; w.splits = sp;
     // one-shot small GEMM over 512-deep K-slices when that fits the slab budget: one memory
@@ -470,7 +502,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
     } else {
       const int K = in_dim(l);
       // dW_ih = dGi^T · h_below, db_ih = row sums of dGi^T
-      wgrad_gemm(y.dgiT, (int)ldG_, Ls_[l - 1].HT + B, (T + 1) * B, H3, K, (int)tok, G("weight_ih_l" + k),
+      wgrad_gemm(y.dgiT, (int)ldG_, xT_of(l - 1), (T + 1) * B, H3, K, (int)tok, G("weight_ih_l" + k),
                  G("bias_ih_l" + k), s);
       if (dp) {
         ar_ready_ = group_end(l);   // FC (if l is the top layer) + this layer's four gradients
@@ -488,6 +520,7 @@ void Trainer::record_fb_seq(hipStream_t s, bool dp) {
       dx.A = y.dgi; dx.lda = H3; dx.B = y.WihT; dx.ldb = H3;
       dx.C = Ls_[l - 1].dy; dx.ldc = H; dx.M = (int)tok; dx.N = H; dx.K = H3;
       gemm_nt(dx, s);
+      drop_bwd(l - 1);
       if (dp && seq_[l - 1].bwd && ar_span()) ar_flush(s, false);
     }
   }
@@ -652,6 +685,11 @@ std::string Trainer::plan() const {
   p += overlap_ ? " overlap(chunks=" + std::to_string(C_) + ")" : " serial";
   if (bwd_tail_) p += " dP=bwd-tail";
   if (fb_one_ && fc_tail_ && bwd_tail_) p += " fb=one-launch";
+  if (dropout_on()) {
+    char b[32];
+    std::snprintf(b, sizeof b, " dropout=%g", o_.dropout);
+    p += b;
+  }
   return p;
 }
 

@@ -59,6 +59,18 @@ DEV float tanhf_(float x) {
   return copysignf(t, x);
 }
 
+// Philox-4x32-10 (Salmon et al., SC'11; the Random123 constants): the one device copy; the host twin is cpu_ref.philox4x32
+DEV void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
 // Cross-lane reductions.  Within a 16-lane row they use DPP (quad_perm xor 1, xor 2,
 // row_half_mirror, row_mirror: four VALU ops, every lane ends with the same value); __shfl_xor
 // lowers to ds_bpermute, an LDS round trip with an lgkmcnt(0) wait per step, which serialised

@@ -920,6 +920,30 @@ struct OptCastJobs { OptCastJob job[32]; int blk_start[33]; int n = 0;
 void adam_cast_multi(const OptimArgs& a, OptCastJobs& j, hipStream_t s);
 
 void fill_f32(float* p, long n, float v, hipStream_t s);
+
+// ------------------------------------------------------------------ training dropout (dropout.hip)
+// Dropout on the non-recurrent connections (docs/DESIGN.md §3.5; the rule: cpu_ref.dropout_mask).  Unit j
+// of sequence b (global index b0 + b) at time t of layer `layer` is kept iff word j & 3 of
+// Philox-4x32-10(key = seed, counter = (j >> 2, b0 + b, (layer << 24) | t, *step)) is >= thr, with
+// thr = floor(p 2^32); a kept value is scaled by `scale` = float(1 / (1 - p)), a dropped one is +0.
+// *step is the device step counter, read by the kernel: graph replays draw fresh masks.
+// Tokens are time-major, token = t Bp + b.  Bp % 4 == 0, H % 4 == 0, T < 2^24, layer < 256.
+struct DropoutArgs {
+  // forward: hsb [(T + 1) Bp][H] bf16 (rows 0 .. Bp are h0 and are not read) -> xd [T Bp][H] bf16 (one
+  // rounding: bf16_rne(float(h) * scale)) and its transpose xdT [H][ldT] bf16, written from column Bp
+  const u16* hsb = nullptr;
+  u16* xd = nullptr;
+  u16* xdT = nullptr; long ldT = 0;
+  // backward: dy [T Bp][H] fp32, in place (dy * scale or +0)
+  float* dy = nullptr;
+  const int* step = nullptr;
+  unsigned long long seed = 0;
+  unsigned thr = 0;
+  float scale = 1.f;
+  int layer = 0, b0 = 0, T = 0, Bp = 0, H = 0;
+};
+void dropout_fwd_seq(const DropoutArgs& a, hipStream_t s);
+void dropout_bwd_seq(const DropoutArgs& a, hipStream_t s);
 // Exact exchange of the fp32 entries of up to 16 flat ranges (the biases, which kernels read in fp32)
 // between ranks of a sharded optimiser: pack (unpack = 0): pack[k] = bits of p[f] if f is in the
 // owned chunk [lo, hi), else 0; unpack (1): p[f] = bits of pack[k] for f < tail (the replicated tail,

@@ -29,17 +29,6 @@ namespace {
 constexpr int kDead = 0, kLive = 1, kFin = 2;   // SmcSelectArgs::state values (BeamSelectArgs')
 constexpr int kMaxWaves = 16;
 
-// Philox-4x32-10 (Salmon et al., SC'11; the Random123 constants)
-DEV void smc_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&o)[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
 DEV float smc_unit(unsigned word) { return (float)(2u * (word >> 9) + 1u) * 0x1p-24f; }   // exact, in [2^-24, 1 - 2^-24]
 }  // namespace
 
@@ -173,7 +162,7 @@ __global__ void __launch_bounds__(1024) smc_select_f32_kernel(SmcSelectArgs a) {
   const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32), g0 = (unsigned)gidx, g1 = (unsigned)(gidx >> 32);
   if (res) {
     unsigned wd[4];
-    smc_philox(0u, (unsigned)a.step, g0, g1, k0, k1, wd);
+    philox4x32_10(0u, (unsigned)a.step, g0, g1, k0, k1, wd);
     U = smc_unit(wd[1]);
   }
   if (threadIdx.x == 0) {
@@ -221,7 +210,7 @@ __global__ void __launch_bounds__(1024) smc_select_f32_kernel(SmcSelectArgs a) {
         load_row(prow, y, ok, false);
         const float mxa = s_mxa[anc], sea = s_sea[anc];
         unsigned wd[4];
-        smc_philox((unsigned)i, (unsigned)a.step, g0, g1, k0, k1, wd);
+        philox4x32_10((unsigned)i, (unsigned)a.step, g0, g1, k0, k1, wd);
         const float target = smc_unit(wd[0]) * sea;
         float ex[MAXPER];
         float loc = 0.f;

@@ -56,8 +56,12 @@ class HipTrainer:
         self.buckets = _bucket_list(self.icfg, self.layout.total)
         offsets = {s.name: s.offset for s in self.layout.segments}
         ic = self.icfg
+        if cfg.dropout > 0 and cfg.overlap:
+            raise ValueError("dropout > 0 is not supported with overlap=True (the chunked side-stream schedule "
+                             "stays undropped)")
         dims = dict(V=ic.vocab, E=ic.embed, H=ic.hidden, L=cfg.layers, B=self.local_batch,
-                    T=cfg.seq, chunks=cfg.time_chunks, overlap=int(cfg.overlap))
+                    T=cfg.seq, chunks=cfg.time_chunks, overlap=int(cfg.overlap),
+                    seed=int(cfg.seed) & 0xFFFFFFFFFFFFFFFF)
         from ..models.cpu_ref import LR_SCHEDS
         if cfg.lr_sched not in LR_SCHEDS:
             raise ValueError(f"lr_sched must be one of {LR_SCHEDS}, got {cfg.lr_sched!r}")
@@ -65,7 +69,7 @@ class HipTrainer:
                    weight_decay=cfg.weight_decay, clip_norm=cfg.clip_norm,
                    sgd=int(cfg.optimizer == "sgd"), lr_sched=LR_SCHEDS.index(cfg.lr_sched),
                    warmup_steps=cfg.warmup_steps, total_steps=cfg.total_steps, lr_min=cfg.lr_min,
-                   keep_grads=int(cfg.keep_grads))
+                   keep_grads=int(cfg.keep_grads), dropout=float(cfg.dropout))
         self.t = self.C.Trainer(dims, opt, self.params.data_ptr(), self.grads.data_ptr(),
                                 self.m.data_ptr(), self.v.data_ptr(), self.layout.total, offsets)
         self.t.set_use_graph(use_graph)
@@ -294,7 +298,9 @@ class CpuTrainer:
         out = [] if self.cfg.carry_hidden else None
         loss, grads = cpu_ref.manual_backward(self.compute_params(), self.cfg, torch.from_numpy(np.asarray(x)),
                                               torch.from_numpy(np.asarray(y)), h0=self._state,
-                                              state_out=out)
+                                              state_out=out,
+                                              dropout_step=self.opt.step_n if self.cfg.dropout > 0 else None,
+                                              b0=self.ctx.rank * self.local_batch)
         if out is not None:
             self._state = out
         for k, g in grads.items():

@@ -39,10 +39,63 @@ def _gates(gi: torch.Tensor, gh: torch.Tensor, h: torch.Tensor):
     return hn, (r, z, n, ghn)
 
 
+# Training dropout on the non-recurrent connections (Zaremba et al. 2014; docs/DESIGN.md §3.5).  With
+# cfg.dropout = p every layer's output h_l[t, b, j] reaches its consumer above (the FC head, or layer l + 1's
+# input projection) as d = m h / (1 - p); layer 0's input, the recurrent path and a carried state are never
+# masked.  m = 1 iff word j & 3 of Philox-4x32-10(key = cfg.seed, counter = (j >> 2, b_global,
+# (layer << 24) | t, step)) is >= thr = floor(p 2^32) (formed in double): j the unit, b_global the sequence's
+# index in the GLOBAL batch (rank * local_batch + b, so a data-parallel step draws the single-GPU step's
+# masks), step the optimiser step counter when the step's forward runs (0 for the first step).  The backward
+# multiplies the gradient arriving at h_l[t] from above by the same m / (1 - p) before the layer's BPTT adds
+# the recurrent carry.  The device (csrc/kernels/dropout.hip) follows this rule bit for bit: its forward
+# scales the bf16 saved state by s = float32(1 / (1 - p)) with one rounding to bf16, its backward the fp32
+# gradient by the same s; a dropped element is +0.
+def dropout_threshold(p: float) -> int:
+    """thr of the mask rule: a unit is kept iff its 32-bit Philox word is >= thr."""
+    return int(math.floor(float(p) * 4294967296.0))
+
+
+def dropout_scale(p: float) -> np.float32:
+    """s of the mask rule as the device forms it: 1 / (1 - p) in double, rounded to float32."""
+    return np.float32(1.0 / (1.0 - float(p)))
+
+
+def dropout_mask(cfg: GRUConfig, layer: int, step: int, b_global, T: int) -> np.ndarray:
+    """The keep mask of ``layer``'s output at optimiser step ``step``: bool [B, T, H] for the sequences with
+    global batch indices ``b_global`` (array-like of B indices; an int is one sequence)."""
+    bg = np.atleast_1d(np.asarray(b_global, dtype=np.int64)).astype(np.uint64)
+    if bg.ndim != 1:
+        raise ValueError("dropout_mask: b_global is an index or a 1-D list of indices")
+    if not (0 <= int(layer) < 256 and 0 < int(T) <= (1 << 24)):
+        raise ValueError("dropout_mask: the counter holds layers < 256 and T <= 2^24")
+    B, H = bg.shape[0], cfg.hidden
+    nb = (H + 3) // 4
+    seed = int(cfg.seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.zeros((B, int(T), nb, 4), np.uint64)
+    ctr[..., 0] = np.arange(nb, dtype=np.uint64)[None, None, :]
+    ctr[..., 1] = (bg & _U32)[:, None, None]
+    ctr[..., 2] = (np.uint64(int(layer) << 24) | np.arange(int(T), dtype=np.uint64))[None, :, None]
+    ctr[..., 3] = np.uint64(int(step) & 0xFFFFFFFF)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64)
+    words = philox4x32(ctr, key).reshape(B, int(T), nb * 4)[..., :H]
+    return words >= np.uint32(dropout_threshold(cfg.dropout))   # (thr = 0 at p = 0: all ones)
+
+
+def _dropout_factor(cfg: GRUConfig, layer: int, step: int, b0: int, B: int, T: int, dt) -> torch.Tensor:
+    """m / (1 - p) of ``layer``'s output in the oracle dtype, [B, T, H]."""
+    m = dropout_mask(cfg, layer, step, b0 + np.arange(B), T)
+    return torch.from_numpy(m).to(dt) / (1.0 - float(cfg.dropout))
+
+
 def forward(params: Params, cfg: GRUConfig, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-            keep_cache: bool = False):
-    """x: [B, T] int ids.  Returns logits [B, T, V] (and per-layer caches if asked)."""
+            keep_cache: bool = False, dropout_step: Optional[int] = None, b0: int = 0):
+    """x: [B, T] int ids.  Returns logits [B, T, V] (and per-layer caches if asked).
+
+    dropout_step: None (every inference caller, and training without dropout) applies no mask; an int applies
+    cfg.dropout's masks of that optimiser step to every layer's output as its consumer sees it, the batch's
+    rows being sequences b0 .. b0 + B of the global batch."""
     B, T = x.shape
+    drop = dropout_step is not None and cfg.dropout > 0
     H = cfg.hidden
     dt = params["fc.weight"].dtype
     inp = params["embedding"][x.long()]                       # [B, T, E]
@@ -64,6 +117,12 @@ def forward(params: Params, cfg: GRUConfig, x: torch.Tensor, h0: Optional[List[t
                                z=torch.stack(zs, 1), n=torch.stack(ns, 1), ghn=torch.stack(ghns, 1),
                                out=out))
         inp = out
+        if drop:   # the consumer above reads d = m h / (1 - p); the recurrence above kept the unmasked h
+            f = _dropout_factor(cfg, l, dropout_step, b0, B, T, dt)
+            inp = out * f
+            if keep_cache:
+                caches[-1]["drop"] = f
+                caches[-1]["dout"] = inp
     logits = inp @ params["fc.weight"].T + params["fc.bias"]
     return (logits, caches) if keep_cache else logits
 
@@ -77,13 +136,15 @@ def xent(logits: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
 
 
 def manual_backward(params: Params, cfg: GRUConfig, x: torch.Tensor, y: torch.Tensor,
-                    h0: Optional[List[torch.Tensor]] = None, state_out: Optional[list] = None
-                    ) -> Tuple[torch.Tensor, Params]:
+                    h0: Optional[List[torch.Tensor]] = None, state_out: Optional[list] = None,
+                    dropout_step: Optional[int] = None, b0: int = 0) -> Tuple[torch.Tensor, Params]:
     """Explicit BPTT. Returns (loss, grads) with grads keyed like params.
 
     h0: optional per-layer initial states (truncated BPTT: treated as constants, no gradient
-    flows into them).  state_out: if a list, receives the per-layer final states h_{T-1}."""
-    logits, caches = forward(params, cfg, x, h0=h0, keep_cache=True)
+    flows into them).  state_out: if a list, receives the per-layer final states h_{T-1}.
+    dropout_step / b0: as in ``forward`` (None: no dropout); the gradient arriving at a layer's output from
+    above is multiplied by the forward's m / (1 - p) before the BPTT."""
+    logits, caches = forward(params, cfg, x, h0=h0, keep_cache=True, dropout_step=dropout_step, b0=b0)
     if state_out is not None:
         state_out[:] = [c["out"][:, -1].detach().clone() for c in caches]
     B, T, V = logits.shape
@@ -95,12 +156,14 @@ def manual_backward(params: Params, cfg: GRUConfig, x: torch.Tensor, y: torch.Te
     dlog = (p - onehot) * (valid.unsqueeze(-1).to(p.dtype) / cnt.to(p.dtype))
     loss = xent(logits, y)
     g: Params = {}
-    top = caches[-1]["out"]
+    top = caches[-1].get("dout", caches[-1]["out"])   # what the head read
     g["fc.weight"] = dlog.reshape(-1, V).T @ top.reshape(-1, H)
     g["fc.bias"] = dlog.sum((0, 1))
     dy = dlog @ params["fc.weight"]                           # [B, T, H]
     for l in reversed(range(cfg.layers)):
         c = caches[l]
+        if "drop" in c:
+            dy = dy * c["drop"]
         W_hh = params[f"weight_hh_l{l}"]
         dgi = torch.zeros(B, T, 3 * H, dtype=dy.dtype)
         dgh = torch.zeros_like(dgi)
@@ -129,10 +192,10 @@ def manual_backward(params: Params, cfg: GRUConfig, x: torch.Tensor, y: torch.Te
 
 
 def autograd_grads(params: Params, cfg: GRUConfig, x: torch.Tensor, y: torch.Tensor,
-                   h0: Optional[List[torch.Tensor]] = None):
+                   h0: Optional[List[torch.Tensor]] = None, dropout_step: Optional[int] = None, b0: int = 0):
     ps = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
     h0 = None if h0 is None else [h.detach() for h in h0]
-    loss = xent(forward(ps, cfg, x, h0=h0), y)
+    loss = xent(forward(ps, cfg, x, h0=h0, dropout_step=dropout_step, b0=b0), y)
     loss.backward()
     return loss.detach(), {k: v.grad for k, v in ps.items()}
 

@@ -73,3 +73,39 @@ def ft_layout(t):
     assert R % 16 == 0 and K % 32 == 0
     # [R/16][16 rows][K/32][4 k-groups][8] -> [R/16][K/32][4 k-groups][16 rows][8]
     return t.reshape(R // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().reshape(-1)
+
+
+def _dropout_common(step, seed: int, p: float, layer: int, b0: int, T: int, Bp: int, H: int) -> dict:
+    import torch
+    from ..models.cpu_ref import dropout_scale, dropout_threshold
+    if step.dtype != torch.int32 or step.numel() < 1 or not step.is_cuda:
+        raise ValueError("step: one int32 word on the device")
+    return dict(step=step.data_ptr(), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, thr=dropout_threshold(p),
+                scale=float(dropout_scale(p)), layer=int(layer), b0=int(b0), T=int(T), Bp=int(Bp), H=int(H))
+
+
+def dropout_fwd_seq(hsb, xd, xdT, step, *, seed: int, p: float, layer: int = 0, b0: int = 0) -> None:
+    """The forward mask kernel (csrc/kernels/dropout.hip) on torch tensors: hsb bf16 [T + 1, Bp, H] (slot 0
+    is h0 and is skipped) -> xd bf16 [T, Bp, H] and xdT bf16 [H, ldT] with ldT >= (T + 1) Bp, written from
+    column Bp; ``step`` is the device step word the kernel reads."""
+    import torch
+    T1, Bp, H = hsb.shape
+    for t in (hsb, xd, xdT):
+        if t.dtype != torch.bfloat16 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("dropout_fwd_seq: contiguous bf16 device tensors")
+    if tuple(xd.shape) != (T1 - 1, Bp, H) or xdT.dim() != 2 or xdT.shape[0] != H or xdT.shape[1] < T1 * Bp:
+        raise ValueError("dropout_fwd_seq: xd is [T, Bp, H], xdT [H, >= (T + 1) Bp]")
+    d = _dropout_common(step, seed, p, layer, b0, T1 - 1, Bp, H)
+    d.update(hsb=hsb.data_ptr(), xd=xd.data_ptr(), xdT=xdT.data_ptr(), ldT=int(xdT.shape[1]))
+    load_ext().dropout_fwd_seq(d, torch.cuda.current_stream(hsb.device).cuda_stream)
+
+
+def dropout_bwd_seq(dy, step, *, seed: int, p: float, layer: int = 0, b0: int = 0) -> None:
+    """The backward mask kernel on a torch tensor: dy fp32 [T, Bp, H], masked and scaled in place."""
+    import torch
+    if dy.dtype != torch.float32 or not dy.is_cuda or not dy.is_contiguous() or dy.dim() != 3:
+        raise ValueError("dropout_bwd_seq: a contiguous fp32 [T, Bp, H] device tensor")
+    T, Bp, H = dy.shape
+    d = _dropout_common(step, seed, p, layer, b0, T, Bp, H)
+    d.update(dy=dy.data_ptr())
+    load_ext().dropout_bwd_seq(d, torch.cuda.current_stream(dy.device).cuda_stream)
