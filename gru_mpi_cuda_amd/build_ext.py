@@ -29,7 +29,10 @@ KERNELS = ["kernels/gru_step.hip", "kernels/gru_seq.hip", "kernels/fc.hip", "ker
            "kernels/gen_f32.hip", "kernels/gemm256.hip", "kernels/gen_persist.hip", "kernels/gru_seq_big.hip",
            "kernels/gru_seq16.hip", "kernels/onehot.hip", "kernels/score.hip", "kernels/gen_ctl.hip",
            "kernels/gen_persist_ctl.hip", "kernels/beam.hip", "kernels/score_ctl.hip", "kernels/gen_persist_con.hip",
-           "kernels/gen_persist_soft.hip", "kernels/sbs.hip", "kernels/smc.hip", "kernels/dropout.hip"]
+           "kernels/gen_persist_soft.hip", "kernels/sbs.hip", "kernels/smc.hip", "kernels/dropout.hip",
+           "kernels/gen_persist_beam.hip"]
+# further flags of single sources (part of their objects' stamps and of the source hash)
+_FLAG_EXTRA = {"kernels/gen_persist_beam.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 ENGINE = ["runtime/blaslt.cpp", "engine/trainer.cpp", "engine/trainer_seq.cpp", "engine/generator.cpp", "comm/rccl_comm.cpp",
           "comm/watchdog.cpp", "comm/bootstrap.cpp", "data/name_loader.cpp"]
 PYBIND = ["bindings.cpp"]
@@ -53,7 +56,7 @@ def source_hash() -> str:
     test, the smoke check or the bench can never silently run an older build than the tree."""
     import hashlib
     h = hashlib.sha256()
-    h.update(("arch=%s;flags=%s" % (ARCH, " ".join(_FLAG_BASE))).encode())
+    h.update(("arch=%s;flags=%s;extra=%s" % (ARCH, " ".join(_FLAG_BASE), sorted(_FLAG_EXTRA.items()))).encode())
     for root, dirs, files in os.walk(CSRC):
         dirs.sort()
         for f in sorted(files):
@@ -109,13 +112,14 @@ def _compile(src: str, force: bool, hdr_digest: str) -> str:
     out = os.path.join(OBJ, src.replace("/", "_") + ".o")
     path = os.path.join(CSRC, src)
     with open(path, "rb") as fh:
-        digest = hashlib.sha256(fh.read() + hdr_digest.encode() + " ".join(_FLAG_BASE + [ARCH]).encode()).hexdigest()
+        digest = hashlib.sha256(fh.read() + hdr_digest.encode() +
+                                " ".join(_FLAG_BASE + [ARCH] + _FLAG_EXTRA.get(src, [])).encode()).hexdigest()
     stamp = out + ".src"
     if not force and os.path.exists(out) and os.path.exists(stamp):
         with open(stamp) as fh:
             if fh.read().strip() == digest:
                 return out
-    cmd = [HIPCC, *_flags(), "-c", path, "-o", out]
+    cmd = [HIPCC, *_flags(_FLAG_EXTRA.get(src, ())), "-c", path, "-o", out]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

@@ -460,7 +460,10 @@ def cmd_beam(args) -> int:
         res = cpu_ref.beam_search({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width,
                                   constraints=_constraints_from(args))
     else:
-        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)))
+        if args.persist_beam is not None and not 0 <= args.persist_beam <= 64:
+            raise SystemExit("--persist-beam needs a row count in [0, 64]")
+        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
+                             persist_beam=args.persist_beam or 0)
         res = gen.beam_search(prefixes, args.width, constraints=_constraints_from(args))
     lines = []
     for pre, names, lps in zip(prefixes, res.names(), res.logp):
@@ -694,6 +697,9 @@ def main(argv=None) -> int:
     bm.add_argument("--prefix", default=None, help="the names start with these chars (default: the empty prefix)")
     bm.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
     _constraint_args(bm)
+    bm.add_argument("--persist-beam", dest="persist_beam", type=int, nargs="?", const=64, default=None,
+                    help="HIP path: unconstrained batches of up to N rows (prefixes x width; bare flag: 64) run as one "
+                         "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4d)")
     bm.add_argument("--out", default=None, help="prefix, rank, name and log-prob per line, tab-separated")
     bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
     bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")

@@ -64,6 +64,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CTL_MAX")) persist_ctl_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CON_MAX")) persist_con_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_SOFT_MAX")) persist_soft_max_ = std::atoi(cm);
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_BEAM_MAX")) persist_beam_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -94,6 +95,14 @@ bool Generator::uses_persist_soft(int n, int con_mode) const {
   if (!uses_persist_ctl(n) || n > persist_soft_max_) return false;
   if (con_mode != kGenConNone && !uses_persist_con(n, con_mode == kGenConAuto)) return false;
   return gen_persist_soft_supported(d_.H, d_.L, d_.V, n, d_.max_len, con_mode);
+}
+
+bool Generator::uses_persist_beam(int n, int W) const {
+  // opt-in (persist_beam_max_ = 0 by default): docs/DESIGN.md §4d has the measurement.  The weights are the
+  // fp32 masters in every mode, as on the beam graph
+  if (!persist_ || n < 1 || W < 1 || (long)n * W > std::min(persist_beam_max_, 64)) return false;
+  if (bready_ && !pbws_) return false;   // the arena was committed without its workspace
+  return gen_persist_beam_supported(d_.H, d_.L, d_.V, n, W, d_.max_len);
 }
 
 Generator::~Generator() {
@@ -841,7 +850,12 @@ void Generator::beam_alloc() {
   const size_t opa = barena_.reserve(B * 4), och = barena_.reserve(B * 4), onx = barena_.reserve(B * 4);
   const size_t onb = barena_.reserve(B * 4), opl = barena_.reserve(B * 4), opre = barena_.reserve(B * ML);
   const size_t otab = barena_.reserve((size_t)kAllowRows * (d_.V / 32) * 4), oidx = barena_.reserve(B * ML * 4);
+  // the persistent small-batch launch's exchange buffers and flags, where the shape has a variant
+  const bool pb = gen_persist_beam_supported(d_.H, d_.L, d_.V, 1, 1, d_.max_len);
+  const size_t opbw = pb ? barena_.reserve((size_t)gen_persist_beam_ws_floats(d_.H, d_.L, d_.V, d_.max_len) * 4) : 0;
+  const size_t opbs = pb ? barena_.reserve((size_t)gen_persist_beam_sync_words(d_.L) * 4) : 0;
   barena_.commit();
+  if (pb) { pbws_ = barena_.get<float>(opbw); pbsync_ = barena_.get<unsigned>(opbs); }
   for (int l = 0; l < d_.L; ++l) { bhA_.push_back(barena_.get<float>(oA[l])); bhB_.push_back(barena_.get<float>(oB[l])); }
   bgh_ = barena_.get<float>(ogh); bgi_ = d_.L > 1 ? barena_.get<float>(ogi) : nullptr;
   blogits_ = barena_.get<float>(olg); bids_ = barena_.get<int>(oids);
@@ -968,7 +982,42 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
   const int ar = masked ? allow_rows : 0;
   if (masked && !aut)   // the table once per call
     HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
-  for (int start = 0; start < N; start += nb) {
+  for (int start = 0; start < N;) {
+    // opt-in: floor(rows / W) prefixes as one persistent launch on the caller's arrays (no staging copies)
+    const int np = masked ? 0 : std::min(std::min(persist_beam_max_, 64) / W, N - start);
+    if (np >= 1 && uses_persist_beam(np, W)) {
+      GenPersistBeamArgs a;
+      for (int l = 0; l < d_.L; ++l) {
+        const std::string k = std::to_string(l);
+        a.Whh[l] = P("weight_hh_l" + k); a.bhh[l] = P("bias_hh_l" + k);
+        if (l > 0) { a.Wih[l] = P("weight_ih_l" + k); a.bih[l] = P("bias_ih_l" + k); }
+      }
+      a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_;
+      a.plen = plen + start; a.prefix = prefix + (size_t)start * ML;
+      const size_t r0 = (size_t)start * W;
+      a.rows = rows + r0 * (ML + 1); a.logp = logp + r0; a.n_tok = n_tok + r0; a.n_beams = n_beams + start;
+      a.ws = pbws_; a.sync = pbsync_; a.err = err_;
+      a.N = np; a.W = W; a.H = d_.H; a.L = d_.L; a.V = d_.V; a.ML = ML; a.sos = d_.sos; a.eos = d_.eos;
+      gen_persist_beam_f32(a, s);
+      HIP_LAUNCH_CHECK();
+      ++persist_beam_launches_;
+      // as persist_launch: a spin timeout means the workgroups were not co-resident; the batch's output is
+      // garbage, so stop using the persistent path and run the batch on the graph
+      HIP_CHECK(hipMemcpyAsync(err_pin_, err_, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      const unsigned e = *reinterpret_cast<volatile unsigned*>(err_pin_);
+      if (!(e & 32u)) {
+        beam_last_persist_ = true;
+        start += np;
+        continue;
+      }
+      std::fprintf(stderr, "[generator] persistent beam launch hit its spin limit (error word %u): "
+                           "disabling it, searching %d prefixes on the per-char graph\n", e, np);
+      persist_ = false;
+      const unsigned keep = e & ~32u;
+      HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
+    }
+    beam_last_persist_ = false;
     const int n = std::min(nb, N - start);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
@@ -998,6 +1047,7 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
     HIP_CHECK(hipMemcpyAsync(logp + r0, bscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + r0, blen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_beams + start, bnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    start += n;
   }
 }
 

@@ -161,6 +161,16 @@ class Generator {
                    const int* allow_idx = nullptr, int allow_rows = 0, const unsigned short* allow_next = nullptr,
                    const int* allow_start = nullptr);
   int conditional_graphs() const { return (int)(qgraphs_.size() + aqgraphs_.size()); }   // recordings so far
+  // Unconstrained beam() batches of n prefixes x W beams run as ONE persistent launch (gen_persist_beam.hip,
+  // docs/DESIGN.md §4d) instead of the recorded graph: up to n W <= GK_GEN_PERSIST_BEAM_MAX /
+  // set_persist_beam_max(rows) rows, at most 64 -- 0 by default, the path is opt-in -- where a variant exists
+  // for the shape (gen_persist_beam_supported) and the persistent path is on (set_persist).  A batch is then
+  // floor(rows / W) prefixes, read from and written to the caller's arrays; its workspace lives in the beam
+  // arena.  A launch that hits its spin limit turns the persistent path off and the batch runs on the graph.
+  bool uses_persist_beam(int n, int W) const;
+  void set_persist_beam_max(int rows) { persist_beam_max_ = rows; }
+  bool beam_last_persist() const { return beam_last_persist_; }   // the path of the last beam() batch
+  long persist_beam_launches() const { return persist_beam_launches_; }
   size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
@@ -317,6 +327,11 @@ class Generator {
   unsigned char* bprefix_ = nullptr;            // [Bmax][ML]
   unsigned* btab_ = nullptr;                    // [kAllowRows][V / 32] the call's constraint table
   int* bidx_ = nullptr;                         // [Bmax][ML] the current batch's lines
+  int persist_beam_max_ = 0;                    // rows per persistent beam launch (GK_GEN_PERSIST_BEAM_MAX): opt-in
+  bool beam_last_persist_ = false;
+  long persist_beam_launches_ = 0;
+  float* pbws_ = nullptr;                       // persistent beam launch: exchange buffers (null: no variant for the shape)
+  unsigned* pbsync_ = nullptr;                  // ... flags + done counter (self-cleaning, arena-zeroed)
   // distinct names (plain allocations, made by the first distinct() call)
   float* dG_[2] = {nullptr, nullptr};           // [Bmax] x2 the slots' perturbed values, by step parity
   float* dinv_ = nullptr;                       // [Bmax] the current batch's 1 / T

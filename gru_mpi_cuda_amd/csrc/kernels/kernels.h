@@ -569,6 +569,37 @@ long gen_persist_ws_floats(int H, int L, int V, int ML);
 void gen_persist_fill_ws(float* ws, int H, int L, int V, int ML, hipStream_t s);   // both sets -> kEmpty
 long gen_persist_sync_words(int L);
 void gen_persist_f32(const GenPersistArgs& a, hipStream_t s);
+// Beam search for small batches as ONE persistent launch (gen_persist_beam.hip, docs/DESIGN.md §4d):
+// N prefixes x W beams = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the selection
+// (beam_select_f32's rule and arithmetic, no constraints) and the gather by parent inside the launch.
+// Outputs in Generator::beam's layout, written by workgroup n for prefix n.  `ws` holds, in floats:
+// h_l(t)[row][c] at ((l ML + t) 64 + row) H + c, logits(t)[row][v] at L ML 64 H + (t 64 + row) V + v, and
+// the records of step t < ML - 1 at L ML 64 H + ML 64 V + (t 64 + row) 2: the word (parent + 1) |
+// (char + 1) << 6 | state << 16 and the new beam's score.  It needs no fill; `sync` is all zero again
+// after every launch.  A prefix byte >= V ORs 16 into err[0] (err[1] = the byte, err[2] = the prefix's
+// first row) and is taken as 0; a wait that hits its spin limit ORs 32.
+struct GenPersistBeamArgs {
+  const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
+  const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
+  const float* Wfc = nullptr; const float* bfc = nullptr;   // [V][H], [V]
+  const float* P = nullptr;                // [V][3H] layer-0 table Emb W_ih0^T + b_ih0
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][ML]
+  unsigned char* rows = nullptr;           // [N][W][ML + 1]
+  float* logp = nullptr;                   // [N][W]  -inf for a dead slot
+  int* n_tok = nullptr;                    // [N][W]
+  int* n_beams = nullptr;                  // [N]
+  float* ws = nullptr;                     // gen_persist_beam_ws_floats()
+  unsigned* sync = nullptr;                // gen_persist_beam_sync_words(): zeroed once, self-cleaning
+  unsigned* err = nullptr;
+  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+};
+// N >= 1, 1 <= W <= 32, N W <= 64, H in {256, 512, 1024} with 2 L H / 32 <= 128 weight registers, V = 256
+// or 512, ML <= 64, and all 256 workgroups of the variant resident (each has scratch 0)
+bool gen_persist_beam_supported(int H, int L, int V, int N, int W, int ML);
+long gen_persist_beam_ws_floats(int H, int L, int V, int ML);
+long gen_persist_beam_sync_words(int L);
+void gen_persist_beam_f32(const GenPersistBeamArgs& a, hipStream_t s);   // throws before launching what is unsupported
 // Teacher-forced scoring of output rows (score.hip).  A row's token count n_tok = index of the first
 // EOS byte among its first ML bytes + 1, else ML; step l < n_tok has input SOS (l = 0) or c[l-1] and
 // target c[l].

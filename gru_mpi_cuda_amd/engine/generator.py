@@ -49,11 +49,14 @@ class HipGenerator:
     ``persist_soft`` = N (opt-in, default 0; docs/DESIGN.md §4h): soft batches (``logit_bias`` /
     ``presence_penalty`` / ``frequency_penalty``) of up to N names (at most 64) run as one soft persistent
     launch instead of the per-char graph, where the shape has a variant (vocab 256, max_len <= 64); a soft
-    batch with constraints needs ``persist_constraints`` to cover it as well."""
+    batch with constraints needs ``persist_constraints`` to cover it as well.
+    ``persist_beam`` = N (opt-in, default 0; docs/DESIGN.md §4d): unconstrained ``beam_search`` batches of up
+    to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where
+    the shape has a variant; ``sample_distinct`` and ``sample_conditional`` keep the graph."""
 
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
-                 precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0):
+                 precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0, persist_beam: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -79,6 +82,16 @@ class HipGenerator:
         self.g.refresh_weights(self._s())
         self.set_persist_constraints(persist_constraints)
         self.set_persist_soft(persist_soft)
+        self.set_persist_beam(persist_beam)
+
+    def set_persist_beam(self, n: int) -> None:
+        """Unconstrained ``beam_search`` batches of up to ``n`` rows (prefixes x width) take the persistent
+        launch where the shape has one (``g.uses_persist_beam``); 0 turns it off (the default).  After a call
+        ``g.beam_last_persist()`` tells which path its last batch took."""
+        n = int(n)
+        if n < 0 or n > 64:
+            raise ValueError(f"persist_beam must be in [0, 64], got {n}")
+        self.g.set_persist_beam_max(n)
 
     def set_persist_constraints(self, n: int) -> None:
         """Constrained batches of up to ``n`` names take the constrained persistent launch where the
@@ -274,7 +287,9 @@ class HipGenerator:
         empty prefixes.  Always exact fp32 arithmetic, whatever ``precision`` this generator samples
         with.  ``constraints`` (a cpu_ref.Constraints for the prefixes, or a dict of
         cpu_ref.make_constraints keywords; docs/DESIGN.md §4e; ``regex`` / ``exclude`` or a cpu_ref.Automaton:
-        §4g, a state per beam): the ``width`` most probable rows that satisfy them.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
+        §4g, a state per beam): the ``width`` most probable rows that satisfy them.  With ``persist_beam`` set,
+        an unconstrained call runs batches of floor(persist_beam / width) prefixes as one persistent launch each
+        (docs/DESIGN.md §4d); a constrained one keeps the graph.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
         raise ValueError before anything is launched."""
         pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
         N, W, ML = pre.shape[0], int(width), self.cfg.max_len
