@@ -420,7 +420,10 @@ def cmd_score(args) -> int:
         out = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows, **ctl)
         res = G.ScoreResult(out[0], out[3], out[1], out[2], out[4] if ctl else None)
     else:
-        res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0]))).score(rows, **ctl)
+        if args.persist_score is not None and not 0 <= args.persist_score <= 64:
+            raise SystemExit("--persist-score needs a name count in [0, 64]")
+        res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0])),
+                             persist_score=args.persist_score or 0).score(rows, **ctl)
     dt = time.perf_counter() - t0
     lines = []
     for r, lp, nt in zip(rows, res.name_logp, res.n_tok):
@@ -651,6 +654,9 @@ def main(argv=None) -> int:
     sc.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line, cycled over the names")
     _constraint_args(sc)
     _soft_args(sc)
+    sc.add_argument("--persist-score", dest="persist_score", type=int, nargs="?", const=64, default=None, metavar="N",
+                    help="HIP path: a call of up to N names (bare flag: 64) with no sampling flags runs as one "
+                         "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4a)")
     sc.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(sc)
     g = sub.add_parser("generate", help="namegen_initialize / namegen / namegen_finalize")

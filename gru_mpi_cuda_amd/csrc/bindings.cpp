@@ -312,6 +312,10 @@ PYBIND11_MODULE(_C, m) {
       .def("set_persist_beam_max", &Generator::set_persist_beam_max)
       .def("beam_last_persist", &Generator::beam_last_persist)
       .def("persist_beam_launches", &Generator::persist_beam_launches)
+      .def("uses_persist_score", &Generator::uses_persist_score)
+      .def("set_persist_score_max", &Generator::set_persist_score_max)
+      .def("score_last_persist", &Generator::score_last_persist)
+      .def("persist_score_launches", &Generator::persist_score_launches)
       .def("set_global_names", &Generator::set_global_names)
       .def("inject_persist_error", &Generator::inject_persist_error)
       .def("dump_graph", &Generator::dump_graph);
@@ -937,6 +941,30 @@ PYBIND11_MODULE(_C, m) {
     a.n_beams = GP(int, d, "n_beams");
     a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
     gen_persist_beam_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the persistent small-batch score on caller-owned buffers (tests/test_score_persist_gpu.py)
+  m.def("gen_persist_score_supported", &gen_persist_score_supported);
+  m.def("gen_persist_score_ws_floats", &gen_persist_score_ws_floats);
+  m.def("gen_persist_score_sync_words", &gen_persist_score_sync_words);
+  m.def("gen_persist_score", [](py::dict d, uintptr_t s) {
+    GenPersistScoreArgs a;
+    a.N = get<int>(d, "N", 0); a.H = get<int>(d, "H", 0); a.L = get<int>(d, "L", 0);
+    a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    // (before the pointer lists: an unsupported shape throws whatever else the dict holds)
+    if (!gen_persist_score_supported(a.H, a.L, a.V, a.N, a.ML))
+      throw std::runtime_error("gen_persist_score: unsupported shape or device (see gen_persist_score_supported)");
+    auto ptrs = [&](const char* k, const float* (&dst)[4], int first) {
+      const auto v = get<std::vector<uintptr_t>>(d, k, {});
+      if ((int)v.size() != a.L) throw std::runtime_error(std::string("gen_persist_score: ") + k + " needs L pointers");
+      for (int l = first; l < a.L; ++l) dst[l] = Pp<const float>(v[l]);
+    };
+    ptrs("Whh", a.Whh, 0); ptrs("bhh", a.bhh, 0); ptrs("Wih", a.Wih, 1); ptrs("bih", a.bih, 1);
+    a.Wfc = GP(const float, d, "Wfc"); a.bfc = GP(const float, d, "bfc"); a.P = GP(const float, d, "P");
+    a.rows = GP(const unsigned char, d, "rows"); a.tok_logp = GP(float, d, "tok_logp"); a.rank = GP(int, d, "rank");
+    a.name_logp = GP(float, d, "name_logp"); a.n_tok = GP(int, d, "n_tok");
+    a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
+    gen_persist_score_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("gru_gates_f32", [](py::dict d, uintptr_t s) {

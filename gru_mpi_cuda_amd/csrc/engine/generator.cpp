@@ -65,6 +65,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   if (const char* cm = std::getenv("GK_GEN_PERSIST_CON_MAX")) persist_con_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_SOFT_MAX")) persist_soft_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_BEAM_MAX")) persist_beam_max_ = std::atoi(cm);
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_SCORE_MAX")) persist_score_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -105,8 +106,17 @@ bool Generator::uses_persist_beam(int n, int W) const {
   return gen_persist_beam_supported(d_.H, d_.L, d_.V, n, W, d_.max_len);
 }
 
+bool Generator::uses_persist_score(int n) const {
+  // opt-in (persist_score_max_ = 0 by default): docs/DESIGN.md §4a has the measurement.  The weights are the
+  // fp32 masters in every mode, as on the score graph
+  if (!persist_ || n < 1 || n > std::min(persist_score_max_, 64)) return false;
+  return gen_persist_score_supported(d_.H, d_.L, d_.V, n, d_.max_len);
+}
+
 Generator::~Generator() {
   if (pcon_) (void)hipFree(pcon_);
+  if (psws_) (void)hipFree(psws_);
+  if (pssync_) (void)hipFree(pssync_);
   graphs_.clear();
   sgraphs_.clear();
   scgraphs_.clear();
@@ -769,6 +779,50 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
   if (N <= 0) return;
   const int ML = d_.max_len;
   if (ML > 64 || d_.V > 512) throw std::runtime_error("Generator::score needs max_len <= 64 and vocab <= 512");
+  score_last_persist_ = false;
+  if (!c && uses_persist_score(N)) {
+    // opt-in: the whole call as one persistent launch on the caller's arrays (no staging, no score arena, no graph)
+    if (!psws_) {
+      const size_t wsb = (size_t)gen_persist_score_ws_floats(d_.H, d_.L, d_.V, ML) * 4;
+      const size_t syb = (size_t)gen_persist_score_sync_words() * 4;
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&psws_), wsb));
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pssync_), syb));
+      HIP_CHECK(hipMemset(pssync_, 0, syb));
+    }
+    unsigned e0 = inject_ ? 32u : 0u;   // (test hook: the launch starts with its spin-limit bit set)
+    inject_ = false;
+    HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));
+    if (e0) {
+      HIP_CHECK(hipMemcpyAsync(err_, &e0, 4, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+    err_clean_ = false;
+    GenPersistScoreArgs a;
+    for (int l = 0; l < d_.L; ++l) {
+      const std::string k = std::to_string(l);
+      a.Whh[l] = P("weight_hh_l" + k); a.bhh[l] = P("bias_hh_l" + k);
+      if (l > 0) { a.Wih[l] = P("weight_ih_l" + k); a.bih[l] = P("bias_ih_l" + k); }
+    }
+    a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_;
+    a.rows = rows; a.tok_logp = tok_logp; a.rank = rank; a.name_logp = name_logp; a.n_tok = n_tok;
+    a.ws = psws_; a.sync = pssync_; a.err = err_;
+    a.N = N; a.H = d_.H; a.L = d_.L; a.V = d_.V; a.ML = ML; a.sos = d_.sos; a.eos = d_.eos;
+    gen_persist_score_f32(a, s);
+    HIP_LAUNCH_CHECK();
+    ++persist_score_launches_;
+    // as persist_launch: a spin timeout means the workgroups were not co-resident; the outputs are garbage,
+    // so stop using the persistent path and run the call on the graph
+    HIP_CHECK(hipMemcpyAsync(err_pin_, err_, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    const unsigned e = *reinterpret_cast<volatile unsigned*>(err_pin_);
+    if (!(e & 32u)) {
+      score_last_persist_ = true;
+      return;
+    }
+    std::fprintf(stderr, "[generator] persistent score launch hit its spin limit (error word %u): "
+                         "disabling it, scoring %d names on the graph\n", e, N);
+    persist_ = false;
+  }
   score_alloc();   // first call: allocates (and synchronises) before anything is captured
   if (c) score_ctl_alloc();   // ... the first controlled one its control buffers
   if (soft) soft_alloc();     // ... the first soft one the soft-control buffers

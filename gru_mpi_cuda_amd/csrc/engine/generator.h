@@ -119,6 +119,17 @@ class Generator {
   // 0 until the first score(); grows when the first controlled score() commits the control buffers
   size_t score_workspace_bytes() const { return sarena_.bytes() + scarena_.bytes(); }
   int score_graphs() const { return (int)(sgraphs_.size() + scgraphs_.size()); }   // recordings so far
+  // A plain score() call (no controls) whose whole N is at most GK_GEN_PERSIST_SCORE_MAX /
+  // set_persist_score_max(n) names, at most 64 -- 0 by default, the path is opt-in -- runs as ONE persistent
+  // launch (gen_persist_score.hip, docs/DESIGN.md §4a) on the caller's arrays, where a variant exists for the
+  // shape (gen_persist_score_supported) and the persistent path is on (set_persist).  Its workspace is a
+  // plain allocation of the first such launch: a generator whose calls all take it never commits the score
+  // arena and records no graph.  A launch that hits its spin limit turns the persistent path off and the
+  // call reruns on the graph.
+  bool uses_persist_score(int n) const;
+  void set_persist_score_max(int n) { persist_score_max_ = n; }
+  bool score_last_persist() const { return score_last_persist_; }   // the path of the last score() call
+  long persist_score_launches() const { return persist_score_launches_; }
   // Beam search (docs/DESIGN.md §4d; the rule: cpu_ref.beam_search): for each of N prefixes (device
   // plen [N], prefix [N][max_len], as generate_ctl's) the W most probable output rows in order:
   // rows [N][W][max_len+1], logp [N][W] (-inf for a dead slot), n_tok [N][W], n_beams [N], all device
@@ -332,6 +343,12 @@ class Generator {
   long persist_beam_launches_ = 0;
   float* pbws_ = nullptr;                       // persistent beam launch: exchange buffers (null: no variant for the shape)
   unsigned* pbsync_ = nullptr;                  // ... flags + done counter (self-cleaning, arena-zeroed)
+  // persistent score launch (plain allocations, made by the first such launch)
+  int persist_score_max_ = 0;                   // names per call (GK_GEN_PERSIST_SCORE_MAX): opt-in
+  bool score_last_persist_ = false;
+  long persist_score_launches_ = 0;
+  float* psws_ = nullptr;                       // exchange buffers
+  unsigned* pssync_ = nullptr;                  // flags + done counter (zeroed once, self-cleaning)
   // distinct names (plain allocations, made by the first distinct() call)
   float* dG_[2] = {nullptr, nullptr};           // [Bmax] x2 the slots' perturbed values, by step parity
   float* dinv_ = nullptr;                       // [Bmax] the current batch's 1 / T

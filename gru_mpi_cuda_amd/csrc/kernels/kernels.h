@@ -629,6 +629,32 @@ struct ScoreLogprobArgs {          // per token: log softmax(logits)[target] and
   int Bp = 0, V = 0, ML = 0;       // V % 64 == 0, V <= 512, ML <= 64
 };
 void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
+// Scoring of N <= 64 rows as ONE persistent launch (gen_persist_score.hip, docs/DESIGN.md §4a): score_prep's
+// rule, the exact-fp32 steps as a layer wavefront on gen_persist_kernel's grid and weight layout, and
+// score_logprob_f32's arithmetic as the tail, workgroup n writing name n's outputs straight to the caller's
+// arrays.  `ws` holds, in floats: h_l(t)[n][c] at ((l ML + t) 64 + n) H + c and logits(t)[n][v] at
+// L ML 64 H + (t 64 + n) V + v.  It needs no fill; `sync` is all zero again after every launch.  A byte >= V
+// at a scored position ORs 16 into err[0] and is taken as 0; a wait that hits its spin limit ORs 32.
+struct GenPersistScoreArgs {
+  const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
+  const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
+  const float* Wfc = nullptr; const float* bfc = nullptr;   // [V][H], [V]
+  const float* P = nullptr;                // [V][3H] layer-0 table Emb W_ih0^T + b_ih0
+  const unsigned char* rows = nullptr;     // [N][ML + 1]
+  float* tok_logp = nullptr;               // [N][ML]; masked positions 0
+  int* rank = nullptr;                     // [N][ML]; masked positions -1
+  float* name_logp = nullptr;              // [N]
+  int* n_tok = nullptr;                    // [N]
+  float* ws = nullptr;                     // gen_persist_score_ws_floats()
+  unsigned* sync = nullptr;                // gen_persist_score_sync_words(): zeroed once, self-cleaning
+  unsigned* err = nullptr;
+  int N = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+};
+// gen_persist_supported's shapes with ML <= 64, and all 256 workgroups of the variant resident (each has scratch 0)
+bool gen_persist_score_supported(int H, int L, int V, int N, int ML);
+long gen_persist_score_ws_floats(int H, int L, int V, int ML);
+long gen_persist_score_sync_words();
+void gen_persist_score_f32(const GenPersistScoreArgs& a, hipStream_t s);   // throws before launching what is unsupported
 // score_logprob_f32 under the sampler's distribution (score_ctl.hip, docs/DESIGN.md §4f): tok_logp is
 // the log-probability that sample_ctl_f32 with the name's controls (row b + row0 of each array) and
 // allowed sets picks the target.  Step l < plen: 0 if the target is prefix[l], else -inf.  inv_temp == 0:

@@ -52,11 +52,15 @@ class HipGenerator:
     batch with constraints needs ``persist_constraints`` to cover it as well.
     ``persist_beam`` = N (opt-in, default 0; docs/DESIGN.md §4d): unconstrained ``beam_search`` batches of up
     to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where
-    the shape has a variant; ``sample_distinct`` and ``sample_conditional`` keep the graph."""
+    the shape has a variant; ``sample_distinct`` and ``sample_conditional`` keep the graph.
+    ``persist_score`` = N (opt-in, default 0; docs/DESIGN.md §4a): a plain ``score`` call of up to N rows (at
+    most 64) runs as one persistent launch instead of the recorded graph, where the shape has a variant; larger
+    calls and calls with controls, constraints or soft terms keep the graph."""
 
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
-                 precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0, persist_beam: int = 0):
+                 precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0, persist_beam: int = 0,
+                 persist_score: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -83,6 +87,16 @@ class HipGenerator:
         self.set_persist_constraints(persist_constraints)
         self.set_persist_soft(persist_soft)
         self.set_persist_beam(persist_beam)
+        self.set_persist_score(persist_score)
+
+    def set_persist_score(self, n: int) -> None:
+        """A plain ``score`` call of up to ``n`` rows takes the persistent launch where the shape has one
+        (``g.uses_persist_score``); 0 turns it off (the default).  After a call ``g.score_last_persist()``
+        tells which path it took."""
+        n = int(n)
+        if n < 0 or n > 64:
+            raise ValueError(f"persist_score must be in [0, 64], got {n}")
+        self.g.set_persist_score_max(n)
 
     def set_persist_beam(self, n: int) -> None:
         """Unconstrained ``beam_search`` batches of up to ``n`` rows (prefixes x width) take the persistent
