@@ -505,7 +505,10 @@ def cmd_distinct(args) -> int:
     if args.cpu or not torch.cuda.is_available():
         res = cpu_ref.sample_distinct({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width, **kw)
     else:
-        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)))
+        if args.persist_distinct is not None and not 0 <= args.persist_distinct <= 64:
+            raise SystemExit("--persist-distinct needs a row count in [0, 64]")
+        gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
+                             persist_distinct=args.persist_distinct or 0)
         res = gen.sample_distinct(prefixes, args.width, **kw)
     lines = []
     for pre, names, lqs in zip(prefixes, res.names(), res.logq):
@@ -718,6 +721,9 @@ def main(argv=None) -> int:
     ds.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
     ds.add_argument("--temperature", type=float, default=None, help="softmax temperature, > 0 (default 1)")
     _constraint_args(ds)
+    ds.add_argument("--persist-distinct", dest="persist_distinct", type=int, nargs="?", const=64, default=None,
+                    help="HIP path: unconstrained batches of up to N rows (prefixes x width; bare flag: 64) run as one "
+                         "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4i)")
     ds.add_argument("--out", default=None, help="prefix, draw, name and log-prob per line, tab-separated")
     ds.add_argument("--cpu", action="store_true", help="cpu_ref.sample_distinct in fp32 instead of the HIP generator")
     ds.add_argument("--seed", dest="noise_seed", type=int, default=0,

@@ -158,6 +158,17 @@ class Generator {
                 int* n_found, hipStream_t s, const unsigned* allow_tab = nullptr, const int* allow_idx = nullptr,
                 int allow_rows = 0, const unsigned short* allow_next = nullptr, const int* allow_start = nullptr);
   int distinct_graphs() const { return (int)(dgraphs_.size() + adgraphs_.size()); }   // recordings so far
+  // Unconstrained distinct() batches of n prefixes x W slots run as ONE persistent launch (gen_persist_sbs.hip,
+  // docs/DESIGN.md §4i) instead of the recorded graph: up to n W <= GK_GEN_PERSIST_DISTINCT_MAX /
+  // set_persist_distinct_max(rows) rows, at most 64 -- 0 by default, the path is opt-in -- where a variant
+  // exists for the shape (gen_persist_sbs_supported) and the persistent path is on (set_persist).  A batch is
+  // then floor(rows / W) prefixes, read from and written to the caller's arrays (name n still draws at start +
+  // n: the bytes do not depend on the batches); its workspace is a plain allocation made by the first such
+  // launch.  A launch that hits its spin limit turns the persistent path off and the batch runs on the graph.
+  bool uses_persist_distinct(int n, int W) const;
+  void set_persist_distinct_max(int rows) { persist_distinct_max_ = rows; }
+  bool distinct_last_persist() const { return distinct_last_persist_; }   // the path of the last distinct() batch
+  long persist_distinct_launches() const { return persist_distinct_launches_; }
   // Conditional names (docs/DESIGN.md §4j; the rule: cpu_ref.sample_conditional): for each of N names W
   // weighted particles of a sequential Monte Carlo run over the constrained sampler.  rows [N][W][max_len+1],
   // logw [N][W] (the unnormalised log importance weights: their mean of exp is an unbiased estimate of the
@@ -353,6 +364,11 @@ class Generator {
   float* dG_[2] = {nullptr, nullptr};           // [Bmax] x2 the slots' perturbed values, by step parity
   float* dinv_ = nullptr;                       // [Bmax] the current batch's 1 / T
   unsigned long long* dwords_ = nullptr;        // [2] the call's seed, the current batch's first global index
+  int persist_distinct_max_ = 0;                // rows per persistent distinct launch (GK_GEN_PERSIST_DISTINCT_MAX): opt-in
+  bool distinct_last_persist_ = false;
+  long persist_distinct_launches_ = 0;
+  float* pdws_ = nullptr;                       // persistent distinct launch: exchange buffers (made by its first launch)
+  unsigned* pdsync_ = nullptr;                  // ... flags + done counter (zeroed once, self-cleaning)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> dgraphs_;    // keyed by (names, W, table lines or 0)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> adgraphs_;   // keyed by (names, W, states)
   // conditional names (plain allocations, made by the first conditional() call)

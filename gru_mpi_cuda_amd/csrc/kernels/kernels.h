@@ -600,6 +600,38 @@ bool gen_persist_beam_supported(int H, int L, int V, int N, int W, int ML);
 long gen_persist_beam_ws_floats(int H, int L, int V, int ML);
 long gen_persist_beam_sync_words(int L);
 void gen_persist_beam_f32(const GenPersistBeamArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// Stochastic beam search for small calls as ONE persistent launch (gen_persist_sbs.hip, docs/DESIGN.md §4i):
+// N prefixes x W slots = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the selection
+// (sbs_select_f32's rule, order and arithmetic, no constraints) and the gather by parent inside the launch.
+// Name n draws its noise at the global index start + n under seed.  Outputs in Generator::distinct's layout,
+// written by workgroup n for prefix n.  `ws` holds, in floats: h_l(t)[row][c] at ((l ML + t) 64 + row) H + c,
+// logits(t)[row][v] at L ML 64 H + (t 64 + row) V + v, and the records of step t < ML - 1 at L ML 64 H +
+// ML 64 V + (t 64 + row) 4: the word (parent + 1) | (char + 1) << 6 | state << 16, the new slot's logq and G,
+// and a pad word.  It needs no fill; `sync` is all zero again after every launch.  err as GenPersistBeamArgs'.
+struct GenPersistSbsArgs {
+  const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
+  const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
+  const float* Wfc = nullptr; const float* bfc = nullptr;   // [V][H], [V]
+  const float* P = nullptr;                // [V][3H] layer-0 table Emb W_ih0^T + b_ih0
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][ML]
+  const float* inv_t = nullptr;            // [N] 1 / temperature
+  unsigned char* rows = nullptr;           // [N][W][ML + 1]
+  float* logq = nullptr;                   // [N][W]  -inf for a dead slot
+  float* gumbel = nullptr;                 // [N][W]  -inf for a dead slot
+  int* n_tok = nullptr;                    // [N][W]
+  int* n_found = nullptr;                  // [N]
+  float* ws = nullptr;                     // gen_persist_sbs_ws_floats()
+  unsigned* sync = nullptr;                // gen_persist_sbs_sync_words(): zeroed once, self-cleaning
+  unsigned* err = nullptr;
+  unsigned long long seed = 0, start = 0;
+  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+};
+// gen_persist_beam_supported's family, with this kernel's own list of instances (each has scratch 0)
+bool gen_persist_sbs_supported(int H, int L, int V, int N, int W, int ML);
+long gen_persist_sbs_ws_floats(int H, int L, int V, int ML);
+long gen_persist_sbs_sync_words(int L);
+void gen_persist_sbs_f32(const GenPersistSbsArgs& a, hipStream_t s);   // throws before launching what is unsupported
 // Teacher-forced scoring of output rows (score.hip).  A row's token count n_tok = index of the first
 // EOS byte among its first ML bytes + 1, else ML; step l < n_tok has input SOS (l = 0) or c[l-1] and
 // target c[l].

@@ -52,7 +52,10 @@ class HipGenerator:
     batch with constraints needs ``persist_constraints`` to cover it as well.
     ``persist_beam`` = N (opt-in, default 0; docs/DESIGN.md §4d): unconstrained ``beam_search`` batches of up
     to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where
-    the shape has a variant; ``sample_distinct`` and ``sample_conditional`` keep the graph.
+    the shape has a variant.
+    ``persist_distinct`` = N (opt-in, default 0; docs/DESIGN.md §4i): unconstrained ``sample_distinct`` batches
+    of up to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph,
+    where the shape has a variant; ``sample_conditional`` keeps the graph.
     ``persist_score`` = N (opt-in, default 0; docs/DESIGN.md §4a): a plain ``score`` call of up to N rows (at
     most 64) runs as one persistent launch instead of the recorded graph, where the shape has a variant; larger
     calls and calls with controls, constraints or soft terms keep the graph."""
@@ -60,7 +63,7 @@ class HipGenerator:
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
                  precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0, persist_beam: int = 0,
-                 persist_score: int = 0):
+                 persist_score: int = 0, persist_distinct: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -88,6 +91,16 @@ class HipGenerator:
         self.set_persist_soft(persist_soft)
         self.set_persist_beam(persist_beam)
         self.set_persist_score(persist_score)
+        self.set_persist_distinct(persist_distinct)
+
+    def set_persist_distinct(self, n: int) -> None:
+        """Unconstrained ``sample_distinct`` batches of up to ``n`` rows (prefixes x width) take the persistent
+        launch where the shape has one (``g.uses_persist_distinct``); 0 turns it off (the default).  After a
+        call ``g.distinct_last_persist()`` tells which path its last batch took."""
+        n = int(n)
+        if n < 0 or n > 64:
+            raise ValueError(f"persist_distinct must be in [0, 64], got {n}")
+        self.g.set_persist_distinct_max(n)
 
     def set_persist_score(self, n: int) -> None:
         """A plain ``score`` call of up to ``n`` rows takes the persistent launch where the shape has one
@@ -336,7 +349,9 @@ class HipGenerator:
         -- stochastic beam search (the rule: cpu_ref.sample_distinct, docs/DESIGN.md §4i).  ``logq`` is what
         ``score(rows, temperature=, prefix=, constraints=).name_logp`` returns for the rows; ``gumbel`` the
         final perturbed values.  Name n of the call draws its noise at the global index ``start + n`` under
-        ``seed``, so the result does not depend on how a job is cut into calls or batches.  Always exact fp32
+        ``seed``, so the result does not depend on how a job is cut into calls or batches.  With
+        ``persist_distinct`` set, an unconstrained call runs batches of floor(persist_distinct / width) prefixes
+        as one persistent launch each (docs/DESIGN.md §4i).  Always exact fp32
         arithmetic; precision "bf16" is refused (ValueError), as are top_k, top_p, temperature 0 and the soft
         controls, before anything is launched."""
         if self.precision == "bf16":
