@@ -554,7 +554,10 @@ def cmd_conditional(args) -> int:
         if args.cpu or not torch.cuda.is_available():
             res = cpu_ref.sample_conditional({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width, **kw)
         else:
-            gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.runs * args.width)))
+            if args.persist_conditional is not None and not 0 <= args.persist_conditional <= 64:
+                raise SystemExit("--persist-conditional needs a row count in [0, 64]")
+            gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.runs * args.width)),
+                                 persist_conditional=args.persist_conditional or 0)
             res = gen.sample_conditional(prefixes, args.width, **kw)
     except ValueError as e:
         raise SystemExit(f"conditional: {e}")
@@ -742,6 +745,9 @@ def main(argv=None) -> int:
     cd.add_argument("--ess-threshold", dest="ess_threshold", type=float, default=0.5,
                     help="resample when the effective sample size falls below this fraction of the width (0: never)")
     _constraint_args(cd)
+    cd.add_argument("--persist-conditional", dest="persist_conditional", type=int, nargs="?", const=64, default=None,
+                    help="HIP path: batches of up to N rows (systems x width; bare flag: 64) run as one persistent "
+                         "launch instead of the recorded graph, constraints included (opt-in; docs/DESIGN.md §4j)")
     cd.add_argument("--draw", type=int, default=None, help="print K names per prefix drawn from the weighted pool instead")
     cd.add_argument("--out", default=None, help="prefix, index, name and weight per line, tab-separated")
     cd.add_argument("--cpu", action="store_true", help="cpu_ref.sample_conditional in fp32 instead of the HIP generator")

@@ -316,6 +316,10 @@ PYBIND11_MODULE(_C, m) {
       .def("set_persist_distinct_max", &Generator::set_persist_distinct_max)
       .def("distinct_last_persist", &Generator::distinct_last_persist)
       .def("persist_distinct_launches", &Generator::persist_distinct_launches)
+      .def("uses_persist_conditional", &Generator::uses_persist_conditional)
+      .def("set_persist_conditional_max", &Generator::set_persist_conditional_max)
+      .def("conditional_last_persist", &Generator::conditional_last_persist)
+      .def("persist_conditional_launches", &Generator::persist_conditional_launches)
       .def("uses_persist_score", &Generator::uses_persist_score)
       .def("set_persist_score_max", &Generator::set_persist_score_max)
       .def("score_last_persist", &Generator::score_last_persist)
@@ -972,6 +976,36 @@ PYBIND11_MODULE(_C, m) {
     a.n_tok = GP(int, d, "n_tok"); a.n_found = GP(int, d, "n_found");
     a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
     gen_persist_sbs_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the persistent small-call sequential Monte Carlo on caller-owned buffers (tests/test_smc_persist_gpu.py)
+  m.def("gen_persist_smc_supported", &gen_persist_smc_supported);
+  m.def("gen_persist_smc_ws_floats", &gen_persist_smc_ws_floats);
+  m.def("gen_persist_smc_sync_words", &gen_persist_smc_sync_words);
+  m.def("gen_persist_smc", [](py::dict d, uintptr_t s) {
+    GenPersistSmcArgs a;
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.H = get<int>(d, "H", 0); a.L = get<int>(d, "L", 0);
+    a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    // (before the pointer lists: an unsupported shape throws whatever else the dict holds)
+    if (!gen_persist_smc_supported(a.H, a.L, a.V, a.N, a.W, a.ML))
+      throw std::runtime_error("gen_persist_smc: unsupported shape or device (see gen_persist_smc_supported)");
+    auto ptrs = [&](const char* k, const float* (&dst)[4], int first) {
+      const auto v = get<std::vector<uintptr_t>>(d, k, {});
+      if ((int)v.size() != a.L) throw std::runtime_error(std::string("gen_persist_smc: ") + k + " needs L pointers");
+      for (int l = first; l < a.L; ++l) dst[l] = Pp<const float>(v[l]);
+    };
+    ptrs("Whh", a.Whh, 0); ptrs("bhh", a.bhh, 0); ptrs("Wih", a.Wih, 1); ptrs("bih", a.bih, 1);
+    a.Wfc = GP(const float, d, "Wfc"); a.bfc = GP(const float, d, "bfc"); a.P = GP(const float, d, "P");
+    a.plen = GP(const int, d, "plen"); a.prefix = GP(const unsigned char, d, "prefix");
+    a.inv_t = GP(const float, d, "inv_t"); a.thr = get<float>(d, "thr", 0.5f);
+    a.seed = get<unsigned long long>(d, "seed", 0); a.start = get<unsigned long long>(d, "start", 0);
+    a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
+    a.allow_next = GP(const unsigned short, d, "allow_next"); a.allow_start = GP(const int, d, "allow_start");
+    a.allow_rows = get<int>(d, "allow_rows", 0);
+    a.rows = GP(unsigned char, d, "rows"); a.logw = GP(float, d, "logw"); a.logq = GP(float, d, "logq");
+    a.n_tok = GP(int, d, "n_tok"); a.n_res = GP(int, d, "n_res");
+    a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
+    gen_persist_smc_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   // the persistent small-batch score on caller-owned buffers (tests/test_score_persist_gpu.py)

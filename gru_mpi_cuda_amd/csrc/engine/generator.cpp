@@ -67,6 +67,7 @@ Generator::Generator(const GenDims& d, const float* params, const std::map<std::
   if (const char* cm = std::getenv("GK_GEN_PERSIST_BEAM_MAX")) persist_beam_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_SCORE_MAX")) persist_score_max_ = std::atoi(cm);
   if (const char* cm = std::getenv("GK_GEN_PERSIST_DISTINCT_MAX")) persist_distinct_max_ = std::atoi(cm);
+  if (const char* cm = std::getenv("GK_GEN_PERSIST_CONDITIONAL_MAX")) persist_conditional_max_ = std::atoi(cm);
 }
 
 bool Generator::uses_persist(int n) const {
@@ -114,6 +115,13 @@ bool Generator::uses_persist_distinct(int n, int W) const {
   return gen_persist_sbs_supported(d_.H, d_.L, d_.V, n, W, d_.max_len);
 }
 
+bool Generator::uses_persist_conditional(int n, int W) const {
+  // opt-in (persist_conditional_max_ = 0 by default): docs/DESIGN.md §4j has the measurement.  The weights are
+  // the fp32 masters in every mode, as on the conditional graph
+  if (!persist_ || n < 1 || W < 1 || (long)n * W > std::min(persist_conditional_max_, 64)) return false;
+  return gen_persist_smc_supported(d_.H, d_.L, d_.V, n, W, d_.max_len);
+}
+
 bool Generator::uses_persist_score(int n) const {
   // opt-in (persist_score_max_ = 0 by default): docs/DESIGN.md §4a has the measurement.  The weights are the
   // fp32 masters in every mode, as on the score graph
@@ -146,7 +154,7 @@ Generator::~Generator() {
     if (p) (void)hipFree(p);
   for (void* p : {(void*)dG_[0], (void*)dG_[1], (void*)dinv_, (void*)dwords_, (void*)pdws_, (void*)pdsync_})
     if (p) (void)hipFree(p);
-  for (void* p : {(void*)qw_[0], (void*)qw_[1], (void*)qinv_, (void*)qres_, (void*)qwords_})
+  for (void* p : {(void*)qw_[0], (void*)qw_[1], (void*)qinv_, (void*)qres_, (void*)qwords_, (void*)pqws_, (void*)pqsync_})
     if (p) (void)hipFree(p);
   if (cap_) (void)hipStreamDestroy(cap_);
   if (err_pin_) (void)hipHostFree(err_pin_);
@@ -1279,8 +1287,55 @@ void Generator::conditional(const int* plen, const unsigned char* prefix, int N,
   const int ar = masked ? allow_rows : 0;
   if (masked && !aut)   // the table once per call
     HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
-  for (int b0 = 0; b0 < N; b0 += nb) {
-    const int n = std::min(nb, N - b0);
+  for (int b0 = 0, n = 0; b0 < N; b0 += n) {
+    // opt-in: floor(rows / W) systems as one persistent launch on the caller's arrays and tables (no staging
+    // copies); system i of the batch draws at start + b0 + i, as on the graph, so the batches do not show in
+    // the bytes
+    n = std::min(std::min(persist_conditional_max_, 64) / W, N - b0);
+    if (n >= 1 && uses_persist_conditional(n, W)) {
+      if (!pqws_) {   // the first such launch: its exchange buffers and flags (zeroed once, self-cleaning)
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pqws_), (size_t)gen_persist_smc_ws_floats(d_.H, d_.L, d_.V, ML) * 4));
+        const size_t sb = (size_t)gen_persist_smc_sync_words(d_.L) * 4;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pqsync_), sb));
+        HIP_CHECK(hipMemset(pqsync_, 0, sb));
+      }
+      GenPersistSmcArgs a;
+      for (int l = 0; l < d_.L; ++l) {
+        const std::string k = std::to_string(l);
+        a.Whh[l] = P("weight_hh_l" + k); a.bhh[l] = P("bias_hh_l" + k);
+        if (l > 0) { a.Wih[l] = P("weight_ih_l" + k); a.bih[l] = P("bias_ih_l" + k); }
+      }
+      a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_;
+      a.plen = plen + b0; a.prefix = prefix + (size_t)b0 * ML; a.inv_t = inv_t + b0;
+      a.seed = seed; a.start = start + (unsigned long long)b0; a.thr = thr;
+      if (masked) { a.allow_tab = allow_tab; a.allow_rows = allow_rows; }
+      if (aut) { a.allow_next = allow_next; a.allow_start = allow_start + b0; }
+      else if (masked) a.allow_idx = allow_idx + (size_t)b0 * ML;
+      const size_t r0 = (size_t)b0 * W;
+      a.rows = rows + r0 * (ML + 1); a.logw = logw + r0; a.logq = logq + r0; a.n_tok = n_tok + r0;
+      a.n_res = n_res + b0;
+      a.ws = pqws_; a.sync = pqsync_; a.err = err_;
+      a.N = n; a.W = W; a.H = d_.H; a.L = d_.L; a.V = d_.V; a.ML = ML; a.sos = d_.sos; a.eos = d_.eos;
+      gen_persist_smc_f32(a, s);
+      HIP_LAUNCH_CHECK();
+      ++persist_conditional_launches_;
+      // as in distinct(): a spin timeout means the workgroups were not co-resident; the batch's output is
+      // garbage, so stop using the persistent path and run the batch on the graph
+      HIP_CHECK(hipMemcpyAsync(err_pin_, err_, 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      const unsigned e = *reinterpret_cast<volatile unsigned*>(err_pin_);
+      if (!(e & 32u)) {
+        conditional_last_persist_ = true;
+        continue;
+      }
+      std::fprintf(stderr, "[generator] persistent conditional launch hit its spin limit (error word %u): "
+                           "disabling it, running %d systems on the per-char graph\n", e, n);
+      persist_ = false;
+      const unsigned keep = e & ~32u;
+      HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
+    }
+    conditional_last_persist_ = false;
+    n = std::min(nb, N - b0);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)b0 * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(qinv_, inv_t + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));

@@ -183,6 +183,18 @@ class Generator {
                    const int* allow_idx = nullptr, int allow_rows = 0, const unsigned short* allow_next = nullptr,
                    const int* allow_start = nullptr);
   int conditional_graphs() const { return (int)(qgraphs_.size() + aqgraphs_.size()); }   // recordings so far
+  // conditional() batches of n systems x W slots run as ONE persistent launch (gen_persist_smc.hip,
+  // docs/DESIGN.md §4j) instead of the recorded graph, constraints included (the caller's tables are read in
+  // place): up to n W <= GK_GEN_PERSIST_CONDITIONAL_MAX / set_persist_conditional_max(rows) rows, at most 64 --
+  // 0 by default, the path is opt-in -- where a variant exists for the shape (gen_persist_smc_supported) and
+  // the persistent path is on (set_persist).  A batch is then floor(rows / W) systems, read from and written
+  // to the caller's arrays (system n still draws at start + n: the bytes do not depend on the batches); its
+  // workspace is a plain allocation made by the first such launch.  A launch that hits its spin limit turns
+  // the persistent path off and the batch runs on the graph.
+  bool uses_persist_conditional(int n, int W) const;
+  void set_persist_conditional_max(int rows) { persist_conditional_max_ = rows; }
+  bool conditional_last_persist() const { return conditional_last_persist_; }   // the path of the last conditional() batch
+  long persist_conditional_launches() const { return persist_conditional_launches_; }
   // Unconstrained beam() batches of n prefixes x W beams run as ONE persistent launch (gen_persist_beam.hip,
   // docs/DESIGN.md §4d) instead of the recorded graph: up to n W <= GK_GEN_PERSIST_BEAM_MAX /
   // set_persist_beam_max(rows) rows, at most 64 -- 0 by default, the path is opt-in -- where a variant exists
@@ -376,6 +388,11 @@ class Generator {
   float* qinv_ = nullptr;                       // [Bmax] the current batch's 1 / T
   int* qres_ = nullptr;                         // [Bmax] the current batch's resampling steps per name
   unsigned long long* qwords_ = nullptr;        // [4] the call's seed, the batch's first global index, the ESS threshold
+  int persist_conditional_max_ = 0;             // rows per persistent conditional launch (GK_GEN_PERSIST_CONDITIONAL_MAX): opt-in
+  bool conditional_last_persist_ = false;
+  long persist_conditional_launches_ = 0;
+  float* pqws_ = nullptr;                       // persistent conditional launch: exchange buffers (made by its first launch)
+  unsigned* pqsync_ = nullptr;                  // ... flags + done counter (zeroed once, self-cleaning)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> qgraphs_;    // keyed by (names, W, table lines or 0)
   std::map<std::tuple<int, int, int>, std::unique_ptr<Graph>> aqgraphs_;   // keyed by (names, W, states)
   // automaton constraints (plain allocations, made by the first automaton call and grown on demand)

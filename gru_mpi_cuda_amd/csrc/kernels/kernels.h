@@ -632,6 +632,44 @@ bool gen_persist_sbs_supported(int H, int L, int V, int N, int W, int ML);
 long gen_persist_sbs_ws_floats(int H, int L, int V, int ML);
 long gen_persist_sbs_sync_words(int L);
 void gen_persist_sbs_f32(const GenPersistSbsArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// Sequential Monte Carlo under constraints for small calls as ONE persistent launch (gen_persist_smc.hip,
+// docs/DESIGN.md §4j): N systems x W slots = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the
+// selection (smc_select_f32's rule, order and arithmetic), the constraints (the caller's tables, read in place:
+// allow_tab + allow_idx per position, or allow_tab + allow_next + allow_start for an automaton, or none) and
+// the gather by ancestor inside the launch.  System n draws its noise at the global index start + n under
+// seed.  Outputs in Generator::conditional's layout, written by workgroup n for system n.  `ws` is laid out as
+// GenPersistSbsArgs'; a record's words: (ancestor + 1) | (char + 1) << 6 | state << 16, the automaton state,
+// the new slot's logq and logw.  It needs no fill; `sync` is all zero again after every launch.  err as
+// GenPersistBeamArgs' (bit 16: a prefix char, a line or a state out of range, clamped).
+struct GenPersistSmcArgs {
+  const float* Whh[4] = {}; const float* Wih[4] = {};   // [3H][H] (Wih[0] unused: folded into P)
+  const float* bhh[4] = {}; const float* bih[4] = {};   // [3H]
+  const float* Wfc = nullptr; const float* bfc = nullptr;   // [V][H], [V]
+  const float* P = nullptr;                // [V][3H] layer-0 table Emb W_ih0^T + b_ih0
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][ML]
+  const float* inv_t = nullptr;            // [N] 1 / temperature
+  const unsigned* allow_tab = nullptr;     // nullable [allow_rows][V / 32]: bit c of a line = char c allowed
+  const int* allow_idx = nullptr;          // per position: [N][ML] lines
+  const unsigned short* allow_next = nullptr;   // automaton: [allow_rows][V] transitions
+  const int* allow_start = nullptr;        // automaton: [N] start states
+  unsigned char* rows = nullptr;           // [N][W][ML + 1]
+  float* logw = nullptr;                   // [N][W] log importance weights
+  float* logq = nullptr;                   // [N][W]
+  int* n_tok = nullptr;                    // [N][W]
+  int* n_res = nullptr;                    // [N] resampling steps
+  float* ws = nullptr;                     // gen_persist_smc_ws_floats()
+  unsigned* sync = nullptr;                // gen_persist_smc_sync_words(): zeroed once, self-cleaning
+  unsigned* err = nullptr;
+  unsigned long long seed = 0, start = 0;
+  float thr = 0.5f;                        // resample when ESS < thr W
+  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0, allow_rows = 0;
+};
+// gen_persist_beam_supported's family, with this kernel's own list of instances (each has scratch 0)
+bool gen_persist_smc_supported(int H, int L, int V, int N, int W, int ML);
+long gen_persist_smc_ws_floats(int H, int L, int V, int ML);
+long gen_persist_smc_sync_words(int L);
+void gen_persist_smc_f32(const GenPersistSmcArgs& a, hipStream_t s);   // throws before launching what is unsupported
 // Teacher-forced scoring of output rows (score.hip).  A row's token count n_tok = index of the first
 // EOS byte among its first ML bytes + 1, else ML; step l < n_tok has input SOS (l = 0) or c[l-1] and
 // target c[l].

@@ -20,16 +20,14 @@
 #include "kernels.h"
 #include "common.h"
 #include "gen_sample.h"
+#include "smc_dev.h"   // the state values and smc_unit (shared with gen_persist_smc.hip)
 
 #pragma clang fp contract(off)
 
 namespace gk {
 
 namespace {
-constexpr int kDead = 0, kLive = 1, kFin = 2;   // SmcSelectArgs::state values (BeamSelectArgs')
 constexpr int kMaxWaves = 16;
-
-DEV float smc_unit(unsigned word) { return (float)(2u * (word >> 9) + 1u) * 0x1p-24f; }   // exact, in [2^-24, 1 - 2^-24]
 }  // namespace
 
 // R: slot rows per wave (wave w owns slots w and w + nw), MAXPER: logits per lane and row

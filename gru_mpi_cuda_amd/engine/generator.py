@@ -55,7 +55,10 @@ class HipGenerator:
     the shape has a variant.
     ``persist_distinct`` = N (opt-in, default 0; docs/DESIGN.md §4i): unconstrained ``sample_distinct`` batches
     of up to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph,
-    where the shape has a variant; ``sample_conditional`` keeps the graph.
+    where the shape has a variant.
+    ``persist_conditional`` = N (opt-in, default 0; docs/DESIGN.md §4j): ``sample_conditional`` batches of up to
+    N rows (systems x width, at most 64) run as one persistent launch instead of the recorded graph, constraints
+    included, where the shape has a variant.
     ``persist_score`` = N (opt-in, default 0; docs/DESIGN.md §4a): a plain ``score`` call of up to N rows (at
     most 64) runs as one persistent launch instead of the recorded graph, where the shape has a variant; larger
     calls and calls with controls, constraints or soft terms keep the graph."""
@@ -63,7 +66,7 @@ class HipGenerator:
     def __init__(self, cfg: GRUConfig, params: Dict[str, torch.Tensor], max_batch: int = 4096,
                  device: Optional[torch.device] = None, flat: Optional[torch.Tensor] = None,
                  precision: str = "fp32", persist_constraints: int = 0, persist_soft: int = 0, persist_beam: int = 0,
-                 persist_score: int = 0, persist_distinct: int = 0):
+                 persist_score: int = 0, persist_distinct: int = 0, persist_conditional: int = 0):
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}")
         self.precision = precision
@@ -92,6 +95,16 @@ class HipGenerator:
         self.set_persist_beam(persist_beam)
         self.set_persist_score(persist_score)
         self.set_persist_distinct(persist_distinct)
+        self.set_persist_conditional(persist_conditional)
+
+    def set_persist_conditional(self, n: int) -> None:
+        """``sample_conditional`` batches of up to ``n`` rows (systems x width) take the persistent launch where
+        the shape has one (``g.uses_persist_conditional``); 0 turns it off (the default).  After a call
+        ``g.conditional_last_persist()`` tells which path its last batch took."""
+        n = int(n)
+        if n < 0 or n > 64:
+            raise ValueError(f"persist_conditional must be in [0, 64], got {n}")
+        self.g.set_persist_conditional_max(n)
 
     def set_persist_distinct(self, n: int) -> None:
         """Unconstrained ``sample_distinct`` batches of up to ``n`` rows (prefixes x width) take the persistent
@@ -397,7 +410,9 @@ class HipGenerator:
 
         ``runs`` independent systems of ``width`` <= 32 particles per prefix are pooled (run r of prefix n draws
         its noise at the global index ``start + n * runs + r`` under ``seed``: the result does not depend on
-        how a job is cut into calls or batches).  ``exp(result.log_z)`` is an unbiased estimate of P(rule |
+        how a job is cut into calls or batches).  With ``persist_conditional`` set, batches of
+        floor(persist_conditional / width) systems run as one persistent launch each (docs/DESIGN.md §4j).
+        ``exp(result.log_z)`` is an unbiased estimate of P(rule |
         prefix) at any width; ``weights`` / ``expectation`` / ``draw`` are self-normalised: consistent, with a
         bias of order 1 / particles.  Always exact fp32 arithmetic; precision "bf16" is refused (ValueError),
         as are top_k, top_p, temperature 0 and the soft controls, before anything is launched."""
