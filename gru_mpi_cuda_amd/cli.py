@@ -465,8 +465,10 @@ def cmd_beam(args) -> int:
     else:
         if args.persist_beam is not None and not 0 <= args.persist_beam <= 64:
             raise SystemExit("--persist-beam needs a row count in [0, 64]")
+        if args.persist_constraints is not None and args.persist_constraints < 0:
+            raise SystemExit("--persist-constraints needs a count >= 0")
         gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
-                             persist_beam=args.persist_beam or 0)
+                             persist_beam=args.persist_beam or 0, persist_constraints=args.persist_constraints or 0)
         res = gen.beam_search(prefixes, args.width, constraints=_constraints_from(args))
     lines = []
     for pre, names, lps in zip(prefixes, res.names(), res.logp):
@@ -507,8 +509,10 @@ def cmd_distinct(args) -> int:
     else:
         if args.persist_distinct is not None and not 0 <= args.persist_distinct <= 64:
             raise SystemExit("--persist-distinct needs a row count in [0, 64]")
+        if args.persist_constraints is not None and args.persist_constraints < 0:
+            raise SystemExit("--persist-constraints needs a count >= 0")
         gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
-                             persist_distinct=args.persist_distinct or 0)
+                             persist_distinct=args.persist_distinct or 0, persist_constraints=args.persist_constraints or 0)
         res = gen.sample_distinct(prefixes, args.width, **kw)
     lines = []
     for pre, names, lqs in zip(prefixes, res.names(), res.logq):
@@ -710,8 +714,13 @@ def main(argv=None) -> int:
     bm.add_argument("--prefix-file", dest="prefix_file", default=None, help="one prefix per line")
     _constraint_args(bm)
     bm.add_argument("--persist-beam", dest="persist_beam", type=int, nargs="?", const=64, default=None,
-                    help="HIP path: unconstrained batches of up to N rows (prefixes x width; bare flag: 64) run as one "
-                         "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4d)")
+                    help="HIP path: batches of up to N rows (prefixes x width; bare flag: 64) run as one persistent "
+                         "launch instead of the recorded graph (opt-in; docs/DESIGN.md §4d); constrained ones with "
+                         "--persist-constraints")
+    bm.add_argument("--persist-constraints", dest="persist_constraints", type=int, nargs="?", const=64, default=None,
+                    metavar="N", help="HIP path: a constrained batch takes the persistent launch of --persist-beam when "
+                                      "this covers its rows too (bare flag: 64; opt-in; docs/DESIGN.md §4d); no "
+                                      "effect with --cpu")
     bm.add_argument("--out", default=None, help="prefix, rank, name and log-prob per line, tab-separated")
     bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
     bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
@@ -725,8 +734,13 @@ def main(argv=None) -> int:
     ds.add_argument("--temperature", type=float, default=None, help="softmax temperature, > 0 (default 1)")
     _constraint_args(ds)
     ds.add_argument("--persist-distinct", dest="persist_distinct", type=int, nargs="?", const=64, default=None,
-                    help="HIP path: unconstrained batches of up to N rows (prefixes x width; bare flag: 64) run as one "
-                         "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4i)")
+                    help="HIP path: batches of up to N rows (prefixes x width; bare flag: 64) run as one persistent "
+                         "launch instead of the recorded graph (opt-in; docs/DESIGN.md §4i); constrained ones with "
+                         "--persist-constraints")
+    ds.add_argument("--persist-constraints", dest="persist_constraints", type=int, nargs="?", const=64, default=None,
+                    metavar="N", help="HIP path: a constrained batch takes the persistent launch of --persist-distinct when "
+                                      "this covers its rows too (bare flag: 64; opt-in; docs/DESIGN.md §4i); no "
+                                      "effect with --cpu")
     ds.add_argument("--out", default=None, help="prefix, draw, name and log-prob per line, tab-separated")
     ds.add_argument("--cpu", action="store_true", help="cpu_ref.sample_distinct in fp32 instead of the HIP generator")
     ds.add_argument("--seed", dest="noise_seed", type=int, default=0,

@@ -928,6 +928,7 @@ PYBIND11_MODULE(_C, m) {
   });
   // the persistent small-batch beam search on caller-owned buffers (tests/test_beam_persist_gpu.py)
   m.def("gen_persist_beam_supported", &gen_persist_beam_supported);
+  m.def("gen_persist_beam_con_supported", &gen_persist_beam_con_supported);   // (..., mode: 1 per position, 2 automaton)
   m.def("gen_persist_beam_ws_floats", &gen_persist_beam_ws_floats);
   m.def("gen_persist_beam_sync_words", &gen_persist_beam_sync_words);
   m.def("gen_persist_beam", [](py::dict d, uintptr_t s) {
@@ -935,7 +936,9 @@ PYBIND11_MODULE(_C, m) {
     a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.H = get<int>(d, "H", 0); a.L = get<int>(d, "L", 0);
     a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
     // (before the pointer lists: an unsupported shape throws whatever else the dict holds)
-    if (!gen_persist_beam_supported(a.H, a.L, a.V, a.N, a.W, a.ML))
+    const int con_mode = get<int>(d, "con_mode", kGenConNone);   // the rule the allow_* pointers below will hold
+    if (!gen_persist_beam_supported(a.H, a.L, a.V, a.N, a.W, a.ML) ||
+        (con_mode != kGenConNone && !gen_persist_beam_con_supported(a.H, a.L, a.V, a.N, a.W, a.ML, con_mode)))
       throw std::runtime_error("gen_persist_beam: unsupported shape or device (see gen_persist_beam_supported)");
     auto ptrs = [&](const char* k, const float* (&dst)[4], int first) {
       const auto v = get<std::vector<uintptr_t>>(d, k, {});
@@ -947,12 +950,17 @@ PYBIND11_MODULE(_C, m) {
     a.plen = GP(const int, d, "plen"); a.prefix = GP(const unsigned char, d, "prefix");
     a.rows = GP(unsigned char, d, "rows"); a.logp = GP(float, d, "logp"); a.n_tok = GP(int, d, "n_tok");
     a.n_beams = GP(int, d, "n_beams");
+    a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
+    a.allow_next = GP(const unsigned short, d, "allow_next"); a.allow_start = GP(const int, d, "allow_start");
+    a.allow_rows = get<int>(d, "allow_rows", 0);
+    if (gen_persist_beam_con_mode(a) != con_mode) throw std::runtime_error("gen_persist_beam: con_mode and the allow_* pointers disagree");
     a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
     gen_persist_beam_f32(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   // the persistent small-call stochastic beam search on caller-owned buffers (tests/test_sbs_persist_gpu.py)
   m.def("gen_persist_sbs_supported", &gen_persist_sbs_supported);
+  m.def("gen_persist_sbs_con_supported", &gen_persist_sbs_con_supported);   // (..., mode: 1 per position, 2 automaton)
   m.def("gen_persist_sbs_ws_floats", &gen_persist_sbs_ws_floats);
   m.def("gen_persist_sbs_sync_words", &gen_persist_sbs_sync_words);
   m.def("gen_persist_sbs", [](py::dict d, uintptr_t s) {
@@ -960,7 +968,9 @@ PYBIND11_MODULE(_C, m) {
     a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.H = get<int>(d, "H", 0); a.L = get<int>(d, "L", 0);
     a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0); a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
     // (before the pointer lists: an unsupported shape throws whatever else the dict holds)
-    if (!gen_persist_sbs_supported(a.H, a.L, a.V, a.N, a.W, a.ML))
+    const int con_mode = get<int>(d, "con_mode", kGenConNone);   // the rule the allow_* pointers below will hold
+    if (!gen_persist_sbs_supported(a.H, a.L, a.V, a.N, a.W, a.ML) ||
+        (con_mode != kGenConNone && !gen_persist_sbs_con_supported(a.H, a.L, a.V, a.N, a.W, a.ML, con_mode)))
       throw std::runtime_error("gen_persist_sbs: unsupported shape or device (see gen_persist_sbs_supported)");
     auto ptrs = [&](const char* k, const float* (&dst)[4], int first) {
       const auto v = get<std::vector<uintptr_t>>(d, k, {});
@@ -974,6 +984,10 @@ PYBIND11_MODULE(_C, m) {
     a.seed = get<unsigned long long>(d, "seed", 0); a.start = get<unsigned long long>(d, "start", 0);
     a.rows = GP(unsigned char, d, "rows"); a.logq = GP(float, d, "logq"); a.gumbel = GP(float, d, "gumbel");
     a.n_tok = GP(int, d, "n_tok"); a.n_found = GP(int, d, "n_found");
+    a.allow_tab = GP(const unsigned, d, "allow_tab"); a.allow_idx = GP(const int, d, "allow_idx");
+    a.allow_next = GP(const unsigned short, d, "allow_next"); a.allow_start = GP(const int, d, "allow_start");
+    a.allow_rows = get<int>(d, "allow_rows", 0);
+    if (gen_persist_sbs_con_mode(a) != con_mode) throw std::runtime_error("gen_persist_sbs: con_mode and the allow_* pointers disagree");
     a.ws = GP(float, d, "ws"); a.sync = GP(unsigned, d, "sync"); a.err = GP(unsigned, d, "err");
     gen_persist_sbs_f32(a, S(s));
     HIP_LAUNCH_CHECK();

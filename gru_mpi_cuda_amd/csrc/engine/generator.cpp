@@ -1045,17 +1045,18 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
     throw std::runtime_error("Generator::beam: constraints need allow_tab, allow_idx and 1 <= allow_rows <= 1024");
   if (N <= 0) return;
   beam_alloc();   // first call: allocates (and synchronises) before anything is captured
-  if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);   // the tables once per call
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in generate()
   err_clean_ = false;
   const int nb = d_.max_batch / W, fin = ML & 1;
   const int ar = masked ? allow_rows : 0;
-  if (masked && !aut)   // the table once per call
-    HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+  const int mode = aut ? kGenConAuto : masked ? kGenConMask : kGenConNone;
+  bool staged = false;   // the graph's copies of the tables: once per call, by the first batch that takes the graph
   for (int start = 0; start < N;) {
-    // opt-in: floor(rows / W) prefixes as one persistent launch on the caller's arrays (no staging copies)
-    const int np = masked ? 0 : std::min(std::min(persist_beam_max_, 64) / W, N - start);
-    if (np >= 1 && uses_persist_beam(np, W)) {
+    // opt-in: floor(rows / W) prefixes as one persistent launch on the caller's arrays and tables (no staging
+    // copies); a constrained batch needs persist_constraints to cover its rows too, and a constrained instance
+    const int np = std::min(std::min(persist_beam_max_, 64) / W, N - start);
+    if (np >= 1 && uses_persist_beam(np, W) &&
+        (!masked || (np * W <= persist_con_max_ && gen_persist_beam_con_supported(d_.H, d_.L, d_.V, np, W, ML, mode)))) {
       GenPersistBeamArgs a;
       for (int l = 0; l < d_.L; ++l) {
         const std::string k = std::to_string(l);
@@ -1064,6 +1065,9 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
       }
       a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_;
       a.plen = plen + start; a.prefix = prefix + (size_t)start * ML;
+      if (masked) { a.allow_tab = allow_tab; a.allow_rows = allow_rows; }   // the batch's own prefixes' lines / starts
+      if (aut) { a.allow_next = allow_next; a.allow_start = allow_start + start; }
+      else if (masked) a.allow_idx = allow_idx + (size_t)start * ML;
       const size_t r0 = (size_t)start * W;
       a.rows = rows + r0 * (ML + 1); a.logp = logp + r0; a.n_tok = n_tok + r0; a.n_beams = n_beams + start;
       a.ws = pbws_; a.sync = pbsync_; a.err = err_;
@@ -1088,6 +1092,11 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
       HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
     }
     beam_last_persist_ = false;
+    if (!staged) {
+      if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);
+      else if (masked) HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+      staged = true;
+    }
     const int n = std::min(nb, N - start);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
@@ -1156,18 +1165,19 @@ void Generator::distinct(const int* plen, const unsigned char* prefix, int N, in
   if (N <= 0) return;
   beam_alloc();       // first call: allocates (and synchronises) before anything is captured
   distinct_alloc();
-  if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);   // the tables once per call
   HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));
   err_clean_ = false;
   const int nb = d_.max_batch / W, fin = ML & 1;
   const int ar = masked ? allow_rows : 0;
-  if (masked && !aut)   // the table once per call
-    HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+  const int mode = aut ? kGenConAuto : masked ? kGenConMask : kGenConNone;
+  bool staged = false;   // the graph's copies of the tables: once per call, by the first batch that takes the graph
   for (int b0 = 0, n = 0; b0 < N; b0 += n) {
-    // opt-in: floor(rows / W) prefixes as one persistent launch on the caller's arrays (no staging copies);
-    // name i of the batch draws at start + b0 + i, as on the graph, so the batches do not show in the bytes
-    n = masked ? 0 : std::min(std::min(persist_distinct_max_, 64) / W, N - b0);
-    if (n >= 1 && uses_persist_distinct(n, W)) {
+    // opt-in: floor(rows / W) prefixes as one persistent launch on the caller's arrays and tables (no staging
+    // copies); name i of the batch draws at start + b0 + i, as on the graph, so the batches do not show in the
+    // bytes.  A constrained batch needs persist_constraints to cover its rows too, and a constrained instance
+    n = std::min(std::min(persist_distinct_max_, 64) / W, N - b0);
+    if (n >= 1 && uses_persist_distinct(n, W) &&
+        (!masked || (n * W <= persist_con_max_ && gen_persist_sbs_con_supported(d_.H, d_.L, d_.V, n, W, ML, mode)))) {
       if (!pdws_) {   // the first such launch: its exchange buffers and flags (zeroed once, self-cleaning)
         HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&pdws_), (size_t)gen_persist_sbs_ws_floats(d_.H, d_.L, d_.V, ML) * 4));
         const size_t sb = (size_t)gen_persist_sbs_sync_words(d_.L) * 4;
@@ -1183,6 +1193,9 @@ void Generator::distinct(const int* plen, const unsigned char* prefix, int N, in
       a.Wfc = P("fc.weight"); a.bfc = P("fc.bias"); a.P = Ptab32_;
       a.plen = plen + b0; a.prefix = prefix + (size_t)b0 * ML; a.inv_t = inv_t + b0;
       a.seed = seed; a.start = start + (unsigned long long)b0;
+      if (masked) { a.allow_tab = allow_tab; a.allow_rows = allow_rows; }   // the batch's own prefixes' lines / starts
+      if (aut) { a.allow_next = allow_next; a.allow_start = allow_start + b0; }
+      else if (masked) a.allow_idx = allow_idx + (size_t)b0 * ML;
       const size_t r0 = (size_t)b0 * W;
       a.rows = rows + r0 * (ML + 1); a.logq = logq + r0; a.gumbel = gumbel + r0; a.n_tok = n_tok + r0;
       a.n_found = n_found + b0;
@@ -1207,6 +1220,11 @@ void Generator::distinct(const int* plen, const unsigned char* prefix, int N, in
       HIP_CHECK(hipMemcpy(err_, &keep, 4, hipMemcpyHostToDevice));
     }
     distinct_last_persist_ = false;
+    if (!staged) {
+      if (aut) automaton_stage(allow_tab, allow_next, allow_rows, s);
+      else if (masked) HIP_CHECK(hipMemcpyAsync(btab_, allow_tab, (size_t)ar * (d_.V / 32) * 4, hipMemcpyDeviceToDevice, s));
+      staged = true;
+    }
     n = std::min(nb, N - b0);
     HIP_CHECK(hipMemcpyAsync(bplen_, plen + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(bprefix_, prefix + (size_t)b0 * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));

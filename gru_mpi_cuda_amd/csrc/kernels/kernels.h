@@ -571,7 +571,7 @@ long gen_persist_sync_words(int L);
 void gen_persist_f32(const GenPersistArgs& a, hipStream_t s);
 // Beam search for small batches as ONE persistent launch (gen_persist_beam.hip, docs/DESIGN.md §4d):
 // N prefixes x W beams = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the selection
-// (beam_select_f32's rule and arithmetic, no constraints) and the gather by parent inside the launch.
+// (beam_select_f32's rule and arithmetic) and the gather by parent inside the launch.
 // Outputs in Generator::beam's layout, written by workgroup n for prefix n.  `ws` holds, in floats:
 // h_l(t)[row][c] at ((l ML + t) 64 + row) H + c, logits(t)[row][v] at L ML 64 H + (t 64 + row) V + v, and
 // the records of step t < ML - 1 at L ML 64 H + ML 64 V + (t 64 + row) 2: the word (parent + 1) |
@@ -585,6 +585,12 @@ struct GenPersistBeamArgs {
   const float* P = nullptr;                // [V][3H] layer-0 table Emb W_ih0^T + b_ih0
   const int* plen = nullptr;               // [N]
   const unsigned char* prefix = nullptr;   // [N][ML]
+  // constraints (gen_persist_beam_con.hip; all null: none): the caller's tables at this launch's prefixes, in
+  // BeamSelectArgs' layout -- allow_tab + allow_idx per position, or allow_tab + allow_next + allow_start (automaton)
+  const unsigned* allow_tab = nullptr;     // [allow_rows][V / 32]: bit c of a line = char c allowed
+  const int* allow_idx = nullptr;          // per position: [N][ML] lines
+  const unsigned short* allow_next = nullptr;   // automaton: [allow_rows][V] transitions
+  const int* allow_start = nullptr;        // automaton: [N] start states
   unsigned char* rows = nullptr;           // [N][W][ML + 1]
   float* logp = nullptr;                   // [N][W]  -inf for a dead slot
   int* n_tok = nullptr;                    // [N][W]
@@ -592,7 +598,7 @@ struct GenPersistBeamArgs {
   float* ws = nullptr;                     // gen_persist_beam_ws_floats()
   unsigned* sync = nullptr;                // gen_persist_beam_sync_words(): zeroed once, self-cleaning
   unsigned* err = nullptr;
-  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0, allow_rows = 0;
 };
 // N >= 1, 1 <= W <= 32, N W <= 64, H in {256, 512, 1024} with 2 L H / 32 <= 128 weight registers, V = 256
 // or 512, ML <= 64, and all 256 workgroups of the variant resident (each has scratch 0)
@@ -600,9 +606,19 @@ bool gen_persist_beam_supported(int H, int L, int V, int N, int W, int ML);
 long gen_persist_beam_ws_floats(int H, int L, int V, int ML);
 long gen_persist_beam_sync_words(int L);
 void gen_persist_beam_f32(const GenPersistBeamArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// Constraints inside that launch (gen_persist_beam_con.hip, docs/DESIGN.md §4d): beam_select_f32's MASK / AUTO
+// rule on the tables of GenPersistBeamArgs, workspace, records and flags unchanged.  A line or a state outside
+// [0, allow_rows) ORs 16 into err[0] (err[1] = the value, err[2] = the row) and is taken as line 0.
+// gen_persist_beam_con_mode: the rule the fields ask for (kGenConNone / kGenConMask / kGenConAuto; throws on an
+// inconsistent set).  gen_persist_beam_con_supported: gen_persist_beam_supported, and the constrained instance
+// of that mode exists (scratch 0, all workgroups resident); false: the shape keeps the graph.
+// gen_persist_beam_f32 dispatches a constrained launch to gen_persist_beam_con_launch
+int gen_persist_beam_con_mode(const GenPersistBeamArgs& a);
+bool gen_persist_beam_con_supported(int H, int L, int V, int N, int W, int ML, int mode);
+void gen_persist_beam_con_launch(const GenPersistBeamArgs& a, int mode, hipStream_t s);
 // Stochastic beam search for small calls as ONE persistent launch (gen_persist_sbs.hip, docs/DESIGN.md §4i):
 // N prefixes x W slots = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the selection
-// (sbs_select_f32's rule, order and arithmetic, no constraints) and the gather by parent inside the launch.
+// (sbs_select_f32's rule, order and arithmetic) and the gather by parent inside the launch.
 // Name n draws its noise at the global index start + n under seed.  Outputs in Generator::distinct's layout,
 // written by workgroup n for prefix n.  `ws` holds, in floats: h_l(t)[row][c] at ((l ML + t) 64 + row) H + c,
 // logits(t)[row][v] at L ML 64 H + (t 64 + row) V + v, and the records of step t < ML - 1 at L ML 64 H +
@@ -616,6 +632,12 @@ struct GenPersistSbsArgs {
   const int* plen = nullptr;               // [N]
   const unsigned char* prefix = nullptr;   // [N][ML]
   const float* inv_t = nullptr;            // [N] 1 / temperature
+  // constraints (gen_persist_sbs_con.hip; all null: none): the caller's tables at this launch's prefixes, in
+  // SbsSelectArgs' layout -- allow_tab + allow_idx per position, or allow_tab + allow_next + allow_start (automaton)
+  const unsigned* allow_tab = nullptr;     // [allow_rows][V / 32]: bit c of a line = char c allowed
+  const int* allow_idx = nullptr;          // per position: [N][ML] lines
+  const unsigned short* allow_next = nullptr;   // automaton: [allow_rows][V] transitions
+  const int* allow_start = nullptr;        // automaton: [N] start states
   unsigned char* rows = nullptr;           // [N][W][ML + 1]
   float* logq = nullptr;                   // [N][W]  -inf for a dead slot
   float* gumbel = nullptr;                 // [N][W]  -inf for a dead slot
@@ -625,13 +647,18 @@ struct GenPersistSbsArgs {
   unsigned* sync = nullptr;                // gen_persist_sbs_sync_words(): zeroed once, self-cleaning
   unsigned* err = nullptr;
   unsigned long long seed = 0, start = 0;
-  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0;
+  int N = 0, W = 0, H = 0, L = 0, V = 0, ML = 0, sos = 0, eos = 0, allow_rows = 0;
 };
 // gen_persist_beam_supported's family, with this kernel's own list of instances (each has scratch 0)
 bool gen_persist_sbs_supported(int H, int L, int V, int N, int W, int ML);
 long gen_persist_sbs_ws_floats(int H, int L, int V, int ML);
 long gen_persist_sbs_sync_words(int L);
 void gen_persist_sbs_f32(const GenPersistSbsArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// Constraints inside that launch (gen_persist_sbs_con.hip, docs/DESIGN.md §4i): sbs_select_f32's MASK / AUTO rule
+// on the tables of GenPersistSbsArgs; the three functions are gen_persist_beam_con_*'s counterparts
+int gen_persist_sbs_con_mode(const GenPersistSbsArgs& a);
+bool gen_persist_sbs_con_supported(int H, int L, int V, int N, int W, int ML, int mode);
+void gen_persist_sbs_con_launch(const GenPersistSbsArgs& a, int mode, hipStream_t s);
 // Sequential Monte Carlo under constraints for small calls as ONE persistent launch (gen_persist_smc.hip,
 // docs/DESIGN.md §4j): N systems x W slots = N W <= 64 rows on gen_persist_kernel's grid and weight layout, the
 // selection (smc_select_f32's rule, order and arithmetic), the constraints (the caller's tables, read in place:

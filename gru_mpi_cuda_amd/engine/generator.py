@@ -45,17 +45,18 @@ class HipGenerator:
     "bf16": bf16 MFMA fast mode (fused step kernels, bf16 weight copies).
     Small batches run the exact fp32 persistent kernel in both fp32 modes.
     ``persist_constraints`` = N (opt-in, default 0; docs/DESIGN.md §4e): constrained batches of up to N
-    names (at most 64) run as one constrained persistent launch instead of the per-char graph.
+    names (at most 64) run as one constrained persistent launch instead of the per-char graph.  It also gates
+    the constrained ``beam_search`` / ``sample_distinct`` launches below, counted in rows.
     ``persist_soft`` = N (opt-in, default 0; docs/DESIGN.md §4h): soft batches (``logit_bias`` /
     ``presence_penalty`` / ``frequency_penalty``) of up to N names (at most 64) run as one soft persistent
     launch instead of the per-char graph, where the shape has a variant (vocab 256, max_len <= 64); a soft
     batch with constraints needs ``persist_constraints`` to cover it as well.
-    ``persist_beam`` = N (opt-in, default 0; docs/DESIGN.md §4d): unconstrained ``beam_search`` batches of up
-    to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where
-    the shape has a variant.
-    ``persist_distinct`` = N (opt-in, default 0; docs/DESIGN.md §4i): unconstrained ``sample_distinct`` batches
-    of up to N rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph,
-    where the shape has a variant.
+    ``persist_beam`` = N (opt-in, default 0; docs/DESIGN.md §4d): ``beam_search`` batches of up to N rows
+    (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where the shape
+    has a variant; a constrained batch only if ``persist_constraints`` covers its rows as well.
+    ``persist_distinct`` = N (opt-in, default 0; docs/DESIGN.md §4i): ``sample_distinct`` batches of up to N
+    rows (prefixes x width, at most 64) run as one persistent launch instead of the recorded graph, where the
+    shape has a variant; a constrained batch only if ``persist_constraints`` covers its rows as well.
     ``persist_conditional`` = N (opt-in, default 0; docs/DESIGN.md §4j): ``sample_conditional`` batches of up to
     N rows (systems x width, at most 64) run as one persistent launch instead of the recorded graph, constraints
     included, where the shape has a variant.
@@ -135,7 +136,9 @@ class HipGenerator:
 
     def set_persist_constraints(self, n: int) -> None:
         """Constrained batches of up to ``n`` names take the constrained persistent launch where the
-        shape has one (``g.uses_persist_con``); 0 turns it off (the default)."""
+        shape has one (``g.uses_persist_con``); 0 turns it off (the default).  Constrained ``beam_search`` /
+        ``sample_distinct`` batches of up to ``n`` rows may take the launches of ``set_persist_beam`` /
+        ``set_persist_distinct``."""
         n = int(n)
         if n < 0:
             raise ValueError(f"persist_constraints must be >= 0, got {n}")
@@ -328,8 +331,9 @@ class HipGenerator:
         with.  ``constraints`` (a cpu_ref.Constraints for the prefixes, or a dict of
         cpu_ref.make_constraints keywords; docs/DESIGN.md §4e; ``regex`` / ``exclude`` or a cpu_ref.Automaton:
         §4g, a state per beam): the ``width`` most probable rows that satisfy them.  With ``persist_beam`` set,
-        an unconstrained call runs batches of floor(persist_beam / width) prefixes as one persistent launch each
-        (docs/DESIGN.md §4d); a constrained one keeps the graph.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
+        a call runs batches of floor(persist_beam / width) prefixes as one persistent launch each (docs/DESIGN.md
+        §4d); a constrained one does so when ``persist_constraints`` covers the batch's rows too, else
+        that batch keeps the graph.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
         raise ValueError before anything is launched."""
         pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
         N, W, ML = pre.shape[0], int(width), self.cfg.max_len
@@ -363,8 +367,9 @@ class HipGenerator:
         ``score(rows, temperature=, prefix=, constraints=).name_logp`` returns for the rows; ``gumbel`` the
         final perturbed values.  Name n of the call draws its noise at the global index ``start + n`` under
         ``seed``, so the result does not depend on how a job is cut into calls or batches.  With
-        ``persist_distinct`` set, an unconstrained call runs batches of floor(persist_distinct / width) prefixes
-        as one persistent launch each (docs/DESIGN.md §4i).  Always exact fp32
+        ``persist_distinct`` set, a call runs batches of floor(persist_distinct / width) prefixes as one
+        persistent launch each (docs/DESIGN.md §4i); a constrained one does so when ``persist_constraints`` covers
+        the batch's rows too, else it keeps the graph.  Always exact fp32
         arithmetic; precision "bf16" is refused (ValueError), as are top_k, top_p, temperature 0 and the soft
         controls, before anything is launched."""
         if self.precision == "bf16":
