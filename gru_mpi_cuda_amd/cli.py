@@ -152,7 +152,7 @@ def cmd_train(args) -> int:
     data = make_stream(cfg.batch // ctx.world, cfg.seq, cfg.sos, cfg.eos, seed=cfg.seed * 1000 + ctx.rank + start,
                        max_len=cfg.max_len, path=args.data)
     mw = MetricsWriter(args.metrics)
-    evaluate = _Evaluator(args.eval_data, cfg, ctx.device.type == "cuda") if args.eval_data else None
+    evaluate = _Evaluator(args.eval_data, cfg, ctx.device.type == "cuda", args.eval_fast) if args.eval_data else None
     timer = StepTimer()
     for it in range(start, start + args.steps):
         tr.step(*data.next())
@@ -415,15 +415,19 @@ def cmd_score(args) -> int:
     if _constraints_from(args) is not None:
         ctl["constraints"] = _constraints_from(args)
     ctl.update(_soft_from(args, cfg.eos))
+    if args.fast and ctl:
+        raise SystemExit("--fast takes no sampling, constraint or soft flag (they score in exact fp32)")
     t0 = time.perf_counter()
     if args.cpu or not torch.cuda.is_available():
-        out = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows, **ctl)
+        out = cpu_ref.score({k: v.float() for k, v in params.items()}, cfg, rows, round_operands=args.fast, **ctl)
         res = G.ScoreResult(out[0], out[3], out[1], out[2], out[4] if ctl else None)
     else:
         if args.persist_score is not None and not 0 <= args.persist_score <= 64:
             raise SystemExit("--persist-score needs a name count in [0, 64]")
+        # --fast: the bf16 mode holds the operands of the fast schedule (docs/DESIGN.md §4a)
         res = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, rows.shape[0])),
-                             persist_score=args.persist_score or 0).score(rows, **ctl)
+                             precision="bf16" if args.fast else "fp32",
+                             persist_score=args.persist_score or 0).score(rows, fast=args.fast, **ctl)
     dt = time.perf_counter() - t0
     lines = []
     for r, lp, nt in zip(rows, res.name_logp, res.n_tok):
@@ -592,23 +596,26 @@ class _Evaluator:
     """Held-out evaluation for `train --eval-data`: the file is read once; every call scores the
     trainer's current weights on all of it (each rank the whole file: no collective of its own)."""
 
-    def __init__(self, path: str, cfg, on_gpu: bool):
+    def __init__(self, path: str, cfg, on_gpu: bool, fast: bool = False):
         from .engine import generator as G
         self.G, self.cfg, self.gen = G, cfg, None
         self.rows = G.encode_names(_read_names(path), cfg)
         self.on_gpu = on_gpu
+        self.fast = fast   # the bf16 fast scorer (its CPU twin: the oracle with bf16-rounded operands)
 
     def __call__(self, tr) -> dict:
         from .models import cpu_ref
         params = tr.state_dict()           # collective with shard_optim=2: every rank calls it
         if self.on_gpu:
             if self.gen is None:
-                self.gen = self.G.HipGenerator(self.cfg, params, max_batch=max(64, min(4096, self.rows.shape[0])))
+                self.gen = self.G.HipGenerator(self.cfg, params, max_batch=max(64, min(4096, self.rows.shape[0])),
+                                               precision="bf16" if self.fast else "fp32")
             else:
                 self.gen.load_state(params)
-            res = self.gen.score(self.rows)
+            res = self.gen.score(self.rows, fast=self.fast)
         else:
-            tok, name, n_tok, rank = cpu_ref.score({k: v.float() for k, v in params.items()}, self.cfg, self.rows)
+            tok, name, n_tok, rank = cpu_ref.score({k: v.float() for k, v in params.items()}, self.cfg, self.rows,
+                                                   round_operands=self.fast)
             res = self.G.ScoreResult(tok, rank, name, n_tok)
         return dict(eval_nll=res.nll_per_char, eval_ppl=res.perplexity, eval_top1=res.top1,
                     eval_names=int(self.rows.shape[0]))
@@ -643,6 +650,8 @@ def main(argv=None) -> int:
                    help="held-out names file, one per line: scored every --eval-every steps and at the end "
                         "(eval_nll / eval_ppl / eval_top1 in the log line and the metrics record)")
     t.add_argument("--eval-every", dest="eval_every", type=int, default=0)
+    t.add_argument("--eval-fast", dest="eval_fast", action="store_true",
+                   help="held-out evaluation on the bf16 fast scorer (`score --fast`; docs/DESIGN.md §4a)")
     _add_model_args(t)
     t.add_argument("--dropout", type=float, default=None, metavar="P",
                    help="training dropout on the non-recurrent connections, 0 <= P < 1 (default 0: off)")
@@ -667,6 +676,10 @@ def main(argv=None) -> int:
     sc.add_argument("--persist-score", dest="persist_score", type=int, nargs="?", const=64, default=None, metavar="N",
                     help="HIP path: a call of up to N names (bare flag: 64) with no sampling flags runs as one "
                          "persistent launch instead of the recorded graph (opt-in; docs/DESIGN.md §4a)")
+    sc.add_argument("--fast", action="store_true",
+                    help="bf16 fast scoring: bf16 MFMA products with fp32 accumulation and a fused log-softmax head "
+                         "(opt-in, not bit-faithful to fp32; with --cpu: the oracle with bf16-rounded operands; "
+                         "docs/DESIGN.md §4a)")
     sc.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")
     _add_model_args(sc)
     g = sub.add_parser("generate", help="namegen_initialize / namegen / namegen_finalize")

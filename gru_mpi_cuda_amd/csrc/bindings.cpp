@@ -253,6 +253,12 @@ PYBIND11_MODULE(_C, m) {
          py::arg("n_kept") = (uintptr_t)0, py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
          py::arg("allow_rows") = 0, py::arg("soft_tab") = (uintptr_t)0, py::arg("soft_idx") = (uintptr_t)0,
          py::arg("soft_rows") = 0, py::arg("soft_pres") = (uintptr_t)0, py::arg("soft_freq") = (uintptr_t)0)
+      .def("score_fast", [](Generator& g, uintptr_t rows, int N, uintptr_t tok_logp, uintptr_t rank, uintptr_t name_logp,
+                            uintptr_t n_tok, uintptr_t s) {
+        g.score_fast(Pp<const unsigned char>(rows), N, Pp<float>(tok_logp), Pp<int>(rank), Pp<float>(name_logp),
+                     Pp<int>(n_tok), S(s));
+      }, py::arg("rows"), py::arg("N"), py::arg("tok_logp"), py::arg("rank"), py::arg("name_logp"), py::arg("n_tok"),
+         py::arg("stream"))
       .def("score_workspace_bytes", &Generator::score_workspace_bytes)
       .def("score_graphs", &Generator::score_graphs)
       .def("beam", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
@@ -1108,6 +1114,18 @@ PYBIND11_MODULE(_C, m) {
     if (!a.logits || !a.tgt || !a.ntok || !a.tok_logp || !a.rank || !a.name_logp || !a.ntok_out)
       throw std::runtime_error("score_logprob: logits, tgt, ntok, tok_logp, rank, name_logp, ntok_out required");
     score_logprob_f32(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the fast scorer's fused bf16 head on caller-owned buffers (tests/test_score_fast_kernel_gpu.py)
+  m.def("score_head_supported", &score_head_supported);
+  m.def("score_head", [](py::dict d, uintptr_t s) {
+    ScoreHeadArgs a;
+    a.h = GP(const u16, d, "h"); a.Wfc = GP(const u16, d, "Wfc"); a.bfc = GP(const float, d, "bfc");
+    a.tgt = GP(const int, d, "tgt"); a.ntok = GP(const int, d, "ntok");
+    a.tok_logp = GP(float, d, "tok_logp"); a.rank = GP(int, d, "rank"); a.name_logp = GP(float, d, "name_logp");
+    a.ntok_out = GP(int, d, "ntok_out"); a.err = GP(unsigned, d, "err");
+    a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0); a.V = get<int>(d, "V", 0); a.ML = get<int>(d, "ML", 0);
+    score_head_bf16(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   // score_logprob under the sampler's controls and constraints (tests/test_score_ctl_gpu.py)

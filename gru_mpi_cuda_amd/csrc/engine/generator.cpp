@@ -136,6 +136,7 @@ Generator::~Generator() {
   graphs_.clear();
   sgraphs_.clear();
   scgraphs_.clear();
+  sfgraphs_.clear();
   cgraphs_.clear();
   bgraphs_.clear();
   dgraphs_.clear();
@@ -897,6 +898,115 @@ void Generator::score(const unsigned char* rows, int N, float* tok_logp, int* ra
     HIP_CHECK(hipMemcpyAsync(name_logp + start, sname_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + start, sntok_out_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     if (c) HIP_CHECK(hipMemcpyAsync(n_kept + (size_t)start * ML, snkept_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ------------------------------------------------------------------------- fast bf16 scoring
+// A fast chunk of n names runs on Bp rows: 64 for up to 64 names, else a multiple of 128 (the LDS-staged step
+// kernels' tile; the register step kernel and the head take either).
+static int fast_pad(int n) { return n <= 64 ? 64 : rup(n, 128); }
+
+// Buffers of the fast schedule, sized for the largest padded chunk: a generator that never takes the fast
+// path never allocates them.
+void Generator::score_fast_alloc() {
+  if (sfready_) return;
+  const size_t H = d_.H, ML = d_.max_len, B = fast_pad(Bmax_);
+  const size_t orows = sfarena_.reserve(B * (ML + 1)), on = sfarena_.reserve(256);
+  const size_t oids = sfarena_.reserve(ML * B * 4), otgt = sfarena_.reserve(ML * B * 4), ont = sfarena_.reserve(B * 4);
+  const size_t oh0 = sfarena_.reserve(B * H * 4), ohf0 = sfarena_.reserve(B * H * 4), ohf1 = sfarena_.reserve(B * H * 4);
+  std::vector<size_t> ohb;
+  for (int l = 0; l < d_.L; ++l) ohb.push_back(sfarena_.reserve(ML * B * H * 2));
+  const size_t ogi = d_.L > 1 ? sfarena_.reserve(ML * B * 3 * H * 4) : 0;
+  const size_t otok = sfarena_.reserve(B * ML * 4), ornk = sfarena_.reserve(B * ML * 4);
+  const size_t onm = sfarena_.reserve(B * 4), onto = sfarena_.reserve(B * 4);
+  sfarena_.commit();
+  frows_ = sfarena_.get<unsigned char>(orows); fn_ = sfarena_.get<int>(on);
+  fids_ = sfarena_.get<int>(oids); ftgt_ = sfarena_.get<int>(otgt); fntok_ = sfarena_.get<int>(ont);
+  fh0_ = sfarena_.get<float>(oh0); fhf_[0] = sfarena_.get<float>(ohf0); fhf_[1] = sfarena_.get<float>(ohf1);
+  for (int l = 0; l < d_.L; ++l) fhb_.push_back(sfarena_.get<u16>(ohb[l]));
+  fgi_ = d_.L > 1 ? sfarena_.get<float>(ogi) : nullptr;
+  ftok_ = sfarena_.get<float>(otok); frank_ = sfarena_.get<int>(ornk);
+  fname_ = sfarena_.get<float>(onm); fntok_out_ = sfarena_.get<int>(onto);
+  sfready_ = true;
+}
+
+// The fast schedule for a padded batch of Bp rows (the name count is read from fn_ by score_prep, as in
+// record_score): L ML + (L - 1) + 3 launches, a single chain.  No saves: sr .. s16 stay null.
+void Generator::record_score_fast(int Bp, hipStream_t s) {
+  const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
+  ScorePrepArgs p;
+  p.rows = frows_; p.n_dev = fn_; p.ids = fids_; p.tgt = ftgt_; p.ntok = fntok_; p.err = err_;
+  p.Bp = Bp; p.ML = ML; p.V = V; p.sos = d_.sos; p.eos = d_.eos;
+  score_prep(p, s);
+  const long step = (long)Bp * H;   // one step's h rows
+  for (int l = 0; l < L; ++l) {
+    const std::string k = std::to_string(l);
+    if (l > 0) {   // the layer's input projection for every step at once: Gi = h_below W_ih^T + b_ih
+      GemmArgs g;
+      g.A = fhb_[l - 1]; g.lda = H; g.B = Wih_[l]; g.ldb = H; g.C = fgi_; g.ldc = 3 * H;
+      g.bias = P("bias_ih_l" + k); g.M = ML * Bp; g.N = 3 * H; g.K = H;
+      gemm_nt(g, s);
+    }
+    for (int st = 0; st < ML; ++st) {
+      FwdStepArgs a;
+      // h before step 0: the zero buffer, read as fp32 and (its first half) as bf16
+      a.hprev_bf = st == 0 ? reinterpret_cast<const u16*>(fh0_) : fhb_[l] + (st - 1) * step;
+      a.hprev_f = st == 0 ? fh0_ : fhf_[(st - 1) & 1];
+      a.Whh = Whh_[l]; a.bhh = P("bias_hh_l" + k);
+      if (l == 0) { a.P = Ptab_; a.ids = fids_ + (long)st * Bp; }
+      else a.Gi = fgi_ + (long)st * Bp * 3 * H;
+      a.h_f = fhf_[st & 1]; a.h_bf = fhb_[l] + st * step;
+      a.Bp = Bp; a.H = H; a.algo = step_algo_;
+      gru_fwd_step(a, s);
+    }
+  }
+  ScoreHeadArgs q;
+  q.h = fhb_[L - 1]; q.Wfc = Wfc_; q.bfc = P("fc.bias"); q.tgt = ftgt_; q.ntok = fntok_;
+  q.tok_logp = ftok_; q.rank = frank_; q.name_logp = fname_; q.ntok_out = fntok_out_; q.err = err_;
+  q.Bp = Bp; q.H = H; q.V = V; q.ML = ML;
+  score_head_bf16(q, s);
+  HIP_LAUNCH_CHECK();
+}
+
+void Generator::score_fast(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok,
+                           hipStream_t s) {
+  GK_TRACE("gk.score_fast");
+  if (d_.fp32) throw std::runtime_error("Generator::score_fast needs the bf16 mode (only it holds the bf16 operands)");
+  const int ML = d_.max_len;
+  if (!score_head_supported(d_.H, d_.V, ML))
+    throw std::runtime_error("Generator::score_fast needs vocab % 64 == 0, vocab <= 512 and max_len <= 64");
+  if (d_.sos < 0 || d_.sos >= d_.V) throw std::runtime_error("Generator::score_fast needs 0 <= sos < vocab");
+  if (N <= 0) return;
+  for (int start = 0; start < N; start += Bmax_) {   // what gru_fwd_step refuses, before anything is launched
+    FwdStepArgs a;
+    a.Bp = fast_pad(std::min(Bmax_, N - start)); a.H = d_.H; a.algo = step_algo_;
+    (void)gru_fwd_step_plan(a);
+  }
+  score_last_persist_ = false;
+  score_fast_alloc();   // first call: allocates (and synchronises) before anything is captured
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in score()
+  err_clean_ = false;
+  for (int start = 0; start < N; start += Bmax_) {
+    const int n = std::min(Bmax_, N - start);
+    const int Bp = fast_pad(n);
+    score_set_count(fn_, n, s);
+    HIP_CHECK(hipMemcpyAsync(frows_, rows + (size_t)start * (ML + 1), (size_t)n * (ML + 1), hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      auto& g = sfgraphs_[Bp];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_score_fast(Bp, cap_);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_score_fast(Bp, s);
+    }
+    HIP_CHECK(hipMemcpyAsync(tok_logp + (size_t)start * ML, ftok_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(rank + (size_t)start * ML, frank_, (size_t)n * ML * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(name_logp + start, fname_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + start, fntok_out_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

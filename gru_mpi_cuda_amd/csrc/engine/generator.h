@@ -116,9 +116,18 @@ class Generator {
   // on the graphs it had.  Every precision mode scores with controls (scoring is exact fp32 always).
   void score(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok, hipStream_t s,
              const Ctl* c = nullptr, int* n_kept = nullptr);
-  // 0 until the first score(); grows when the first controlled score() commits the control buffers
-  size_t score_workspace_bytes() const { return sarena_.bytes() + scarena_.bytes(); }
-  int score_graphs() const { return (int)(sgraphs_.size() + scgraphs_.size()); }   // recordings so far
+  // score() on the bf16 operands (docs/DESIGN.md §4a "Fast bf16 scoring"; opt-in, the same arrays and the same
+  // n_tok / mask / rank rules): layer 0 as max_len gru_fwd_step launches on the P table, each layer above as ONE
+  // bf16 input-projection GEMM over all max_len * Bp rows and its steps, every step's bf16 h kept per layer,
+  // then score_head_bf16 -- no logits in memory.  Only the bf16 mode holds the operands: the other modes throw,
+  // as does a shape the kernels do not cover, before anything is launched.  Chunks of max_batch names, padded
+  // to 64 (one chunk of up to 64 names) or 128 rows; one recording per padded batch; buffers in an arena of its
+  // own, committed by the first fast call.  Never the persistent score launch.
+  void score_fast(const unsigned char* rows, int N, float* tok_logp, int* rank, float* name_logp, int* n_tok,
+                  hipStream_t s);
+  // 0 until the first score(); grows when the first controlled / the first fast call commits its buffers
+  size_t score_workspace_bytes() const { return sarena_.bytes() + scarena_.bytes() + sfarena_.bytes(); }
+  int score_graphs() const { return (int)(sgraphs_.size() + scgraphs_.size() + sfgraphs_.size()); }   // recordings so far
   // A plain score() call (no controls) whose whole N is at most GK_GEN_PERSIST_SCORE_MAX /
   // set_persist_score_max(n) names, at most 64 -- 0 by default, the path is opt-in -- runs as ONE persistent
   // launch (gen_persist_score.hip, docs/DESIGN.md §4a) on the caller's arrays, where a variant exists for the
@@ -258,6 +267,8 @@ class Generator {
   void record_score(int Bp, hipStream_t s, bool ctl = false, int allow_rows = 0, int soft_rows = 0);
   void soft_alloc();
   void score_ctl_alloc();
+  void score_fast_alloc();
+  void record_score_fast(int Bp, hipStream_t s);
   void beam_alloc();
   // the beam loop's selection: beam_select_f32; sbs_select_f32 (G by step parity, step 0 reads the reset scores
   // as G); smc_select_f32 (logw by step parity, step 0 reads the reset scores as logw)
@@ -335,6 +346,18 @@ class Generator {
   unsigned* sctab_ = nullptr;                   // [kAllowRows][V / 32] the call's constraint table
   int* scidx_ = nullptr;                        // [Bmax][ML] the current batch's lines
   int* snkept_ = nullptr;                       // staged output [Bmax][ML]
+  // fast bf16 scoring (committed by the first score_fast() call), sized for Bmax_ padded to 128 rows
+  Arena sfarena_;
+  bool sfready_ = false;
+  std::map<int, std::unique_ptr<Graph>> sfgraphs_;   // keyed by the padded batch Bp
+  unsigned char* frows_ = nullptr;              // staged input rows
+  int *fn_ = nullptr, *fids_ = nullptr, *ftgt_ = nullptr, *fntok_ = nullptr;   // N word, [ML][Bp] x2, [Bp]
+  float* fh0_ = nullptr;                        // [Bp][H] zeros (arena-zeroed, never written): h before step 0, fp32 and bf16
+  float* fhf_[2] = {nullptr, nullptr};          // [Bp][H] x2: the fp32 h, by step parity
+  std::vector<u16*> fhb_;                       // per layer [ML][Bp][H] bf16: every step's h
+  float* fgi_ = nullptr;                        // [ML * Bp][3H] a layer's input projection (L > 1)
+  float *ftok_ = nullptr, *fname_ = nullptr;    // staged outputs [Bp][ML], [Bp]
+  int *frank_ = nullptr, *fntok_out_ = nullptr;
   // sampling controls (third arena, committed by the first generate_ctl() call)
   Arena carena_;
   bool cready_ = false;

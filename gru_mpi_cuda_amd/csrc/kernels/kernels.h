@@ -726,6 +726,26 @@ struct ScoreLogprobArgs {          // per token: log softmax(logits)[target] and
   int Bp = 0, V = 0, ML = 0;       // V % 64 == 0, V <= 512, ML <= 64
 };
 void score_logprob_f32(const ScoreLogprobArgs& a, hipStream_t s);
+// The bf16 fast scorer's head (score_fast.hip, docs/DESIGN.md §4a "Fast bf16 scoring"): logits = h W_fc^T + b_fc
+// on bf16 MFMA with fp32 accumulation, fused with score_logprob_f32's log-softmax, target pick and rank, so the
+// [ML Bp][V] logits never reach memory; then a tail launch adds each name's tok_logp in step order.  Grid
+// (Bp / 64, ML): a workgroup whose 64 names are all masked at its step only writes the masked values.  A target
+// outside [0, V) at a scored position ORs 16 into err[0] and is clamped.  No atomics on the results.
+struct ScoreHeadArgs {
+  const u16* h = nullptr;          // [ML][Bp][H] bf16: the top layer's h of every step
+  const u16* Wfc = nullptr;        // [V][H] bf16
+  const float* bfc = nullptr;      // [V]
+  const int* tgt = nullptr;        // [ML][Bp]
+  const int* ntok = nullptr;       // [Bp]; pad rows 0
+  float* tok_logp = nullptr;       // [Bp][ML]; masked positions 0
+  int* rank = nullptr;             // [Bp][ML]; masked positions -1
+  float* name_logp = nullptr;      // [Bp]
+  int* ntok_out = nullptr;         // [Bp]
+  unsigned* err = nullptr;         // nullable
+  int Bp = 0, H = 0, V = 0, ML = 0;   // Bp, H, V % 64 == 0, V <= 512, ML <= 64
+};
+bool score_head_supported(int H, int V, int ML);
+void score_head_bf16(const ScoreHeadArgs& a, hipStream_t s);   // throws before launching what is unsupported
 // Scoring of N <= 64 rows as ONE persistent launch (gen_persist_score.hip, docs/DESIGN.md §4a): score_prep's
 // rule, the exact-fp32 steps as a layer wavefront on gen_persist_kernel's grid and weight layout, and
 // score_logprob_f32's arithmetic as the tail, workgroup n writing name n's outputs straight to the caller's

@@ -262,11 +262,19 @@ class HipGenerator:
         self.g.refresh_weights(self._s())
 
     def score(self, rows: np.ndarray, *, temperature=None, top_k=None, top_p=None, prefix=None,
-              constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None) -> "ScoreResult":
+              constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None,
+              fast: bool = False) -> "ScoreResult":
         """Teacher-forced log-likelihood of output rows ([N, MAX_LEN+1] or flat uint8, the format
-        ``generate`` writes; semantics: cpu_ref.score_inputs).  Always exact fp32 arithmetic, whatever
-        ``precision`` this generator samples with.  A byte >= vocab at a scored position raises
-        ValueError before anything is launched.
+        ``generate`` writes; semantics: cpu_ref.score_inputs).  Exact fp32 arithmetic, whatever
+        ``precision`` this generator samples with, unless ``fast`` is set.  A byte >= vocab at a scored
+        position raises ValueError before anything is launched.
+        ``fast=True`` (opt-in; docs/DESIGN.md §4a "Fast bf16 scoring"; the rule:
+        cpu_ref.score(round_operands=True)): the same outputs from the bf16 MFMA step kernels and a fused
+        logits + log-softmax + rank head -- every product on bf16 operands with fp32 accumulation, no logits
+        in memory.  For ranking or filtering many names and for held-out evaluation, where throughput counts
+        and bit-faithfulness to fp32 does not.  Only precision "bf16" holds the bf16 operands: the other modes,
+        any control, constraint or soft term beside ``fast``, vocab > 512 and max_len > 64 raise ValueError
+        before anything is launched.  A fast call never takes the persistent score launch.
         ``temperature`` / ``top_k`` / ``top_p`` / ``prefix`` / ``constraints`` (``generate``'s keywords, scalars
         or one value per row; the rule: cpu_ref.score, docs/DESIGN.md §4f): any that is not None -- a neutral
         value too -- scores the rows under the distribution ``generate`` samples from with these settings:
@@ -278,7 +286,18 @@ class HipGenerator:
         ML = self.cfg.max_len
         ctl = cons = soft = None
         soft_given = any(v is not None for v in (logit_bias, presence_penalty, frequency_penalty))
-        if constraints is not None or soft_given or any(v is not None for v in (temperature, top_k, top_p, prefix)):
+        controlled = constraints is not None or soft_given or any(v is not None for v in (temperature, top_k, top_p, prefix))
+        if fast:
+            if self.precision != "bf16":
+                raise ValueError('score(fast=True) needs precision "bf16" (only that mode holds the bf16 operands), '
+                                 f"got {self.precision!r}")
+            if controlled:
+                raise ValueError("score(fast=True) takes no sampling control, constraint or soft term (they score in "
+                                 "exact fp32)")
+            if not self.C.score_head_supported(pad_config(self.cfg).hidden, self.cfg.vocab, ML):
+                raise ValueError(f"score(fast=True) needs vocab % 64 == 0, vocab <= 512 and max_len <= 64 "
+                                 f"(got vocab {self.cfg.vocab}, max_len {ML})")
+        if controlled:
             count = np.ascontiguousarray(rows, dtype=np.uint8).size // (ML + 1)
             soft = cpu_ref.as_soft(self.cfg, count, None, logit_bias, presence_penalty, frequency_penalty)
             cons = cpu_ref.as_constraints(self.cfg, count, constraints)
@@ -300,7 +319,9 @@ class HipGenerator:
         name = torch.empty(N, dtype=torch.float32, device=self.dev)
         nt = torch.empty(N, dtype=torch.int32, device=self.dev)
         nk = None
-        if ctl is None:
+        if fast:
+            self.g.score_fast(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s())
+        elif ctl is None:
             self.g.score(r.data_ptr(), N, tok.data_ptr(), rank.data_ptr(), name.data_ptr(), nt.data_ptr(), self._s())
         else:
             dev = [torch.from_numpy(a).to(self.dev) for a in (ctl.inv_temp, ctl.top_k, ctl.top_p, ctl.plen, ctl.prefix)]

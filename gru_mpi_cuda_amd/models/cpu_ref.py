@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ..config import GRUConfig
+from .seq_ref import bf16_round
 
 Params = Dict[str, torch.Tensor]
 
@@ -88,8 +89,13 @@ def _dropout_factor(cfg: GRUConfig, layer: int, step: int, b0: int, B: int, T: i
 
 
 def forward(params: Params, cfg: GRUConfig, x: torch.Tensor, h0: Optional[List[torch.Tensor]] = None,
-            keep_cache: bool = False, dropout_step: Optional[int] = None, b0: int = 0):
+            keep_cache: bool = False, dropout_step: Optional[int] = None, b0: int = 0,
+            round_operands: bool = False):
     """x: [B, T] int ids.  Returns logits [B, T, V] (and per-layer caches if asked).
+
+    round_operands: the bf16 fast paths' operand precision in the dtype of ``params`` -- every weight matrix
+    (the embedding included) and every h fed to a product is rounded to bf16 (seq_ref.bf16_round, the rounding
+    of ``seq_ref.fwd_ref(exact=False)``); the biases, the carried state, the gates and the accumulation are not.
 
     dropout_step: None (every inference caller, and training without dropout) applies no mask; an int applies
     cfg.dropout's masks of that optimiser step to every layer's output as its consumer sees it, the batch's
@@ -98,16 +104,17 @@ def forward(params: Params, cfg: GRUConfig, x: torch.Tensor, h0: Optional[List[t
     drop = dropout_step is not None and cfg.dropout > 0
     H = cfg.hidden
     dt = params["fc.weight"].dtype
-    inp = params["embedding"][x.long()]                       # [B, T, E]
+    rnd = bf16_round if round_operands else (lambda v: v)
+    inp = rnd(params["embedding"])[x.long()]                  # [B, T, E]
     caches = []
     for l in range(cfg.layers):
-        W_ih, W_hh = params[f"weight_ih_l{l}"], params[f"weight_hh_l{l}"]
+        W_ih, W_hh = rnd(params[f"weight_ih_l{l}"]), rnd(params[f"weight_hh_l{l}"])
         b_ih, b_hh = params[f"bias_ih_l{l}"], params[f"bias_hh_l{l}"]
-        gi_all = inp @ W_ih.T + b_ih                          # hoisted input projection [B,T,3H]
+        gi_all = rnd(inp) @ W_ih.T + b_ih                     # hoisted input projection [B,T,3H]
         h = torch.zeros(B, H, dtype=dt) if h0 is None else h0[l]
         hs, rs, zs, ns, ghns, hprev = [], [], [], [], [], []
         for t in range(T):
-            gh = h @ W_hh.T + b_hh
+            gh = rnd(h) @ W_hh.T + b_hh
             hprev.append(h)
             h, (r, z, n, ghn) = _gates(gi_all[:, t], gh, h)
             hs.append(h); rs.append(r); zs.append(z); ns.append(n); ghns.append(ghn)
@@ -123,7 +130,7 @@ def forward(params: Params, cfg: GRUConfig, x: torch.Tensor, h0: Optional[List[t
             if keep_cache:
                 caches[-1]["drop"] = f
                 caches[-1]["dout"] = inp
-    logits = inp @ params["fc.weight"].T + params["fc.bias"]
+    logits = rnd(inp) @ rnd(params["fc.weight"]).T + params["fc.bias"]
     return (logits, caches) if keep_cache else logits
 
 
@@ -288,8 +295,12 @@ def score_inputs(cfg: GRUConfig, rows: np.ndarray):
 
 
 def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, top_k=None, top_p=None, prefix=None,
-          constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None, soft=None):
+          constraints=None, logit_bias=None, presence_penalty=None, frequency_penalty=None, soft=None,
+          round_operands: bool = False):
     """log P of output rows under the model, teacher-forced from a zero hidden state (score_inputs).
+
+    ``round_operands``: the twin of ``HipGenerator.score(fast=True)`` (docs/DESIGN.md §4a "Fast bf16 scoring"):
+    ``forward``'s bf16 operand rounding, the softmax and everything else as below.
 
     Returns numpy (tok_logp [N, ML], name_logp [N], n_tok [N] int32, rank [N, ML] int32) in the dtype
     of ``params`` (fp64 params: the oracle).  tok_logp[l] = log softmax(logits_l)[c[l]]; rank[l] = the
@@ -329,7 +340,7 @@ def score(params: Params, cfg: GRUConfig, rows: np.ndarray, temperature=None, to
     if N == 0:
         empty = (np.zeros((0, ML), npdt), np.zeros(0, npdt), n_tok, np.zeros((0, ML), np.int32))
         return empty if ctl is None else empty + (np.zeros((0, ML), np.int32),)
-    logits = forward(params, cfg, torch.from_numpy(x))
+    logits = forward(params, cfg, torch.from_numpy(x), round_operands=round_operands)
     if dt != torch.float64:
         logits = logits.to(torch.float32)
     t = torch.from_numpy(tgt)
