@@ -463,17 +463,21 @@ def cmd_beam(args) -> int:
         prefixes = [b.decode("latin-1") for b in _read_names(args.prefix_file)]
     else:
         prefixes = [args.prefix or ""]
+    if args.fast and _constraints_from(args) is not None:
+        raise SystemExit("--fast takes no constraint flag (constrained searches run in exact fp32)")
     if args.cpu or not torch.cuda.is_available():
         res = cpu_ref.beam_search({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width,
-                                  constraints=_constraints_from(args))
+                                  constraints=_constraints_from(args), round_operands=args.fast)
     else:
         if args.persist_beam is not None and not 0 <= args.persist_beam <= 64:
             raise SystemExit("--persist-beam needs a row count in [0, 64]")
         if args.persist_constraints is not None and args.persist_constraints < 0:
             raise SystemExit("--persist-constraints needs a count >= 0")
+        # --fast: the bf16 mode holds the operands of the fast loop (docs/DESIGN.md §4d)
         gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
+                             precision="bf16" if args.fast else "fp32",
                              persist_beam=args.persist_beam or 0, persist_constraints=args.persist_constraints or 0)
-        res = gen.beam_search(prefixes, args.width, constraints=_constraints_from(args))
+        res = gen.beam_search(prefixes, args.width, constraints=_constraints_from(args), fast=args.fast)
     lines = []
     for pre, names, lps in zip(prefixes, res.names(), res.logp):
         for k, nm in enumerate(names):
@@ -734,6 +738,10 @@ def main(argv=None) -> int:
                     metavar="N", help="HIP path: a constrained batch takes the persistent launch of --persist-beam when "
                                       "this covers its rows too (bare flag: 64; opt-in; docs/DESIGN.md §4d); no "
                                       "effect with --cpu")
+    bm.add_argument("--fast", action="store_true",
+                    help="bf16 fast beam search: bf16 MFMA products with fp32 accumulation and a fused logits / top-W "
+                         "head (opt-in, not bit-faithful to fp32, no constraints; with --cpu: the rule with "
+                         "bf16-rounded operands; docs/DESIGN.md §4d)")
     bm.add_argument("--out", default=None, help="prefix, rank, name and log-prob per line, tab-separated")
     bm.add_argument("--cpu", action="store_true", help="cpu_ref.beam_search in fp32 instead of the HIP generator")
     bm.add_argument("--preset", default="ref", help="dims for --fmt ref (headerless blob)")

@@ -271,6 +271,13 @@ PYBIND11_MODULE(_C, m) {
          py::arg("n_tok"), py::arg("n_beams"), py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0,
          py::arg("allow_idx") = (uintptr_t)0, py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0,
          py::arg("allow_start") = (uintptr_t)0)
+      .def("beam_fast", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, uintptr_t rows, uintptr_t logp,
+                           uintptr_t n_tok, uintptr_t n_beams, uintptr_t s) {
+        g.beam_fast(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, Pp<unsigned char>(rows), Pp<float>(logp),
+                    Pp<int>(n_tok), Pp<int>(n_beams), S(s));
+      }, py::arg("plen"), py::arg("prefix"), py::arg("N"), py::arg("W"), py::arg("rows"), py::arg("logp"),
+         py::arg("n_tok"), py::arg("n_beams"), py::arg("stream"))
+      .def("beam_fast_graphs", &Generator::beam_fast_graphs)
       .def("distinct", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, unsigned long long seed,
                           unsigned long long start, uintptr_t inv_t, uintptr_t rows, uintptr_t logq, uintptr_t gumbel,
                           uintptr_t n_tok, uintptr_t n_found, uintptr_t s, uintptr_t allow_tab, uintptr_t allow_idx,
@@ -1225,6 +1232,47 @@ PYBIND11_MODULE(_C, m) {
     a.len_src = GP(const int, d, "len_src"); a.len_dst = GP(int, d, "len_dst");
     a.ids = GP(int, d, "ids"); a.n_beams = GP(int, d, "n_beams");
     beam_reorder(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the fast bf16 beam search's kernels on caller-owned buffers (tests/test_beam_fast_kernel_gpu.py)
+  m.def("beam_head_supported", &beam_head_supported);
+  m.def("beam_head", [](py::dict d, uintptr_t s) {
+    BeamHeadArgs a;
+    a.h = GP(const u16, d, "h"); a.Wfc = GP(const u16, d, "Wfc"); a.bfc = GP(const float, d, "bfc");
+    a.score_in = GP(const float, d, "score_in"); a.state_in = GP(const int, d, "state_in");
+    a.plen = GP(const int, d, "plen"); a.prefix = GP(const unsigned char, d, "prefix");
+    a.cand_score = GP(float, d, "cand_score"); a.cand_chr = GP(int, d, "cand_chr");
+    a.lp = GP(float, d, "lp"); a.err = GP(unsigned, d, "err");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
+    a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0); a.max_len = get<int>(d, "max_len", 0);
+    beam_head_bf16(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("beam_merge", [](py::dict d, uintptr_t s) {
+    BeamMergeArgs a;
+    a.cand_score = GP(const float, d, "cand_score"); a.cand_chr = GP(const int, d, "cand_chr");
+    a.score_in = GP(const float, d, "score_in"); a.state_in = GP(const int, d, "state_in");
+    a.score_out = GP(float, d, "score_out"); a.parent = GP(int, d, "parent"); a.chr = GP(int, d, "chr");
+    a.state_out = GP(int, d, "state_out"); a.next_id = GP(int, d, "next_id"); a.sel = GP(int, d, "sel");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0);
+    a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    beam_merge(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("beam_reorder_bf16", [](py::dict d, uintptr_t s) {
+    BeamReorderBf16Args a;
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.L = get<int>(d, "L", 0); a.H = get<int>(d, "H", 0);
+    a.max_len = get<int>(d, "max_len", 0);
+    const auto hs = get<std::vector<uintptr_t>>(d, "h_src", {}), hd = get<std::vector<uintptr_t>>(d, "h_dst", {});
+    const auto hb = get<std::vector<uintptr_t>>(d, "hb_dst", {});
+    if (a.L < 1 || a.L > 4 || (int)hs.size() != a.L || (int)hd.size() != a.L || (int)hb.size() != a.L)
+      throw std::runtime_error("beam_reorder_bf16: 1 <= L <= 4, L h_src, L h_dst and L hb_dst pointers");
+    for (int l = 0; l < a.L; ++l) { a.h_src[l] = Pp<const float>(hs[l]); a.h_dst[l] = Pp<float>(hd[l]); a.hb_dst[l] = Pp<u16>(hb[l]); }
+    a.parent = GP(const int, d, "parent"); a.chr = GP(const int, d, "chr"); a.next_id = GP(const int, d, "next_id");
+    a.rows_src = GP(const unsigned char, d, "rows_src"); a.rows_dst = GP(unsigned char, d, "rows_dst");
+    a.len_src = GP(const int, d, "len_src"); a.len_dst = GP(int, d, "len_dst");
+    a.ids = GP(int, d, "ids"); a.n_beams = GP(int, d, "n_beams");
+    beam_reorder_bf16(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("beam_reset", [](py::dict d, uintptr_t s) {

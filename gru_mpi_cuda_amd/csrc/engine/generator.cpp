@@ -139,6 +139,7 @@ Generator::~Generator() {
   sfgraphs_.clear();
   cgraphs_.clear();
   bgraphs_.clear();
+  bfgraphs_.clear();
   dgraphs_.clear();
   adgraphs_.clear();
   qgraphs_.clear();
@@ -1237,6 +1238,150 @@ void Generator::beam(const int* plen, const unsigned char* prefix, int N, int W,
     HIP_CHECK(hipMemcpyAsync(n_tok + r0, blen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_beams + start, bnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     start += n;
+  }
+}
+
+// ------------------------------------------------------------------------- fast bf16 beam search
+// Buffers of the fast beam loop, sized for the largest padded batch: a generator that never takes the fast
+// path never allocates them.
+void Generator::beam_fast_alloc() {
+  if (bfready_) return;
+  const size_t H = d_.H, ML = d_.max_len, B = fast_pad(Bmax_);
+  const size_t oz = bfarena_.reserve(B * H * 4);
+  std::vector<size_t> ofA, ofB, obA, obB;
+  for (int l = 0; l < d_.L; ++l) {
+    ofA.push_back(bfarena_.reserve(B * H * 4)); ofB.push_back(bfarena_.reserve(B * H * 4));
+    obA.push_back(bfarena_.reserve(B * H * 2)); obB.push_back(bfarena_.reserve(B * H * 2));
+  }
+  const size_t oids = bfarena_.reserve(B * 4);
+  size_t osc[2], ost[2], oln[2], orw[2];
+  for (int i = 0; i < 2; ++i) {
+    osc[i] = bfarena_.reserve(B * 4); ost[i] = bfarena_.reserve(B * 4); oln[i] = bfarena_.reserve(B * 4);
+    orw[i] = bfarena_.reserve(B * (ML + 1));
+  }
+  const size_t opa = bfarena_.reserve(B * 4), och = bfarena_.reserve(B * 4), onx = bfarena_.reserve(B * 4);
+  const size_t onb = bfarena_.reserve(B * 4), opl = bfarena_.reserve(B * 4), opre = bfarena_.reserve(B * ML);
+  const size_t ocs = bfarena_.reserve(B * 32 * 4), occ = bfarena_.reserve(B * 32 * 4);
+  bfarena_.commit();
+  fbz_ = bfarena_.get<float>(oz);
+  for (int l = 0; l < d_.L; ++l) {
+    fbhfA_.push_back(bfarena_.get<float>(ofA[l])); fbhfB_.push_back(bfarena_.get<float>(ofB[l]));
+    fbhbA_.push_back(bfarena_.get<u16>(obA[l])); fbhbB_.push_back(bfarena_.get<u16>(obB[l]));
+  }
+  fbids_ = bfarena_.get<int>(oids);
+  for (int i = 0; i < 2; ++i) {
+    fbscore_[i] = bfarena_.get<float>(osc[i]); fbstate_[i] = bfarena_.get<int>(ost[i]); fblen_[i] = bfarena_.get<int>(oln[i]);
+    fbrows_[i] = bfarena_.get<unsigned char>(orw[i]);
+  }
+  fbparent_ = bfarena_.get<int>(opa); fbchr_ = bfarena_.get<int>(och); fbnext_ = bfarena_.get<int>(onx);
+  fbnb_ = bfarena_.get<int>(onb); fbplen_ = bfarena_.get<int>(opl); fbprefix_ = bfarena_.get<unsigned char>(opre);
+  fbcs_ = bfarena_.get<float>(ocs); fbcc_ = bfarena_.get<int>(occ);
+  bfready_ = true;
+}
+
+// The two step forms of the fast loop for a padded batch (layer 0 on the P table, a layer above fused), so
+// that beam_fast() can ask gru_fwd_step_plan about both before anything is launched.
+static FwdStepArgs fast_step_shape(int Bp, int H, int algo, bool fused) {
+  FwdStepArgs a;
+  a.Bp = Bp; a.H = H; a.algo = algo;
+  static const u16 form = 0;   // the plan reads only whether x_bf is set
+  if (fused) { a.x_bf = &form; a.Kin = H; }
+  return a;
+}
+
+// The fast beam loop for n names of W beams: 1 + ML (L steps + head + merge + reorder) launches, a single
+// chain.  Fixed slots as record_beam: a step reads the A slots (fp32 and bf16; before step 0 the zero buffer)
+// and writes the B slots, the reorder gathers B -> A.  Scores, states, lengths and output rows alternate
+// between two sets by step parity; the result is in set ML & 1.  No saves: sr .. s16 stay null.
+void Generator::record_beam_fast(int n, int W, hipStream_t s) {
+  const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
+  const int Bp = fast_pad(n * W);
+  BeamResetArgs r;
+  for (int l = 0; l < L; ++l) r.h[l] = fbhfA_[l];
+  r.ids = fbids_; r.score = fbscore_[0]; r.state = fbstate_[0]; r.len = fblen_[0]; r.rows = fbrows_[0];
+  r.N = n; r.W = W; r.L = L; r.Bp = Bp; r.H = H; r.max_len = ML; r.sos = d_.sos;
+  beam_reset(r, s);
+  for (int st = 0; st < ML; ++st) {
+    const int cur = st & 1, nxt = cur ^ 1;
+    for (int l = 0; l < L; ++l) {
+      const std::string k = std::to_string(l);
+      FwdStepArgs a;
+      a.hprev_bf = st == 0 ? reinterpret_cast<const u16*>(fbz_) : fbhbA_[l];
+      a.hprev_f = st == 0 ? fbz_ : fbhfA_[l];
+      a.Whh = Whh_[l]; a.bhh = P("bias_hh_l" + k);
+      if (l == 0) { a.P = Ptab_; a.ids = fbids_; }
+      else { a.x_bf = fbhbB_[l - 1]; a.Wih = Wih_[l]; a.bih = P("bias_ih_l" + k); a.Kin = H; }
+      a.h_f = fbhfB_[l]; a.h_bf = fbhbB_[l];
+      a.Bp = Bp; a.H = H; a.algo = step_algo_;
+      gru_fwd_step(a, s);
+    }
+    BeamHeadArgs q;
+    q.h = fbhbB_[L - 1]; q.Wfc = Wfc_; q.bfc = P("fc.bias");
+    q.score_in = fbscore_[cur]; q.state_in = fbstate_[cur]; q.plen = fbplen_; q.prefix = fbprefix_;
+    q.cand_score = fbcs_; q.cand_chr = fbcc_; q.err = err_;
+    q.N = n; q.W = W; q.Bp = Bp; q.H = H; q.V = V; q.step = st; q.max_len = ML;
+    beam_head_bf16(q, s);
+    BeamMergeArgs m;
+    m.cand_score = fbcs_; m.cand_chr = fbcc_; m.score_in = fbscore_[cur]; m.state_in = fbstate_[cur];
+    m.score_out = fbscore_[nxt]; m.parent = fbparent_; m.chr = fbchr_; m.state_out = fbstate_[nxt]; m.next_id = fbnext_;
+    m.N = n; m.W = W; m.V = V; m.sos = d_.sos; m.eos = d_.eos;
+    beam_merge(m, s);
+    BeamReorderBf16Args o;
+    for (int l = 0; l < L; ++l) { o.h_src[l] = fbhfB_[l]; o.h_dst[l] = fbhfA_[l]; o.hb_dst[l] = fbhbA_[l]; }
+    o.parent = fbparent_; o.chr = fbchr_; o.next_id = fbnext_;
+    o.rows_src = fbrows_[cur]; o.rows_dst = fbrows_[nxt]; o.len_src = fblen_[cur]; o.len_dst = fblen_[nxt];
+    o.ids = fbids_; o.n_beams = fbnb_;
+    o.N = n; o.W = W; o.L = L; o.H = H; o.max_len = ML;
+    beam_reorder_bf16(o, s);
+    HIP_LAUNCH_CHECK();
+  }
+}
+
+void Generator::beam_fast(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
+                          int* n_tok, int* n_beams, hipStream_t s) {
+  GK_TRACE("gk.beam_fast");
+  const int ML = d_.max_len;
+  if (d_.fp32) throw std::runtime_error("Generator::beam_fast needs the bf16 mode (only it holds the bf16 operands)");
+  if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::beam_fast needs 1 <= width <= min(32, vocab)");
+  if (!beam_head_supported(d_.H, d_.V, ML))
+    throw std::runtime_error("Generator::beam_fast needs vocab % 64 == 0, vocab <= 512 and max_len <= 64");
+  if (d_.max_batch < W) throw std::runtime_error("Generator::beam_fast needs max_batch >= width");
+  if (d_.L > 4) throw std::runtime_error("Generator::beam_fast needs at most 4 layers");
+  if (d_.sos < 0 || d_.sos >= d_.V) throw std::runtime_error("Generator::beam_fast needs 0 <= sos < vocab");
+  if (!plen || !prefix || !rows || !logp || !n_tok || !n_beams)
+    throw std::runtime_error("Generator::beam_fast: plen, prefix, rows, logp, n_tok and n_beams are required");
+  if (N <= 0) return;
+  const int nb = d_.max_batch / W, fin = ML & 1;
+  for (int start = 0; start < N; start += nb) {   // what gru_fwd_step refuses, before anything is launched
+    const int Bp = fast_pad(std::min(nb, N - start) * W);
+    (void)gru_fwd_step_plan(fast_step_shape(Bp, d_.H, step_algo_, false));
+    if (d_.L > 1) (void)gru_fwd_step_plan(fast_step_shape(Bp, d_.H, step_algo_, true));
+  }
+  beam_fast_alloc();   // first call: allocates (and synchronises) before anything is captured
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in beam()
+  err_clean_ = false;
+  beam_last_persist_ = false;
+  for (int start = 0; start < N; start += nb) {
+    const int n = std::min(nb, N - start);
+    HIP_CHECK(hipMemcpyAsync(fbplen_, plen + start, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(fbprefix_, prefix + (size_t)start * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    if (use_graph_) {
+      auto& g = bfgraphs_[std::make_pair(n, W)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_beam_fast(n, W, cap_);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_beam_fast(n, W, s);
+    }
+    const size_t r0 = (size_t)start * W, nr = (size_t)n * W;
+    HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), fbrows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(logp + r0, fbscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + r0, fblen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_beams + start, fbnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

@@ -214,7 +214,19 @@ class Generator {
   void set_persist_beam_max(int rows) { persist_beam_max_ = rows; }
   bool beam_last_persist() const { return beam_last_persist_; }   // the path of the last beam() batch
   long persist_beam_launches() const { return persist_beam_launches_; }
-  size_t beam_workspace_bytes() const { return barena_.bytes(); }   // 0 until the first beam()
+  // beam() on the bf16 operands (docs/DESIGN.md §4d "Fast bf16 beam search"; opt-in; the same arrays, states
+  // and total order, the rule: cpu_ref.beam_search(round_operands=True)).  Per char step L gru_fwd_step
+  // launches (layer 0 on the P table, each layer above in the fused x_bf / Wih form on the layer below's bf16
+  // h, no saves), then beam_head_bf16, beam_merge and beam_reorder_bf16: L + 3 launches against 3 L + 2, and
+  // no logits in memory.  Fixed slots A / B, one recording per (names, W), prefixes read from arena buffers,
+  // batches of floor(max_batch / W) names on 64 rows (up to 64) or a multiple of 128.  Only the bf16 mode
+  // holds the operands: the other modes throw, as does a shape the kernels do not cover, before anything is
+  // launched.  No constraints; never the persistent beam launch.  Its arena is committed by the first call.
+  void beam_fast(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
+                 int* n_tok, int* n_beams, hipStream_t s);
+  int beam_fast_graphs() const { return (int)bfgraphs_.size(); }
+  // 0 until the first beam(); grows when the first beam_fast() commits its buffers
+  size_t beam_workspace_bytes() const { return barena_.bytes() + bfarena_.bytes(); }
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
   int automaton_graphs() const { return (int)(agraphs_.size() + abgraphs_.size()); }   // ... with an automaton
@@ -270,6 +282,8 @@ class Generator {
   void score_fast_alloc();
   void record_score_fast(int Bp, hipStream_t s);
   void beam_alloc();
+  void beam_fast_alloc();
+  void record_beam_fast(int n, int W, hipStream_t s);
   // the beam loop's selection: beam_select_f32; sbs_select_f32 (G by step parity, step 0 reads the reset scores
   // as G); smc_select_f32 (logw by step parity, step 0 reads the reset scores as logw)
   enum class BeamSelect { kBeam, kDistinct, kConditional };
@@ -389,6 +403,23 @@ class Generator {
   long persist_beam_launches_ = 0;
   float* pbws_ = nullptr;                       // persistent beam launch: exchange buffers (null: no variant for the shape)
   unsigned* pbsync_ = nullptr;                  // ... flags + done counter (self-cleaning, arena-zeroed)
+  // fast bf16 beam search (committed by the first beam_fast() call), sized for Bmax_ padded to 128 rows
+  Arena bfarena_;
+  bool bfready_ = false;
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> bfgraphs_;   // keyed by (names, W)
+  float* fbz_ = nullptr;                        // [Bp][H] zeros (arena-zeroed, never written): h before step 0, fp32 and bf16
+  std::vector<float*> fbhfA_, fbhfB_;           // per layer [Bp][H] fp32: a step's input / output states
+  std::vector<u16*> fbhbA_, fbhbB_;             // ... and their bf16 copies, the MFMA operands
+  int* fbids_ = nullptr;                        // [Bp]
+  float* fbscore_[2] = {nullptr, nullptr};      // [Bp] x2, by step parity, like the three below
+  int* fbstate_[2] = {nullptr, nullptr};
+  int* fblen_[2] = {nullptr, nullptr};
+  unsigned char* fbrows_[2] = {nullptr, nullptr};   // [Bp][ML + 1] x2
+  int *fbparent_ = nullptr, *fbchr_ = nullptr, *fbnext_ = nullptr, *fbnb_ = nullptr;   // [Bp] each
+  int* fbplen_ = nullptr;                       // [Bp] the current batch's prefixes
+  unsigned char* fbprefix_ = nullptr;           // [Bp][ML]
+  float* fbcs_ = nullptr;                       // [Bp][32] the head's candidate scores ([rows][W] of a recording)
+  int* fbcc_ = nullptr;                         // [Bp][32] ... and chars
   // persistent score launch (plain allocations, made by the first such launch)
   int persist_score_max_ = 0;                   // names per call (GK_GEN_PERSIST_SCORE_MAX): opt-in
   bool score_last_persist_ = false;

@@ -953,6 +953,48 @@ struct BeamResetArgs {
 };
 void beam_reset(const BeamResetArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------------ fast bf16 beam search (beam_fast.hip, §4d)
+// beam_head_bf16: logits = h W_fc^T + b_fc of 64 beam rows per workgroup on bf16 MFMA with fp32 accumulation,
+// fused with the log-softmax (score_logprob_f32's operations), the candidate scores s_b + lp[c] and each
+// row's top W of them in the order "score descending, c ascending": the [rows][V] logits never reach memory.
+// A live row offers its W best (only c = prefix[step] while step < plen[n]), a finished row its carry as
+// (s_b, c = 0), a dead row and a row >= N W nothing; unused entries are (-inf, -1).  A workgroup without a
+// live row skips the product.  A forced byte >= V of a name with a live row is taken as 0 and ORs 16 into
+// err[0] (err[1] = the byte, err[2] = the name's first row).  No atomics on the results.
+struct BeamHeadArgs {
+  const u16* h = nullptr;          // [Bp][H] bf16: the top layer's h of this step
+  const u16* Wfc = nullptr;        // [V][H] bf16
+  const float* bfc = nullptr;      // [V]
+  const float* score_in = nullptr; const int* state_in = nullptr;   // [N W]
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][max_len]
+  float* cand_score = nullptr;     // [N W][W]
+  int* cand_chr = nullptr;         // [N W][W]
+  float* lp = nullptr;             // nullable [N W][V]: a live row's log-softmax (tests); other rows are not written
+  unsigned* err = nullptr;         // nullable
+  int N = 0, W = 0, Bp = 0, H = 0, V = 0, step = 0, max_len = 0;   // Bp % 64 == 0, N W <= Bp, W <= min(32, V)
+};
+bool beam_head_supported(int H, int V, int ML);
+void beam_head_bf16(const BeamHeadArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// beam_merge, one wave per name: the W-way merge of the name's W sorted candidate lists on the key
+// (score, -j), j = b V + c, heads only -- beam_select_f32's total order and exactly its outputs.
+struct BeamMergeArgs {
+  const float* cand_score = nullptr; const int* cand_chr = nullptr;   // [N W][W], beam_head_bf16's
+  const float* score_in = nullptr; const int* state_in = nullptr;     // [N W]
+  float* score_out = nullptr; int* parent = nullptr; int* chr = nullptr; int* state_out = nullptr;   // [N W],
+  int* next_id = nullptr;                                                                        // never the inputs
+  int* sel = nullptr;              // nullable [N W]: the winners' flat indices j, -1 for a dead beam (tests)
+  int N = 0, W = 0, V = 0, sos = 0, eos = 0;
+};
+void beam_merge(const BeamMergeArgs& a, hipStream_t s);
+// beam_reorder for the fast loop: the same gather, and per layer hb_dst = the gathered fp32 row rounded to
+// bf16 -- what gru_fwd_step stored beside that fp32 row (h_bf = f2bf(h_f) in every step kernel), so the next
+// step's MFMA reads the bytes the parent's step wrote; a dead beam's row is zero in both.
+struct BeamReorderBf16Args : BeamReorderArgs {
+  u16* hb_dst[4] = {nullptr, nullptr, nullptr, nullptr};   // [.][H] the next step's bf16 input states
+};
+void beam_reorder_bf16(const BeamReorderBf16Args& a, hipStream_t s);
+
 // ------------------------------------------------------------------ generic GEMM
 // C[M][N] (+)= A[M][K] · B[N][K]^T  (bf16 in, fp32 accumulate), both operands K-contiguous.
 struct GemmArgs {

@@ -345,7 +345,8 @@ class HipGenerator:
             raise RuntimeError("HipGenerator.score: device token counts differ from the host's")
         return res
 
-    def beam_search(self, prefix=None, width: int = 4, count: Optional[int] = None, constraints=None) -> "BeamResult":
+    def beam_search(self, prefix=None, width: int = 4, count: Optional[int] = None, constraints=None,
+                    fast: bool = False) -> "BeamResult":
         """The ``width`` most probable output rows per prefix, in order (the rule: cpu_ref.beam_search,
         docs/DESIGN.md §4d).  ``prefix``: a string, a list of strings, or None for ``count`` (default 1)
         empty prefixes.  Always exact fp32 arithmetic, whatever ``precision`` this generator samples
@@ -355,9 +356,25 @@ class HipGenerator:
         a call runs batches of floor(persist_beam / width) prefixes as one persistent launch each (docs/DESIGN.md
         §4d); a constrained one does so when ``persist_constraints`` covers the batch's rows too, else
         that batch keeps the graph.  A width outside [1, min(32, vocab)], a bad prefix or constraint and max_len > 64
-        raise ValueError before anything is launched."""
+        raise ValueError before anything is launched.
+        ``fast=True`` (opt-in; docs/DESIGN.md §4d "Fast bf16 beam search"; the rule:
+        cpu_ref.beam_search(round_operands=True)): the same outputs and the same rule from the bf16 MFMA step
+        kernels and a fused logits + log-softmax + top-``width`` head -- every product on bf16 operands with
+        fp32 accumulation, no logits in memory.  Not bit-faithful to fp32.  Only precision "bf16" holds the
+        operands: the other modes, constraints beside ``fast``, vocab % 64 != 0, vocab > 512 and a step shape
+        the kernels do not cover raise ValueError before anything is launched.  A fast call never takes the
+        persistent beam launch."""
         pre, plen = cpu_ref.beam_inputs(self.cfg, prefix, width, count)
         N, W, ML = pre.shape[0], int(width), self.cfg.max_len
+        if fast:
+            if self.precision != "bf16":
+                raise ValueError('beam_search(fast=True) needs precision "bf16" (only that mode holds the bf16 '
+                                 f"operands), got {self.precision!r}")
+            if constraints is not None:
+                raise ValueError("beam_search(fast=True) takes no constraints (they search in exact fp32)")
+            if not self.C.beam_head_supported(pad_config(self.cfg).hidden, self.cfg.vocab, ML):
+                raise ValueError(f"beam_search(fast=True) needs vocab % 64 == 0, vocab <= 512 and max_len <= 64 "
+                                 f"(got vocab {self.cfg.vocab}, max_len {ML})")
         cons = cpu_ref.as_constraints(self.cfg, N, constraints)
         cpu_ref.check_prefix_allowed(cons, pre, plen)
         if N == 0:
@@ -372,8 +389,17 @@ class HipGenerator:
         if cons is not None:
             held = self._constraint_tensors(cons)
             extra = self._constraint_args(held)
-        self.g.beam(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(), nb.data_ptr(),
-                    self._s(), *extra)
+        if fast:
+            try:
+                self.g.beam_fast(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(),
+                                 nb.data_ptr(), self._s())
+            except RuntimeError as e:   # what gru_fwd_step refuses, raised before any launch
+                if "gru" in str(e) or "beam_fast" in str(e):
+                    raise ValueError(str(e)) from e
+                raise
+        else:
+            self.g.beam(l.data_ptr(), p.data_ptr(), N, W, rows.data_ptr(), logp.data_ptr(), nt.data_ptr(), nb.data_ptr(),
+                        self._s(), *extra)
         err = self.g.read_error()   # synchronises: the prefix tensors stay alive until the call is done
         if err:
             raise RuntimeError(f"HipGenerator.beam_search: device error word {err}")

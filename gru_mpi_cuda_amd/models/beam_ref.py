@@ -370,7 +370,9 @@ def case_model(c: TrajCase):
 
 
 def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64: bool, mut: Optional[str] = None,
-         cons: Optional[cpu_ref.Constraints] = None) -> Out:
+         cons: Optional[cpu_ref.Constraints] = None, rnd=lambda v: v) -> Out:
+    """``rnd``: applied to every h fed to a product (models/beam_fast_ref.py passes the bf16 rounding and
+    params whose matrices are rounded already); the default changes nothing."""
     N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
     dt = torch.float64 if f64 else torch.float32
     npdt = np.float64 if f64 else np.float32
@@ -393,12 +395,12 @@ def _run(params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, f64:
         inp = p["embedding"][cur]
         new = []
         for k in range(cfg.layers):
-            gi = inp @ p[f"weight_ih_l{k}"].T + p[f"bias_ih_l{k}"]
-            gh = hs[k] @ p[f"weight_hh_l{k}"].T + p[f"bias_hh_l{k}"]
+            gi = rnd(inp) @ p[f"weight_ih_l{k}"].T + p[f"bias_ih_l{k}"]
+            gh = rnd(hs[k]) @ p[f"weight_hh_l{k}"].T + p[f"bias_hh_l{k}"]
             hk, _ = cpu_ref._gates(gi, gh, hs[k])
             new.append(hk)
             inp = hk
-        logits = (inp @ p["fc.weight"].T + p["fc.bias"]).numpy()
+        logits = (rnd(inp) @ p["fc.weight"].T + p["fc.bias"]).numpy()
         lp = log_softmax(logits, f64).reshape(N, W, V)
         gather = np.arange(N * W)
         nrows, nscore = np.zeros_like(rows), np.full_like(score, -np.inf)

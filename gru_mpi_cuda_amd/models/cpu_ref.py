@@ -1699,22 +1699,28 @@ def beam_select(lp: np.ndarray, score: np.ndarray, state: np.ndarray, forced_cha
 
 
 def beam_search(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None,
-                constraints=None) -> BeamResult:
+                constraints=None, round_operands: bool = False) -> BeamResult:
     """The rule above in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli beam``).
     ``constraints``: a Constraints object for the N prefixes or a dict of ``make_constraints`` keywords:
-    the W most probable names that satisfy it."""
+    the W most probable names that satisfy it.
+    ``round_operands``: the twin of ``HipGenerator.beam_search(fast=True)`` (docs/DESIGN.md §4d "Fast bf16 beam
+    search"): ``forward``'s bf16 operand rounding -- every weight matrix, the embedding and every h fed to a
+    product; the biases, the carried state, the gates and the softmax are not rounded."""
     pre, plen = beam_inputs(cfg, prefix, width, count)
     cons = as_constraints(cfg, pre.shape[0], constraints)
     check_prefix_allowed(cons, pre, plen)
-    return beam_search_rule(params, cfg, pre, plen, int(width), cons)
+    return beam_search_rule(params, cfg, pre, plen, int(width), cons, round_operands)
 
 
 def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int,
-                     cons: Optional[Constraints] = None) -> BeamResult:
+                     cons: Optional[Constraints] = None, round_operands: bool = False) -> BeamResult:
     """The rule itself on validated inputs (``beam_inputs`` / ``as_constraints``).  It has no width limit
     of its own -- the limits of ``beam_inputs`` are the device's -- so a width that holds every candidate
     makes the search exhaustive (tests/test_constraints.py)."""
     N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
+    rnd = bf16_round if round_operands else (lambda v: v)
+    if round_operands:   # the weight matrices once; h at every product below
+        params = {k: (rnd(v) if v.dim() == 2 else v) for k, v in params.items()}
     dt = params["fc.weight"].dtype
     npdt = np.float64 if dt == torch.float64 else np.float32
     rows = np.zeros((N, W, ML + 1), np.uint8)
@@ -1734,11 +1740,11 @@ def beam_search_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.n
     for l in range(ML):
         inp = params["embedding"][cur]
         for k in range(cfg.layers):
-            gi = inp @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
-            gh = hs[k] @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
+            gi = rnd(inp) @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
+            gh = rnd(hs[k]) @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
             hs[k], _ = _gates(gi, gh, hs[k])
             inp = hs[k]
-        logits = inp @ params["fc.weight"].T + params["fc.bias"]
+        logits = rnd(inp) @ params["fc.weight"].T + params["fc.bias"]
         if dt != torch.float64:
             logits = logits.to(torch.float32)
         lp = torch.log_softmax(logits, -1).numpy().reshape(N, W, V)
