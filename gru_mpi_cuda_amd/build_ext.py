@@ -32,13 +32,14 @@ KERNELS = ["kernels/gru_step.hip", "kernels/gru_seq.hip", "kernels/fc.hip", "ker
            "kernels/gen_persist_soft.hip", "kernels/sbs.hip", "kernels/smc.hip", "kernels/dropout.hip",
            "kernels/gen_persist_beam.hip", "kernels/gen_persist_score.hip", "kernels/gen_persist_sbs.hip",
            "kernels/gen_persist_smc.hip", "kernels/gen_persist_beam_con.hip", "kernels/gen_persist_sbs_con.hip",
-           "kernels/score_fast.hip", "kernels/beam_fast.hip"]
+           "kernels/score_fast.hip", "kernels/beam_fast.hip", "kernels/sbs_fast.hip"]
 # further flags of single sources (part of their objects' stamps and of the source hash)
 _NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FLAG_EXTRA = {"kernels/gen_persist_beam.hip": _NO_PK, "kernels/gen_persist_score.hip": _NO_PK,
                "kernels/gen_persist_sbs.hip": _NO_PK, "kernels/gen_persist_smc.hip": _NO_PK,
                "kernels/gen_persist_beam_con.hip": _NO_PK, "kernels/gen_persist_sbs_con.hip": _NO_PK,
-               "kernels/score_fast.hip": _NO_PK, "kernels/beam_fast.hip": _NO_PK}
+               "kernels/score_fast.hip": _NO_PK, "kernels/beam_fast.hip": _NO_PK,
+               "kernels/sbs_fast.hip": _NO_PK}
 ENGINE = ["runtime/blaslt.cpp", "engine/trainer.cpp", "engine/trainer_seq.cpp", "engine/generator.cpp", "comm/rccl_comm.cpp",
           "comm/watchdog.cpp", "comm/bootstrap.cpp", "data/name_loader.cpp"]
 PYBIND = ["bindings.cpp"]

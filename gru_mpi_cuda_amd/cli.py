@@ -512,16 +512,21 @@ def cmd_distinct(args) -> int:
     else:
         prefixes = [args.prefix or ""]
     kw = dict(seed=args.noise_seed, temperature=args.temperature, constraints=_constraints_from(args))
+    if args.fast and kw["constraints"] is not None:
+        raise SystemExit("--fast takes no constraint flag (constrained names are drawn in exact fp32)")
     if args.cpu or not torch.cuda.is_available():
-        res = cpu_ref.sample_distinct({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width, **kw)
+        res = cpu_ref.sample_distinct({k: v.float() for k, v in params.items()}, cfg, prefixes, args.width,
+                                      round_operands=args.fast, **kw)
     else:
         if args.persist_distinct is not None and not 0 <= args.persist_distinct <= 64:
             raise SystemExit("--persist-distinct needs a row count in [0, 64]")
         if args.persist_constraints is not None and args.persist_constraints < 0:
             raise SystemExit("--persist-constraints needs a count >= 0")
+        # --fast: the bf16 mode holds the operands of the fast loop (docs/DESIGN.md §4i)
         gen = G.HipGenerator(cfg, params, max_batch=max(64, min(4096, len(prefixes) * args.width)),
+                             precision="bf16" if args.fast else "fp32",
                              persist_distinct=args.persist_distinct or 0, persist_constraints=args.persist_constraints or 0)
-        res = gen.sample_distinct(prefixes, args.width, **kw)
+        res = gen.sample_distinct(prefixes, args.width, fast=args.fast, **kw)
     lines = []
     for pre, names, lqs in zip(prefixes, res.names(), res.logq):
         for k, nm in enumerate(names):
@@ -762,6 +767,10 @@ def main(argv=None) -> int:
                     metavar="N", help="HIP path: a constrained batch takes the persistent launch of --persist-distinct when "
                                       "this covers its rows too (bare flag: 64; opt-in; docs/DESIGN.md §4i); no "
                                       "effect with --cpu")
+    ds.add_argument("--fast", action="store_true",
+                    help="bf16 fast distinct names: bf16 MFMA products with fp32 accumulation and a fused logits / Gumbel "
+                         "top-W head (docs/DESIGN.md §4i); an exact sample from the bf16-operand model; no constraint "
+                         "flag; with --cpu its twin (bf16-rounded operands)")
     ds.add_argument("--out", default=None, help="prefix, draw, name and log-prob per line, tab-separated")
     ds.add_argument("--cpu", action="store_true", help="cpu_ref.sample_distinct in fp32 instead of the HIP generator")
     ds.add_argument("--seed", dest="noise_seed", type=int, default=0,

@@ -291,6 +291,15 @@ PYBIND11_MODULE(_C, m) {
          py::arg("stream"), py::arg("allow_tab") = (uintptr_t)0, py::arg("allow_idx") = (uintptr_t)0,
          py::arg("allow_rows") = 0, py::arg("allow_next") = (uintptr_t)0, py::arg("allow_start") = (uintptr_t)0)
       .def("distinct_graphs", &Generator::distinct_graphs)
+      .def("distinct_fast", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, unsigned long long seed,
+                               unsigned long long start, uintptr_t inv_t, uintptr_t rows, uintptr_t logq, uintptr_t gumbel,
+                               uintptr_t n_tok, uintptr_t n_found, uintptr_t s) {
+        g.distinct_fast(Pp<const int>(plen), Pp<const unsigned char>(prefix), N, W, seed, start, Pp<const float>(inv_t),
+                        Pp<unsigned char>(rows), Pp<float>(logq), Pp<float>(gumbel), Pp<int>(n_tok), Pp<int>(n_found), S(s));
+      }, py::arg("plen"), py::arg("prefix"), py::arg("N"), py::arg("W"), py::arg("seed"), py::arg("start"),
+         py::arg("inv_t"), py::arg("rows"), py::arg("logq"), py::arg("gumbel"), py::arg("n_tok"), py::arg("n_found"),
+         py::arg("stream"))
+      .def("distinct_fast_graphs", &Generator::distinct_fast_graphs)
       .def("conditional", [](Generator& g, uintptr_t plen, uintptr_t prefix, int N, int W, unsigned long long seed,
                              unsigned long long start, float thr, uintptr_t inv_t, uintptr_t rows, uintptr_t logw,
                              uintptr_t logq, uintptr_t n_tok, uintptr_t n_res, uintptr_t s, uintptr_t allow_tab,
@@ -1257,6 +1266,34 @@ PYBIND11_MODULE(_C, m) {
     a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0);
     a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
     beam_merge(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  // the fast bf16 distinct names' kernels on caller-owned buffers (tests/test_sbs_fast_kernel_gpu.py)
+  m.def("sbs_head_supported", &sbs_head_supported);
+  m.def("sbs_head", [](py::dict d, uintptr_t s) {
+    SbsHeadArgs a;
+    a.h = GP(const u16, d, "h"); a.Wfc = GP(const u16, d, "Wfc"); a.bfc = GP(const float, d, "bfc");
+    a.logq_in = GP(const float, d, "logq_in"); a.G_in = GP(const float, d, "G_in"); a.state_in = GP(const int, d, "state_in");
+    a.plen = GP(const int, d, "plen"); a.prefix = GP(const unsigned char, d, "prefix");
+    a.seed = GP(const unsigned long long, d, "seed"); a.start = GP(const unsigned long long, d, "start");
+    a.inv_t = GP(const float, d, "inv_t");
+    a.cand_gt = GP(float, d, "cand_gt"); a.cand_chr = GP(int, d, "cand_chr"); a.cand_psi = GP(float, d, "cand_psi");
+    a.lq = GP(float, d, "lq"); a.gt = GP(float, d, "gt"); a.zmax = GP(float, d, "zmax"); a.err = GP(unsigned, d, "err");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.Bp = get<int>(d, "Bp", 0); a.H = get<int>(d, "H", 0);
+    a.V = get<int>(d, "V", 0); a.step = get<int>(d, "step", 0); a.max_len = get<int>(d, "max_len", 0);
+    sbs_head_bf16(a, S(s));
+    HIP_LAUNCH_CHECK();
+  });
+  m.def("sbs_merge", [](py::dict d, uintptr_t s) {
+    SbsMergeArgs a;
+    a.cand_gt = GP(const float, d, "cand_gt"); a.cand_chr = GP(const int, d, "cand_chr"); a.cand_psi = GP(const float, d, "cand_psi");
+    a.logq_in = GP(const float, d, "logq_in"); a.G_in = GP(const float, d, "G_in"); a.state_in = GP(const int, d, "state_in");
+    a.logq_out = GP(float, d, "logq_out"); a.G_out = GP(float, d, "G_out"); a.parent = GP(int, d, "parent");
+    a.chr = GP(int, d, "chr"); a.state_out = GP(int, d, "state_out"); a.next_id = GP(int, d, "next_id");
+    a.sel = GP(int, d, "sel");
+    a.N = get<int>(d, "N", 0); a.W = get<int>(d, "W", 0); a.V = get<int>(d, "V", 0);
+    a.sos = get<int>(d, "sos", 0); a.eos = get<int>(d, "eos", 0);
+    sbs_merge(a, S(s));
     HIP_LAUNCH_CHECK();
   });
   m.def("beam_reorder_bf16", [](py::dict d, uintptr_t s) {

@@ -1289,11 +1289,11 @@ static FwdStepArgs fast_step_shape(int Bp, int H, int algo, bool fused) {
   return a;
 }
 
-// The fast beam loop for n names of W beams: 1 + ML (L steps + head + merge + reorder) launches, a single
-// chain.  Fixed slots as record_beam: a step reads the A slots (fp32 and bf16; before step 0 the zero buffer)
+// The fast beam loop for n names of W beams (distinct: the fast distinct loop for n names of W slots, the
+// selection swapped): 1 + ML (L steps + head + merge + reorder) launches, a single chain.  Fixed slots as record_beam: a step reads the A slots (fp32 and bf16; before step 0 the zero buffer)
 // and writes the B slots, the reorder gathers B -> A.  Scores, states, lengths and output rows alternate
 // between two sets by step parity; the result is in set ML & 1.  No saves: sr .. s16 stay null.
-void Generator::record_beam_fast(int n, int W, hipStream_t s) {
+void Generator::record_beam_fast(int n, int W, hipStream_t s, bool distinct) {
   const int H = d_.H, L = d_.L, V = d_.V, ML = d_.max_len;
   const int Bp = fast_pad(n * W);
   BeamResetArgs r;
@@ -1315,17 +1315,35 @@ void Generator::record_beam_fast(int n, int W, hipStream_t s) {
       a.Bp = Bp; a.H = H; a.algo = step_algo_;
       gru_fwd_step(a, s);
     }
-    BeamHeadArgs q;
-    q.h = fbhbB_[L - 1]; q.Wfc = Wfc_; q.bfc = P("fc.bias");
-    q.score_in = fbscore_[cur]; q.state_in = fbstate_[cur]; q.plen = fbplen_; q.prefix = fbprefix_;
-    q.cand_score = fbcs_; q.cand_chr = fbcc_; q.err = err_;
-    q.N = n; q.W = W; q.Bp = Bp; q.H = H; q.V = V; q.step = st; q.max_len = ML;
-    beam_head_bf16(q, s);
-    BeamMergeArgs m;
-    m.cand_score = fbcs_; m.cand_chr = fbcc_; m.score_in = fbscore_[cur]; m.state_in = fbstate_[cur];
-    m.score_out = fbscore_[nxt]; m.parent = fbparent_; m.chr = fbchr_; m.state_out = fbstate_[nxt]; m.next_id = fbnext_;
-    m.N = n; m.W = W; m.V = V; m.sos = d_.sos; m.eos = d_.eos;
-    beam_merge(m, s);
+    if (distinct) {   // §4i: the same loop, ranked by truncated Gumbel-perturbed log-probabilities
+      SbsHeadArgs q;
+      q.h = fbhbB_[L - 1]; q.Wfc = Wfc_; q.bfc = P("fc.bias");
+      q.logq_in = fbscore_[cur]; q.G_in = st == 0 ? fbscore_[0] : dfG_[cur];   // before step 0: G = logq = 0 / -inf
+      q.state_in = fbstate_[cur]; q.plen = fbplen_; q.prefix = fbprefix_;
+      q.seed = dfwords_; q.start = dfwords_ + 1; q.inv_t = dfinv_;
+      q.cand_gt = fbcs_; q.cand_chr = fbcc_; q.cand_psi = dfpsi_; q.err = err_;
+      q.N = n; q.W = W; q.Bp = Bp; q.H = H; q.V = V; q.step = st; q.max_len = ML;
+      sbs_head_bf16(q, s);
+      SbsMergeArgs m;
+      m.cand_gt = fbcs_; m.cand_chr = fbcc_; m.cand_psi = dfpsi_;
+      m.logq_in = q.logq_in; m.G_in = q.G_in; m.state_in = fbstate_[cur];
+      m.logq_out = fbscore_[nxt]; m.G_out = dfG_[nxt]; m.parent = fbparent_; m.chr = fbchr_;
+      m.state_out = fbstate_[nxt]; m.next_id = fbnext_;
+      m.N = n; m.W = W; m.V = V; m.sos = d_.sos; m.eos = d_.eos;
+      sbs_merge(m, s);
+    } else {
+      BeamHeadArgs q;
+      q.h = fbhbB_[L - 1]; q.Wfc = Wfc_; q.bfc = P("fc.bias");
+      q.score_in = fbscore_[cur]; q.state_in = fbstate_[cur]; q.plen = fbplen_; q.prefix = fbprefix_;
+      q.cand_score = fbcs_; q.cand_chr = fbcc_; q.err = err_;
+      q.N = n; q.W = W; q.Bp = Bp; q.H = H; q.V = V; q.step = st; q.max_len = ML;
+      beam_head_bf16(q, s);
+      BeamMergeArgs m;
+      m.cand_score = fbcs_; m.cand_chr = fbcc_; m.score_in = fbscore_[cur]; m.state_in = fbstate_[cur];
+      m.score_out = fbscore_[nxt]; m.parent = fbparent_; m.chr = fbchr_; m.state_out = fbstate_[nxt]; m.next_id = fbnext_;
+      m.N = n; m.W = W; m.V = V; m.sos = d_.sos; m.eos = d_.eos;
+      beam_merge(m, s);
+    }
     BeamReorderBf16Args o;
     for (int l = 0; l < L; ++l) { o.h_src[l] = fbhfB_[l]; o.h_dst[l] = fbhfA_[l]; o.hb_dst[l] = fbhbA_[l]; }
     o.parent = fbparent_; o.chr = fbchr_; o.next_id = fbnext_;
@@ -1382,6 +1400,73 @@ void Generator::beam_fast(const int* plen, const unsigned char* prefix, int N, i
     HIP_CHECK(hipMemcpyAsync(logp + r0, fbscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_tok + r0, fblen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
     HIP_CHECK(hipMemcpyAsync(n_beams + start, fbnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+  }
+}
+
+// ------------------------------------------------------------------------- fast bf16 distinct names
+// What the fast distinct loop needs beside beam_fast()'s buffers, sized like them.
+void Generator::distinct_fast_alloc() {
+  if (dfready_) return;
+  const size_t B = fast_pad(Bmax_);
+  const size_t og0 = dfarena_.reserve(B * 4), og1 = dfarena_.reserve(B * 4), oinv = dfarena_.reserve(B * 4);
+  const size_t opsi = dfarena_.reserve(B * 32 * 4), ow = dfarena_.reserve(16);
+  dfarena_.commit();
+  dfG_[0] = dfarena_.get<float>(og0); dfG_[1] = dfarena_.get<float>(og1); dfinv_ = dfarena_.get<float>(oinv);
+  dfpsi_ = dfarena_.get<float>(opsi); dfwords_ = dfarena_.get<unsigned long long>(ow);
+  dfready_ = true;
+}
+
+void Generator::distinct_fast(const int* plen, const unsigned char* prefix, int N, int W, unsigned long long seed,
+                              unsigned long long start, const float* inv_t, unsigned char* rows, float* logq,
+                              float* gumbel, int* n_tok, int* n_found, hipStream_t s) {
+  GK_TRACE("gk.distinct_fast");
+  const int ML = d_.max_len;
+  if (d_.fp32) throw std::runtime_error("Generator::distinct_fast needs the bf16 mode (only it holds the bf16 operands)");
+  if (W < 1 || W > 32 || W > d_.V) throw std::runtime_error("Generator::distinct_fast needs 1 <= width <= min(32, vocab)");
+  if (!sbs_head_supported(d_.H, d_.V, ML))
+    throw std::runtime_error("Generator::distinct_fast needs vocab % 64 == 0, vocab <= 512 and max_len <= 64");
+  if (d_.max_batch < W) throw std::runtime_error("Generator::distinct_fast needs max_batch >= width");
+  if (d_.L > 4) throw std::runtime_error("Generator::distinct_fast needs at most 4 layers");
+  if (d_.sos < 0 || d_.sos >= d_.V) throw std::runtime_error("Generator::distinct_fast needs 0 <= sos < vocab");
+  if (!plen || !prefix || !inv_t || !rows || !logq || !gumbel || !n_tok || !n_found)
+    throw std::runtime_error("Generator::distinct_fast: plen, prefix, inv_t, rows, logq, gumbel, n_tok and n_found are required");
+  if (N <= 0) return;
+  const int nb = d_.max_batch / W, fin = ML & 1;
+  for (int b0 = 0; b0 < N; b0 += nb) {   // what gru_fwd_step refuses, before anything is launched
+    const int Bp = fast_pad(std::min(nb, N - b0) * W);
+    (void)gru_fwd_step_plan(fast_step_shape(Bp, d_.H, step_algo_, false));
+    if (d_.L > 1) (void)gru_fwd_step_plan(fast_step_shape(Bp, d_.H, step_algo_, true));
+  }
+  beam_fast_alloc();       // first call: allocates (and synchronises) before anything is captured
+  distinct_fast_alloc();
+  HIP_CHECK(hipMemsetAsync(err_, 0, 16, s));   // the error word covers the whole call, as in distinct()
+  err_clean_ = false;
+  distinct_last_persist_ = false;
+  for (int b0 = 0; b0 < N; b0 += nb) {
+    const int n = std::min(nb, N - b0);
+    HIP_CHECK(hipMemcpyAsync(fbplen_, plen + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(fbprefix_, prefix + (size_t)b0 * ML, (size_t)n * ML, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(dfinv_, inv_t + b0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    sbs_stage(dfwords_, seed, dfwords_ + 1, start + (unsigned long long)b0, s);   // name i draws at start + b0 + i
+    HIP_LAUNCH_CHECK();
+    if (use_graph_) {
+      auto& g = dfgraphs_[std::make_pair(n, W)];
+      if (!g) {
+        g.reset(new Graph());
+        g->begin(cap_);
+        record_beam_fast(n, W, cap_, true);
+        g->end(cap_);
+      }
+      g->launch(s);
+    } else {
+      record_beam_fast(n, W, s, true);
+    }
+    const size_t r0 = (size_t)b0 * W, nr = (size_t)n * W;
+    HIP_CHECK(hipMemcpyAsync(rows + r0 * (ML + 1), fbrows_[fin], nr * (ML + 1), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(logq + r0, fbscore_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(gumbel + r0, dfG_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_tok + r0, fblen_[fin], nr * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(n_found + b0, fbnb_, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
   }
 }
 

@@ -225,8 +225,21 @@ class Generator {
   void beam_fast(const int* plen, const unsigned char* prefix, int N, int W, unsigned char* rows, float* logp,
                  int* n_tok, int* n_beams, hipStream_t s);
   int beam_fast_graphs() const { return (int)bfgraphs_.size(); }
-  // 0 until the first beam(); grows when the first beam_fast() commits its buffers
-  size_t beam_workspace_bytes() const { return barena_.bytes() + bfarena_.bytes(); }
+  // distinct() on the bf16 operands (docs/DESIGN.md §4i "Fast bf16 distinct names"; opt-in; the same arrays, states,
+  // noise words and total order, the rule: cpu_ref.sample_distinct(round_operands=True)).  beam_fast()'s loop on
+  // beam_fast()'s buffers with sbs_head_bf16 and sbs_merge as the selection: per char step L gru_fwd_step
+  // launches, the head, the merge and beam_reorder_bf16, L + 3 launches against 3 L + 2, no logits in memory.
+  // The same batches as beam_fast(); one recording per (names, W) that bakes in no seed, index or temperature
+  // (sbs_stage writes them to device words).  What only this loop needs -- two G buffers, the candidates' psi,
+  // 1 / T and the two words -- lives in an arena of its own, committed by the first call.  Only the bf16 mode
+  // holds the operands: the other modes throw, as does a shape the kernels do not cover, before anything is
+  // launched.  No constraints; never the persistent distinct launch.
+  void distinct_fast(const int* plen, const unsigned char* prefix, int N, int W, unsigned long long seed,
+                     unsigned long long start, const float* inv_t, unsigned char* rows, float* logq, float* gumbel,
+                     int* n_tok, int* n_found, hipStream_t s);
+  int distinct_fast_graphs() const { return (int)dfgraphs_.size(); }
+  // 0 until the first beam(); grows when the first beam_fast() / distinct_fast() commits its buffers
+  size_t beam_workspace_bytes() const { return barena_.bytes() + bfarena_.bytes() + dfarena_.bytes(); }
   int beam_graphs() const { return (int)bgraphs_.size(); }          // recordings so far, one per (names, W, constrained)
   int ctl_graphs() const { return (int)cgraphs_.size(); }           // ... of the controlled per-char graph, per (n, constrained)
   int automaton_graphs() const { return (int)(agraphs_.size() + abgraphs_.size()); }   // ... with an automaton
@@ -283,7 +296,9 @@ class Generator {
   void record_score_fast(int Bp, hipStream_t s);
   void beam_alloc();
   void beam_fast_alloc();
-  void record_beam_fast(int n, int W, hipStream_t s);
+  // distinct: sbs_head_bf16 / sbs_merge as the selection (G by step parity, step 0 reads the reset scores as G)
+  void record_beam_fast(int n, int W, hipStream_t s, bool distinct = false);
+  void distinct_fast_alloc();
   // the beam loop's selection: beam_select_f32; sbs_select_f32 (G by step parity, step 0 reads the reset scores
   // as G); smc_select_f32 (logw by step parity, step 0 reads the reset scores as logw)
   enum class BeamSelect { kBeam, kDistinct, kConditional };
@@ -420,6 +435,14 @@ class Generator {
   unsigned char* fbprefix_ = nullptr;           // [Bp][ML]
   float* fbcs_ = nullptr;                       // [Bp][32] the head's candidate scores ([rows][W] of a recording)
   int* fbcc_ = nullptr;                         // [Bp][32] ... and chars
+  // fast bf16 distinct names: beam_fast()'s buffers plus these (committed by the first distinct_fast() call)
+  Arena dfarena_;
+  bool dfready_ = false;
+  std::map<std::pair<int, int>, std::unique_ptr<Graph>> dfgraphs_;   // keyed by (names, W)
+  float* dfG_[2] = {nullptr, nullptr};          // [Bp] x2 the slots' perturbed values, by step parity
+  float* dfinv_ = nullptr;                      // [Bp] the current batch's 1 / T
+  float* dfpsi_ = nullptr;                      // [Bp][32] the head's candidate logq ([rows][W] of a recording)
+  unsigned long long* dfwords_ = nullptr;       // [2] the call's seed, the current batch's first global index
   // persistent score launch (plain allocations, made by the first such launch)
   int persist_score_max_ = 0;                   // names per call (GK_GEN_PERSIST_SCORE_MAX): opt-in
   bool score_last_persist_ = false;

@@ -995,6 +995,48 @@ struct BeamReorderBf16Args : BeamReorderArgs {
 };
 void beam_reorder_bf16(const BeamReorderBf16Args& a, hipStream_t s);
 
+// ------------------------------------------------------------------ fast bf16 distinct names (sbs_fast.hip, §4i)
+// sbs_head_bf16: beam_head_bf16's product, geometry and states with sbs_select_f32's steps on the accumulators
+// (SbsSelectArgs' comment: y = x * inv_t[n], lq, psi = logq_b + lq[c], the Philox word of child j = b V + c,
+// g = psi + gum, Z, Gt) and each row's top W candidates in the order "Gt descending, c ascending".  A live row
+// offers its W best (only c = prefix[step] while step < plen[n]: Gt = G_b, psi = logq_b), a finished row its
+// carry as (G_b, c = 0, logq_b), a dead row and a row >= N W nothing; unused entries are (-inf, -1, -inf).  A
+// workgroup without a live row skips the product, unless lq is asked for.  A forced byte >= V of a name with a
+// live row is taken as 0 and ORs 16 into err[0] (err[1] = the byte, err[2] = the name's first row).
+struct SbsHeadArgs {
+  const u16* h = nullptr;          // [Bp][H] bf16: the top layer's h of this step
+  const u16* Wfc = nullptr;        // [V][H] bf16
+  const float* bfc = nullptr;      // [V]
+  const float* logq_in = nullptr; const float* G_in = nullptr; const int* state_in = nullptr;   // [N W]
+  const int* plen = nullptr;               // [N]
+  const unsigned char* prefix = nullptr;   // [N][max_len]
+  const unsigned long long* seed = nullptr;    // one word: the Philox key
+  const unsigned long long* start = nullptr;   // one word: the global index of name 0 of this launch
+  const float* inv_t = nullptr;            // [N] 1 / temperature
+  float* cand_gt = nullptr;        // [N W][W]
+  int* cand_chr = nullptr;         // [N W][W]
+  float* cand_psi = nullptr;       // [N W][W]: the candidates' logq
+  float* lq = nullptr;             // nullable [N W][V]: every row's sampler log-probabilities (tests)
+  float* gt = nullptr;             // nullable [N W][V]: Gt, NaN where not offered (tests)
+  float* zmax = nullptr;           // nullable [N W]: Z, NaN for a row that offers no child (tests)
+  unsigned* err = nullptr;         // nullable
+  int N = 0, W = 0, Bp = 0, H = 0, V = 0, step = 0, max_len = 0;   // Bp % 64 == 0, N W <= Bp, W <= min(32, V)
+};
+bool sbs_head_supported(int H, int V, int ML);
+void sbs_head_bf16(const SbsHeadArgs& a, hipStream_t s);   // throws before launching what is unsupported
+// sbs_merge, one wave per name: the W-way merge of the name's W sorted candidate lists on the key (Gt, -j),
+// j = b V + c, heads only -- sbs_select_f32's total order and exactly its outputs: logq_out = the winner's psi
+// bit for bit, G_out = its Gt; a finished parent's carry keeps logq_in / G_in.
+struct SbsMergeArgs {
+  const float* cand_gt = nullptr; const int* cand_chr = nullptr; const float* cand_psi = nullptr;   // [N W][W]
+  const float* logq_in = nullptr; const float* G_in = nullptr; const int* state_in = nullptr;       // [N W]
+  float* logq_out = nullptr; float* G_out = nullptr; int* parent = nullptr; int* chr = nullptr;     // [N W],
+  int* state_out = nullptr; int* next_id = nullptr;                                                 // never the inputs
+  int* sel = nullptr;              // nullable [N W]: the winners' flat indices j, -1 for a dead slot (tests)
+  int N = 0, W = 0, V = 0, sos = 0, eos = 0;
+};
+void sbs_merge(const SbsMergeArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------------ generic GEMM
 // C[M][N] (+)= A[M][K] · B[N][K]^T  (bf16 in, fp32 accumulate), both operands K-contiguous.
 struct GemmArgs {

@@ -407,7 +407,7 @@ class HipGenerator:
 
 
     def sample_distinct(self, prefix=None, width: int = 4, count: Optional[int] = None, *, seed: int = 0, start: int = 0,
-                        temperature=None, constraints=None, **excluded) -> "DistinctResult":
+                        temperature=None, constraints=None, fast: bool = False, **excluded) -> "DistinctResult":
         """``width`` distinct output rows per prefix, an exact sample without replacement in draw order from
         the distribution ``generate`` samples from with the same ``temperature`` / ``prefix`` / ``constraints``
         -- stochastic beam search (the rule: cpu_ref.sample_distinct, docs/DESIGN.md §4i).  ``logq`` is what
@@ -418,8 +418,25 @@ class HipGenerator:
         persistent launch each (docs/DESIGN.md §4i); a constrained one does so when ``persist_constraints`` covers
         the batch's rows too, else it keeps the graph.  Always exact fp32
         arithmetic; precision "bf16" is refused (ValueError), as are top_k, top_p, temperature 0 and the soft
-        controls, before anything is launched."""
-        if self.precision == "bf16":
+        controls, before anything is launched.
+        ``fast=True`` (opt-in; docs/DESIGN.md §4i "Fast bf16 distinct names"; the rule:
+        cpu_ref.sample_distinct(round_operands=True)): the same outputs, the same rule and the same noise words
+        from the bf16 MFMA step kernels and a fused logits + Gumbel top-``width`` head -- every product on bf16
+        operands with fp32 accumulation, no logits in memory.  An exact sample without replacement from the
+        bf16-operand model's distribution, the one ``score(fast=True)`` scores under; not bit-faithful to fp32.
+        Only precision "bf16" holds the operands: the other modes, constraints beside ``fast``, vocab % 64 != 0,
+        vocab > 512 and a step shape the kernels do not cover raise ValueError before anything is launched.  A
+        fast call never takes the persistent distinct launch."""
+        if fast:
+            if self.precision != "bf16":
+                raise ValueError('sample_distinct(fast=True) needs precision "bf16" (only that mode holds the bf16 '
+                                 f"operands), got {self.precision!r}")
+            if constraints is not None:
+                raise ValueError("sample_distinct(fast=True) takes no constraints (they sample in exact fp32)")
+            if not self.C.sbs_head_supported(pad_config(self.cfg).hidden, self.cfg.vocab, self.cfg.max_len):
+                raise ValueError(f"sample_distinct(fast=True) needs vocab % 64 == 0, vocab <= 512 and max_len <= 64 "
+                                 f"(got vocab {self.cfg.vocab}, max_len {self.cfg.max_len})")
+        elif self.precision == "bf16":
             raise ValueError('sample_distinct needs precision "fp32" or "bf16x3" (it runs exact fp32; the bf16 mode '
                              "samples from another distribution)")
         pre, plen, inv, seed, start = cpu_ref.distinct_inputs(self.cfg, prefix, width, count, seed, start, temperature,
@@ -442,8 +459,17 @@ class HipGenerator:
         if cons is not None:
             held = self._constraint_tensors(cons)
             extra = self._constraint_args(held)
-        self.g.distinct(l.data_ptr(), p.data_ptr(), N, W, seed, start, it.data_ptr(), rows.data_ptr(), logq.data_ptr(),
-                        gum.data_ptr(), nt.data_ptr(), nf.data_ptr(), self._s(), *extra)
+        if fast:
+            try:
+                self.g.distinct_fast(l.data_ptr(), p.data_ptr(), N, W, seed, start, it.data_ptr(), rows.data_ptr(),
+                                     logq.data_ptr(), gum.data_ptr(), nt.data_ptr(), nf.data_ptr(), self._s())
+            except RuntimeError as e:   # what gru_fwd_step refuses, raised before any launch
+                if "gru" in str(e) or "distinct_fast" in str(e):
+                    raise ValueError(str(e)) from e
+                raise
+        else:
+            self.g.distinct(l.data_ptr(), p.data_ptr(), N, W, seed, start, it.data_ptr(), rows.data_ptr(), logq.data_ptr(),
+                            gum.data_ptr(), nt.data_ptr(), nf.data_ptr(), self._s(), *extra)
         err = self.g.read_error()   # synchronises: the input tensors stay alive until the call is done
         if err:
             raise RuntimeError(f"HipGenerator.sample_distinct: device error word {err}")

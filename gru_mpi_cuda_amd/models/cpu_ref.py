@@ -1989,21 +1989,29 @@ def distinct_inputs(cfg: GRUConfig, prefix=None, width: int = 4, count: Optional
 
 
 def sample_distinct(params: Params, cfg: GRUConfig, prefix=None, width: int = 4, count: Optional[int] = None, *,
-                    seed: int = 0, start: int = 0, temperature=None, constraints=None, **excluded) -> DistinctResult:
+                    seed: int = 0, start: int = 0, temperature=None, constraints=None, round_operands: bool = False,
+                    **excluded) -> DistinctResult:
     """``width`` distinct names per prefix, an exact sample without replacement in draw order (the rule
     above) in the dtype of ``params`` (fp64 params: the oracle; the CPU path of ``cli distinct``).  Name n
-    of the call has the global index ``start + n``: its noise does not depend on how a job is cut up."""
+    of the call has the global index ``start + n``: its noise does not depend on how a job is cut up.
+
+    ``round_operands``: the twin of ``HipGenerator.sample_distinct(fast=True)`` (docs/DESIGN.md §4i "Fast bf16
+    distinct names"): ``forward``'s bf16 operand rounding -- every weight matrix, the embedding and every h where
+    a product reads it; biases, carried state, gates, softmax and noise are not rounded."""
     pre, plen, inv, seed, start = distinct_inputs(cfg, prefix, width, count, seed, start, temperature, **excluded)
     cons = as_constraints(cfg, pre.shape[0], constraints)
     check_prefix_allowed(cons, pre, plen)
-    return sample_distinct_rule(params, cfg, pre, plen, int(width), seed, start, inv, cons)
+    return sample_distinct_rule(params, cfg, pre, plen, int(width), seed, start, inv, cons, round_operands=round_operands)
 
 
 def sample_distinct_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: np.ndarray, W: int, seed: int,
                          start: int, inv_t: np.ndarray, cons=None, mut: Optional[str] = None,
-                         trace: Optional[list] = None) -> DistinctResult:
+                         trace: Optional[list] = None, round_operands: bool = False) -> DistinctResult:
     """The rule itself on validated inputs.  ``trace``: a list that receives every step's ``sbs_step``
-    output (models/sbs_ref.py); ``mut``: a planted defect (there too)."""
+    output (models/sbs_ref.py); ``mut``: a planted defect (there too); ``round_operands``: ``sample_distinct``'s."""
+    rnd = bf16_round if round_operands else (lambda v: v)
+    if round_operands:   # the weight matrices once; h at every product below
+        params = {k: (rnd(v) if v.dim() == 2 else v) for k, v in params.items()}
     N, ML, V, H = pre.shape[0], cfg.max_len, cfg.vocab, cfg.hidden
     dt = params["fc.weight"].dtype
     npdt = np.float64 if dt == torch.float64 else np.float32
@@ -2028,12 +2036,12 @@ def sample_distinct_rule(params: Params, cfg: GRUConfig, pre: np.ndarray, plen: 
         inp = params["embedding"][cur]
         new = []
         for k in range(cfg.layers):
-            gi = inp @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
-            gh = hs[k] @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
+            gi = rnd(inp) @ params[f"weight_ih_l{k}"].T + params[f"bias_ih_l{k}"]
+            gh = rnd(hs[k]) @ params[f"weight_hh_l{k}"].T + params[f"bias_hh_l{k}"]
             hk, _ = _gates(gi, gh, hs[k])
             new.append(hk)
             inp = hk
-        logits = inp @ params["fc.weight"].T + params["fc.bias"]
+        logits = rnd(inp) @ params["fc.weight"].T + params["fc.bias"]
         if dt != torch.float64:
             logits = logits.to(torch.float32)
         x = logits.numpy().reshape(N, W, V)

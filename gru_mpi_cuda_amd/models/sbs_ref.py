@@ -382,13 +382,14 @@ def case_kwargs(c: TrajCase) -> dict:
 
 
 def _run(params, cfg: GRUConfig, prefixes, W: int, f64: bool, seed=0, start=0, temperature=None, constraints=None,
-         mut: Optional[str] = None, unit: str = "top_scale") -> Out:
+         mut: Optional[str] = None, unit: str = "top_scale", round_operands: bool = False) -> Out:
+    """``round_operands``: cpu_ref.sample_distinct's (the fast bf16 twin, models/sbs_fast_ref.py)."""
     pre, plen, inv, seed, start = cpu_ref.distinct_inputs(cfg, list(prefixes), W, None, seed, start, temperature)
     cons = cpu_ref.as_constraints(cfg, pre.shape[0], constraints)
     cpu_ref.check_prefix_allowed(cons, pre, plen)
     p = {k: v.to(torch.float64 if f64 else torch.float32) for k, v in params.items()}
     trace: list = []
-    r = cpu_ref.sample_distinct_rule(p, cfg, pre, plen, W, seed, start, inv, cons, mut, trace)
+    r = cpu_ref.sample_distinct_rule(p, cfg, pre, plen, W, seed, start, inv, cons, mut, trace, round_operands)
     clear = np.stack([_clearance(s, unit) for s in trace], 1)
     scale = np.stack([np.nanmax(np.where(np.isnan(s["top_scale"][:, :W]), 1.0, s["top_scale"][:, :W]), 1) for s in trace], 1)
     return dict(rows=r.rows, logq=r.logq, gumbel=r.gumbel, n_tok=r.n_tok, n_found=r.n_found, clear=clear,
